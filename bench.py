@@ -12,6 +12,11 @@ the whole candidate batch + the planner's running_cost (chamfer to a target clou
 (+ RCCL all-reduce(MAX) of two scalars and all-gather of the per-candidate rewards when N > 1).
 Candidates are independent, so they are sharded over ranks (STRONG scaling: the 1024-candidate batch is fixed);
 the only collective is the all-gather of B/N fp32 costs per rank.
+
+A plain run sets up, warms up, times exactly --steps steps and prints the result line (headline figure, ms_per_step,
+config, reward SHA-256).  --dump-outputs DIR also writes what the last timed step returned (dump_outputs).  Everything
+else - the per-kernel roofline passes, the bf16x3 figure, ms per MPC iteration, the CPU baseline with its parity check
+against the oracle and the reference fixtures, the multi-GPU diagnostics - runs only with --full.
 """
 import argparse
 import json
@@ -31,6 +36,11 @@ def _parser():
     ap.add_argument("--lookahead", type=int, default=2)
     ap.add_argument("--repeat", type=int, default=10)
     ap.add_argument("--chunk", type=int, default=0)
+    ap.add_argument("--full", action="store_true", help="after the headline, also run everything else this bench measures or checks "
+                    "(roofline passes, bf16x3 figure, MPC iteration, CPU baseline + parity check, multi-GPU diagnostics); "
+                    "the --no-* flags below select among those legs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--profile-all", action="store_true", help="HIP-event time every kernel family (adds overhead)")
     ap.add_argument("--no-kernel-profile", action="store_true", help="skip the per-kernel HIP-event pass")
@@ -338,6 +348,32 @@ def cpu_baseline(cloud, task, W, actions, picks, gpu_seqs, ref, tol=1e-5):
     return base, parity
 
 
+DUMP_BYTES = 64 * 10 ** 6                                 # --dump-outputs: all files together
+
+
+def dump_outputs(out_dir, rewards, state_seqs):
+    """--dump-outputs: what the timed path handed its caller in the LAST timed step, for output-for-output comparisons of
+    two builds (same arguments -> same inputs: every generator is seeded).
+      rewards.npy     (B,) float32: the reward vector sharded_candidate_rewards returns (whole batch, gathered)
+      state_seqs.npy  (b, H, N_o, 3) float32: dynamics()'s state_seqs of this rank's shard (the whole batch on one GPU; default
+                      size 49.8 MB).  If they do not fit in DUMP_BYTES, a fixed seeded sample of candidates, sorted, whose
+                      local indices go to state_seqs_candidates.npy (float64).
+    state_seqs: a device tensor; only what is written is copied back."""
+    os.makedirs(out_dir, exist_ok=True)
+    rewards = np.ascontiguousarray(rewards, dtype=np.float32)
+    np.save(os.path.join(out_dir, "rewards.npy"), rewards)
+    room = DUMP_BYTES - rewards.nbytes - 3 * 4096              # (npy headers)
+    b = state_seqs.shape[0]
+    per = state_seqs[0].numel() * 4
+    if b * per <= room:
+        seqs = state_seqs.float().cpu().numpy()
+    else:
+        ids = np.sort(np.random.default_rng(0).choice(b, size=max(1, room // (per + 8)), replace=False))
+        seqs = state_seqs[torch.from_numpy(ids).to(state_seqs.device)].float().cpu().numpy()
+        np.save(os.path.join(out_dir, "state_seqs_candidates.npy"), ids.astype(np.float64))
+    np.save(os.path.join(out_dir, "state_seqs.npy"), np.ascontiguousarray(seqs, dtype=np.float32))
+
+
 def plumbing_only(args, world, rank, local_rank):
     """--plumbing-only: what the launch gave every rank, gathered over gloo and printed by rank 0 as one JSON line.  No GPU, no
     engine import: the CPU check of launch_ranks_if_needed (tests/test_bench_launch.py)."""
@@ -360,7 +396,10 @@ def plumbing_only(args, world, rank, local_rank):
 
 
 def main():
-    args = _parser().parse_args()
+    ap = _parser()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -474,17 +513,23 @@ def main():
     assert int(flag[0].item()) <= task["max_nR"], "a graph exceeded max_nR during the bench"
     assert int(flag[1].item()) <= args.repeat, "an action_repeat exceeded the task config's bound during the bench"
     assert torch.isfinite(costs).all()
+    # the last timed step's results, read before anything else runs on the engine
+    rewards_host = costs.detach().cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, rewards_host, last["seq"])
     # candidates of the timed batch that the CPU leg re-computes with the oracle: first, last and evenly spaced ones
     # (every launch chunk of both streams is hit); their GPU results come from the LAST TIMED step
     # four candidates per worker core (16-core CPU share of a one-GPU box): ~12 s of CPU work
-    n_pick = 0 if args.no_cpu_baseline or dist_on else max(2, min(4 * min(16, os.cpu_count() or 2), hi - lo))
+    n_pick = 0 if not args.full or args.no_cpu_baseline or dist_on else max(2, min(4 * min(16, os.cpu_count() or 2), hi - lo))
     picks = parity_picks(hi - lo, n_pick)
     ref = reference_golden(cloud, task, Wt, actions.numpy(), with_margin=True) if picks else {}
     picks = sorted(set(picks) | {c for c in ref if lo <= c < hi})       # world == 1 here: candidate id == local index
     timed_seqs = last["seq"][picks].cpu().numpy() if picks else None
     tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
     multi = None
-    if dist_on:
+    if dist_on and not args.full:
+        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)                    # the headline: the slowest rank's timed region
+    elif dist_on:
         # diagnostics for a multi-GPU run (not part of `value`): every rank's own wall time of the timed region, and the
         # latency of the step's exchange alone (MAX all-reduce of two scalars + all-gather of the B/N rewards)
         per_rank = [torch.zeros(1, device=dev, dtype=torch.float64) for _ in range(world)]
@@ -520,7 +565,7 @@ def main():
     # ---- roofline pass: the same rollout once more with HIP events around every launch of the profiled kernels, on
     # the stream they are launched on.  Profiling pins the engine to ONE stream: with two chunks sharing the GPU an
     # event-bracketed duration measures the neighbour's kernels too.
-    fams = [] if args.no_kernel_profile else ["edge_enc", "node_prop"] if not args.profile_all else [
+    fams = [] if not args.full or args.no_kernel_profile else ["edge_enc", "node_prop"] if not args.profile_all else [
         "edge_count", "edge_emit", "node_enc", "edge_enc", "node_prop", "node_final", "roll_init", "roll_update", "cost"]
     prof_steps = 1
     eng.reset_stats()
@@ -547,14 +592,15 @@ def main():
             eng.set_profiling([])
         ms_edge_co, n_edge_co = eng.kernel_stats("edge_enc")
         eng.reset_stats()
-    one_step()
-    sync_all()
-    share_counts = eng.share_counts()                       # (base edges, slots served by the shared table, slots encoded per candidate)
-    fwd_executed, fwd_needed = eng.rollout_counts()          # candidate-forwards of that call (this rank's shard)
+    if args.full:
+        one_step()
+        sync_all()
+        share_counts = eng.share_counts()                   # (base edges, slots served by the shared table, slots encoded per candidate)
+        fwd_executed, fwd_needed = eng.rollout_counts()      # candidate-forwards of that call (this rank's shard)
     # ---- secondary figure: the opt-in bf16x3 arithmetic (3-way bf16 split on the bf16 matrix pipe, fp32 accumulate;
     # validated at the same 1e-5 parity bar, tests/test_gpu_more.py).  NOT the headline: `value` is exact fp32.
     dt_b3 = None
-    if not args.no_bf16x3:
+    if args.full and not args.no_bf16x3:
         model.set_precision("bf16x3")
         for _ in range(args.warmup):
             one_step()
@@ -582,14 +628,14 @@ def main():
         assert torch.isfinite(costs_b3).all()
     # ---- ms / MPC iteration (BASELINE metric, second half): sample -> rollout -> running_cost -> MPPI update -> best
     # candidate rolled out again (planner.py:234-277), whole batch in one call, exact fp32
-    lo_lim = torch.tensor([float(cloud[:, 0].min()) - 0.5, float(cloud[:, 2].min()) - 0.5, -3.14, R + 0.5], device=dev)
-    hi_lim = torch.tensor([float(cloud[:, 0].max()) + 0.5, float(cloud[:, 2].max()) + 0.5, 3.14, R + 0.5], device=dev)
-    roll_fn = lambda s, a: ag.dynamics(s, a, model, dev, ppm, _sync=False, _overflow_flag=flag)
-    eval_fn = partial(ag.running_cost, error_func=err_fn, penalty_func=pen_fn, bbox=bbox, group=True if dist_on else None)
-    act0 = actions[0].to(dev)
-    torch.manual_seed(1234)                                        # identical samples on every rank
     ms_mpc = None
-    if not args.no_mpc_iter:
+    if args.full and not args.no_mpc_iter:
+        lo_lim = torch.tensor([float(cloud[:, 0].min()) - 0.5, float(cloud[:, 2].min()) - 0.5, -3.14, R + 0.5], device=dev)
+        hi_lim = torch.tensor([float(cloud[:, 0].max()) + 0.5, float(cloud[:, 2].max()) + 0.5, 3.14, R + 0.5], device=dev)
+        roll_fn = lambda s, a: ag.dynamics(s, a, model, dev, ppm, _sync=False, _overflow_flag=flag)
+        eval_fn = partial(ag.running_cost, error_func=err_fn, penalty_func=pen_fn, bbox=bbox, group=True if dist_on else None)
+        act0 = actions[0].to(dev)
+        torch.manual_seed(1234)                                    # identical samples on every rank
         # (reuse_best_rollout: the best candidate's rollout is taken out of the batch instead of being re-rolled with a batch of
         # one - exact on this engine, and what Planner does by default for the engine's own dynamics(); single rank only)
         ag.mpc_iteration(state0, act0, roll_fn, eval_fn, lo_lim, hi_lim, B, dev, group=True if dist_on else None, reuse_best_rollout=True)
@@ -607,7 +653,26 @@ def main():
         assert torch.isfinite(mpc["reward_seqs"]).all()
     fam_ms = fam_single if fams else {}
     ms_edge, n_edge = fam_ms.get("edge_enc", (0.0, 0))
+    total_steps = B * H * R
     if rank == 0:
+        line = {
+            "metric": "rollout-steps/sec", "value": total_steps * args.steps / dt, "unit": "rollout-steps/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": "BASELINE configs[3]: cloth, 1024 candidates x 20 rollout steps (2 look-ahead x "
+                                   "repeat 10) x 2025+1 particles, radius graph rebuilt every step",
+                       "candidates": B, "horizon": H * R, "particles": N_o + 1,
+                       "parallelism": f"candidates sharded over {world} GPU(s), all-gather of costs",
+                       "ms_per_mpc_rollout": dt / args.steps * 1e3,
+                       "action_path": "host decode (ag_rollout)" if "action_upper_lim" not in task else
+                                      "device-planned (ag_rollout_actions: decode + launch plan on the GPU)"},
+            # SHA-256 of the gathered per-candidate reward vector of the last timed step (fp32 bytes): sharded == unsharded
+            # bit for bit (tests/test_gpu_two_ranks.py compares the 2-rank line with the 1-rank line)
+            "reward_sha256": __import__("hashlib").sha256(rewards_host.tobytes()).hexdigest(),
+            # HIP multiplexes streams onto this many hardware queues; the engine's four + RCCL's need more than the default 4
+            "env": {"GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES"), "hw_queues": ag.hw_queues},
+        }
+    if rank == 0 and args.full:
         # edges per graph: measured on the start graph of candidate 0 (constant to within a few edges over the rollout)
         mask = torch.ones((1, N_o + 1), dtype=torch.bool, device=dev)
         tool = torch.zeros((1, N_o + 1), dtype=torch.bool, device=dev)
@@ -619,7 +684,6 @@ def main():
         # self-loop edges are not run through the relation encoder (their C row is a model constant): count the FLOPs
         # of the edges the kernel actually encodes
         E_enc = E - int((el0.recv[0, :E] == el0.send[0, :E]).sum())
-        total_steps = B * H * R
         launches_per_step = max(1, n_edge // prof_steps)
         edges_per_launch = E_enc * (hi - lo) * H * R / launches_per_step
         avg_ms = ms_edge / max(1, n_edge)
@@ -657,17 +721,8 @@ def main():
         np_gbs = np_bytes_launch / (np_avg_ms * 1e-3) / 1e9 if np_avg_ms > 0 else 0.0
         np_traffic_file = latest("traffic_k_node_prop.json")
         np_traffic = pmc_traffic(np_traffic_file, "candidates_per_launch", cand_per_launch)
-        line = {
-            "metric": "rollout-steps/sec", "value": total_steps * args.steps / dt, "unit": "rollout-steps/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "BASELINE configs[3]: cloth, 1024 candidates x 20 rollout steps (2 look-ahead x "
-                                   "repeat 10) x 2025+1 particles, radius graph rebuilt every step",
-                       "candidates": B, "horizon": H * R, "particles": N_o + 1, "edges_per_graph": E, "edges_encoded_per_graph": E_enc,
-                       "parallelism": f"candidates sharded over {world} GPU(s), all-gather of costs",
-                       "ms_per_mpc_rollout": dt / args.steps * 1e3, "ms_per_mpc_iter": ms_mpc,
-                       "action_path": "host decode (ag_rollout)" if "action_upper_lim" not in task else
-                                      "device-planned (ag_rollout_actions: decode + launch plan on the GPU)"},
+        line["config"].update(edges_per_graph=E, edges_encoded_per_graph=E_enc, ms_per_mpc_iter=ms_mpc)
+        line.update({
             "roofline": {"bound": "mfma", "kernel": "k_edge_enc", "achieved": achieved, "peak": PEAK_FP32_MFMA_TFLOPS,
                          "unit": "TFLOP/s", "frac": achieved / PEAK_FP32_MFMA_TFLOPS, "traffic": traffic,
                          "traffic_source": f"profiles/{traffic_file}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this launch "
@@ -692,12 +747,7 @@ def main():
                                                "the other workgroup on its CU; achieved = algorithmic FLOPs resp. compulsory "
                                                "HBM bytes / HIP-event time; traffic = PMC FETCH_SIZE x2 + WRITE_SIZE per launch"},
             "kernel_ms_per_rollout_single_stream": {f: v[0] / prof_steps for f, v in fam_ms.items()},
-            # SHA-256 of the gathered per-candidate reward vector of the last timed step (fp32 bytes): sharded == unsharded
-            # bit for bit (tests/test_gpu_two_ranks.py compares the 2-rank line with the 1-rank line)
-            "reward_sha256": __import__("hashlib").sha256(costs.detach().cpu().numpy().tobytes()).hexdigest(),
-            # HIP multiplexes streams onto this many hardware queues; the engine's four + RCCL's need more than the default 4
-            "env": {"GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES"), "hw_queues": ag.hw_queues},
-        }
+        })
         # The reward vector of this batch is deterministic (no float atomics; sharded == unsharded bit for bit): a run of the default
         # workload - on any number of GPUs - must reproduce the SHA-256 of the committed one-GPU evidence line, whose parity_check
         # compared the same rollouts with the reference's own outputs.  This is the parity statement of an N > 1 line, which has
@@ -763,6 +813,7 @@ def main():
                             "through the LDS, not VALU issue): profiles/r05_bf16x3_limiter.json"}
         if not dist_on and not args.no_cpu_baseline:
             line["cpu_baseline"], line["parity_check"] = cpu_baseline(cloud, task, Wt, actions.numpy(), picks, timed_seqs, ref)
+    if rank == 0:
         print(json.dumps(line), flush=True)
         if "parity_check" in line and not line["parity_check"]["ok"]:
             sys.exit("bench: the timed rollout differs from the reference fixtures / the oracle by more than 1e-5")

@@ -15,7 +15,8 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ARGS = ["--candidates", "64", "--side", "20", "--steps", "1", "--warmup", "0", "--no-bf16x3", "--no-mpc-iter",
+# --full: the multi_gpu diagnostics these tests read are not part of a plain run
+ARGS = ["--candidates", "64", "--side", "20", "--steps", "1", "--warmup", "0", "--full", "--no-bf16x3", "--no-mpc-iter",
         "--no-cpu-baseline", "--no-kernel-profile"]
 
 

@@ -29,7 +29,7 @@ json.dump(line, open(os.path.join(P, f"{rnd}_bench_default.json"), "w"), indent=
 stats(os.path.join(F, "prof_default", "d_kernel_stats.csv"), os.path.join(P, f"{rnd}_bench_default_kernel_stats.csv"))
 stats(os.path.join(F, "prof_single", "s_kernel_stats.csv"), os.path.join(P, f"{rnd}_bench_single_stream_kernel_stats.csv"))
 E_enc, cand = line["config"]["edges_encoded_per_graph"], 128
-src = ("rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (two passes) --kernel-trace -- python3 bench.py --candidates 256 --steps 1 --warmup 0 "
+src = ("rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (two passes) --kernel-trace -- python3 bench.py --full --candidates 256 --steps 1 --warmup 0 "
        "--no-cpu-baseline --no-bf16x3 --no-kernel-profile --no-mpc-iter, AG_STREAMS=1 AG_SHARE_FIRST=0 (tools/profile_round.sh); "
        "tools/pmc_traffic.py")
 for src_name, dst_name in (("traffic_k_edge_enc.json", "traffic_k_edge_enc.json"), ("traffic_k_node_propfalse.json", "traffic_k_node_prop.json"),
@@ -50,7 +50,7 @@ with open(os.path.join(P, f"{rnd}_planner_configs.jsonl"), "a") as f:
                 r = json.loads(l); r.update(tag)
                 f.write(json.dumps(r) + "\n")
 one, plain = bench_line(os.path.join(F, "bench_one_rank_rccl.json")), bench_line(os.path.join(F, "bench_plain_short.json"))
-json.dump({"what": "bench.py --gpus 1 --steps 5 --warmup 2 with AG_BENCH_FORCE_DIST=1: nccl (= RCCL) process group with a world of one rank, "
+json.dump({"what": "bench.py --full --gpus 1 --steps 5 --warmup 2 with AG_BENCH_FORCE_DIST=1: nccl (= RCCL) process group with a world of one rank, "
                    "the all-gather of the rewards and both MAX all-reduces issued on it; against the plain run on the same box",
            "one_rank_rccl": {k: one[k] for k in ("value", "ms_per_step", "reward_sha256", "multi_gpu")},
            "plain": {k: plain[k] for k in ("value", "ms_per_step", "reward_sha256")},
@@ -88,7 +88,7 @@ if all(ranks.values()):
               open(os.path.join(P, f"{rnd}_planner_loop_ranks.json"), "w"), indent=1)
 bare = _last_json(os.path.join(F, "bench_bare_two_ranks.json"))
 if bare:
-    json.dump({"what": "AG_BENCH_SHARE_GPU=1 AG_BENCH_BACKEND=gloo python bench.py --gpus 2 --steps 5 --warmup 2 ... with NO launcher in front, full "
+    json.dump({"what": "AG_BENCH_SHARE_GPU=1 AG_BENCH_BACKEND=gloo python bench.py --full --gpus 2 --steps 5 --warmup 2 ... with NO launcher in front, full "
                        "size: the parent starts python -m torch.distributed.run itself (multi_gpu.launched_by); both ranks share the one GPU of "
                        "the box, so ms_per_step is not a scaling figure", "line": {k: bare[k] for k in ("value", "n_gpus", "ms_per_step", "reward_sha256", "multi_gpu", "config")},
                "one_rank_reward_sha256": plain["reward_sha256"], "reward_vectors_bit_equal": bare["reward_sha256"] == plain["reward_sha256"]},

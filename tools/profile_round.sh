@@ -9,16 +9,16 @@ cd $GRAFT_REPO_ROOT
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/final
 rm -rf $O; mkdir -p $O
-timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err
+timeout -k 10 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err
 export TMPDIR=/tmp
 cd /tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_default -o d -- python3 $R/bench.py --no-cpu-baseline > $O/prof_default.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_default -o d -- python3 $R/bench.py --full --no-cpu-baseline > $O/prof_default.log 2>&1
 # single stream, share_first off: every k_edge_enc launch a full 128-candidate one - the launch shape bench.py's roofline pass times
-AG_STREAMS=1 AG_SHARE_FIRST=0 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_single -o s -- python3 $R/bench.py --no-cpu-baseline --no-bf16x3 --no-mpc-iter > $O/prof_single.log 2>&1
+AG_STREAMS=1 AG_SHARE_FIRST=0 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_single -o s -- python3 $R/bench.py --full --no-cpu-baseline --no-bf16x3 --no-mpc-iter > $O/prof_single.log 2>&1
 for c in FETCH_SIZE WRITE_SIZE GRBM_GUI_ACTIVE; do
-  AG_STREAMS=1 AG_SHARE_FIRST=0 timeout -k 10 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pmc_$c -o p -- python3 $R/bench.py --candidates 256 --steps 1 --warmup 0 --no-cpu-baseline --no-bf16x3 --no-kernel-profile --no-mpc-iter > $O/pmc_$c.log 2>&1
+  AG_STREAMS=1 AG_SHARE_FIRST=0 timeout -k 10 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pmc_$c -o p -- python3 $R/bench.py --full --candidates 256 --steps 1 --warmup 0 --no-cpu-baseline --no-bf16x3 --no-kernel-profile --no-mpc-iter > $O/pmc_$c.log 2>&1
 done
-AG_STREAMS=1 AG_SHARE_FIRST=0 timeout -k 10 300 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_BUSY_CYCLES --kernel-trace --output-format csv -d $O/pmc_sq -o p -- python3 $R/bench.py --candidates 256 --steps 1 --warmup 0 --no-cpu-baseline --no-bf16x3 --no-kernel-profile --no-mpc-iter > $O/pmc_sq.log 2>&1
+AG_STREAMS=1 AG_SHARE_FIRST=0 timeout -k 10 300 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_BUSY_CYCLES --kernel-trace --output-format csv -d $O/pmc_sq -o p -- python3 $R/bench.py --full --candidates 256 --steps 1 --warmup 0 --no-cpu-baseline --no-bf16x3 --no-kernel-profile --no-mpc-iter > $O/pmc_sq.log 2>&1
 cd $R
 for k in "k_edge_enc<4>" "k_node_prop<false, false>" "k_node_prop<true, false>"; do
   n=$(echo $k | sed 's/<4>//; s/<false, false>/false/; s/<true, false>/true/')
@@ -52,8 +52,8 @@ AG_SHARD_CANDIDATES=4000 AG_BENCH_SHARE_GPU=1 timeout -k 10 300 python -m torch.
 AG_SHARE_PREFIX=0 timeout -k 10 300 python tools/bench_planner.py --modes chunked --sorts 1 > $O/planner_configs_share0.jsonl 2> $O/planner_configs_share0.err
 AG_SHARE_PREFIX=0 AG_SHARE_FIRST=0 timeout -k 10 300 python tools/bench_planner.py --modes chunked --sorts 1 > $O/planner_configs_share00.jsonl 2> $O/planner_configs_share00.err
 # the RCCL calls with a world of one rank (bench.py AG_BENCH_FORCE_DIST=1): reward hash equal to the plain line's
-AG_BENCH_FORCE_DIST=1 timeout -k 10 300 python bench.py --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline --no-bf16x3 --no-mpc-iter --no-kernel-profile > $O/bench_one_rank_rccl.json 2> $O/bench_one_rank_rccl.err
-timeout -k 10 300 python bench.py --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline --no-bf16x3 --no-mpc-iter --no-kernel-profile > $O/bench_plain_short.json 2> $O/bench_plain_short.err
+AG_BENCH_FORCE_DIST=1 timeout -k 10 300 python bench.py --full --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline --no-bf16x3 --no-mpc-iter --no-kernel-profile > $O/bench_one_rank_rccl.json 2> $O/bench_one_rank_rccl.err
+timeout -k 10 300 python bench.py --full --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline --no-bf16x3 --no-mpc-iter --no-kernel-profile > $O/bench_plain_short.json 2> $O/bench_plain_short.err
 timeout -k 10 120 python tools/trace_mpc_iter.py > $O/small_call_latency.json 2> /dev/null
 cd $R
 # (SKIP_CONFIGS=1: the per-config evidence is then run as a call of its own - gpurun -- 'bash tools/profile_configs.sh' - the two

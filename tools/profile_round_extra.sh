@@ -13,7 +13,7 @@ timeout -k 10 300 python tools/bench_interact.py > $O/interact_configs.jsonl 2> 
 AG_LOOP_CHUNKS=40 timeout -k 10 300 python tools/two_rank_planner_loop.py > $O/planner_loop_1rank.json 2> $O/planner_loop_ranks.err || true
 AG_LOOP_CHUNKS=40 AG_BENCH_SHARE_GPU=1 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29519 tools/two_rank_planner_loop.py > $O/planner_loop_2ranks.json 2>> $O/planner_loop_ranks.err || true
 # `python bench.py --gpus 2` with NO launcher in front, full size: the parent starts its own two ranks (rehearsal: both on this GPU, gloo)
-AG_BENCH_SHARE_GPU=1 AG_BENCH_BACKEND=gloo timeout -k 10 400 python bench.py --gpus 2 --steps 5 --warmup 2 --no-bf16x3 --no-mpc-iter --no-kernel-profile > $O/bench_bare_two_ranks.json 2> $O/bench_bare_two_ranks.err || true
+AG_BENCH_SHARE_GPU=1 AG_BENCH_BACKEND=gloo timeout -k 10 400 python bench.py --full --gpus 2 --steps 5 --warmup 2 --no-bf16x3 --no-mpc-iter --no-kernel-profile > $O/bench_bare_two_ranks.json 2> $O/bench_bare_two_ranks.err || true
 # HIP-API + kernel traces of the interact configuration (blocking HIP calls per planner call), rope
 export TMPDIR=/tmp
 cd /tmp
@@ -25,13 +25,13 @@ cd $R
 # secondary bf16x3 mode, A/B of ONE 8-wavefront workgroup per CU sharing one weight ring (tools/build_experiment.sh b3wg512 -DAG_B3_WG512)
 # against the shipped two 4-wavefront workgroups: bench line of each, then PMC passes of each (own runs, no other trace domain)
 if [ -f $R/adaptigraph_amd/csrc/libadaptigraph_hip_b3wg512.so ]; then
-  timeout -k 10 300 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-mpc-iter > $O/b3_base.json 2> $O/b3_base.err || true
-  ADAPTIGRAPH_AMD_LIB=$R/adaptigraph_amd/csrc/libadaptigraph_hip_b3wg512.so timeout -k 10 300 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-mpc-iter > $O/b3_wg512.json 2> $O/b3_wg512.err || true
+  timeout -k 10 300 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-mpc-iter > $O/b3_base.json 2> $O/b3_base.err || true
+  ADAPTIGRAPH_AMD_LIB=$R/adaptigraph_amd/csrc/libadaptigraph_hip_b3wg512.so timeout -k 10 300 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-mpc-iter > $O/b3_wg512.json 2> $O/b3_wg512.err || true
   cd /tmp
   for v in base wg512; do
     lib=$R/adaptigraph_amd/csrc/libadaptigraph_hip.so; [ $v = wg512 ] && lib=$R/adaptigraph_amd/csrc/libadaptigraph_hip_b3wg512.so
-    ADAPTIGRAPH_AMD_LIB=$lib AG_STREAMS=1 AG_SHARE_FIRST=0 AG_PRECISION=bf16x3 timeout -k 10 300 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_LDS SQ_INSTS_LDS --kernel-trace --output-format csv -d $O/pmc_b3_${v}_sq -o p -- python3 $R/bench.py --candidates 256 --steps 1 --warmup 0 --no-cpu-baseline --no-bf16x3 --no-kernel-profile --no-mpc-iter > $O/pmc_b3_${v}_sq.log 2>&1 || true
-    ADAPTIGRAPH_AMD_LIB=$lib AG_STREAMS=1 AG_SHARE_FIRST=0 AG_PRECISION=bf16x3 timeout -k 10 300 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT --kernel-trace --output-format csv -d $O/pmc_b3_${v}_lds -o p -- python3 $R/bench.py --candidates 256 --steps 1 --warmup 0 --no-cpu-baseline --no-bf16x3 --no-kernel-profile --no-mpc-iter > $O/pmc_b3_${v}_lds.log 2>&1 || true
+    ADAPTIGRAPH_AMD_LIB=$lib AG_STREAMS=1 AG_SHARE_FIRST=0 AG_PRECISION=bf16x3 timeout -k 10 300 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_LDS SQ_INSTS_LDS --kernel-trace --output-format csv -d $O/pmc_b3_${v}_sq -o p -- python3 $R/bench.py --full --candidates 256 --steps 1 --warmup 0 --no-cpu-baseline --no-bf16x3 --no-kernel-profile --no-mpc-iter > $O/pmc_b3_${v}_sq.log 2>&1 || true
+    ADAPTIGRAPH_AMD_LIB=$lib AG_STREAMS=1 AG_SHARE_FIRST=0 AG_PRECISION=bf16x3 timeout -k 10 300 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT --kernel-trace --output-format csv -d $O/pmc_b3_${v}_lds -o p -- python3 $R/bench.py --full --candidates 256 --steps 1 --warmup 0 --no-cpu-baseline --no-bf16x3 --no-kernel-profile --no-mpc-iter > $O/pmc_b3_${v}_lds.log 2>&1 || true
   done
   cd $R
   python - <<'PY'

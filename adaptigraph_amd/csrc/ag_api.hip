@@ -950,6 +950,78 @@ int ag_forward(ag_ctx* c, void* stream, const float* d_state, const float* d_att
     return AG_OK;
 }
 
+int ag_backward(ag_ctx* c, void* stream, const float* d_state, const float* d_attrs, const float* d_action,
+                const float* d_phys, const float* d_group, int32_t n_inst, const int32_t* d_recv, const int32_t* d_send,
+                const int32_t* d_row_ptr, const int32_t* d_n_edges, int32_t edge_cap, int32_t B, int32_t N, int32_t n_p,
+                const float* const* d_w, const float* d_grad_pos, const float* d_grad_motion, float* d_grad_state,
+                float* const* d_grad_w) {
+    if (!c) return AG_ERR_INVALID;
+    if (!d_state || !d_attrs || !d_action || !d_phys || !d_group || !d_recv || !d_send || !d_row_ptr || !d_n_edges || !d_w)
+        return fail(c, AG_ERR_INVALID, "ag_backward: null pointer");
+    for (int k = 0; k < 22; ++k)
+        if (!d_w[k]) return fail(c, AG_ERR_INVALID, "ag_backward: null parameter %d", k);
+    if (B < 1 || N < 1 || n_p < 1 || n_p > N || n_inst < 1 || edge_cap < 1)
+        return fail(c, AG_ERR_INVALID, "ag_backward: bad sizes B=%d N=%d n_p=%d n_inst=%d edge_cap=%d", B, N, n_p, n_inst, edge_cap);
+    if (c->dims.nf != NF || c->dims.in_dim != IN_DIM || c->dims.rel_dim != 5 + 3 * c->dims.n_his || c->dims.pstep < 1 || c->dims.pstep > 7)
+        return fail(c, AG_ERR_UNSUPPORTED, "ag_backward: nf %d, in_dim %d, rel_dim %d, pstep %d not served", c->dims.nf, c->dims.in_dim,
+                    c->dims.rel_dim, c->dims.pstep);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // the edge counts size the workspace (rows per graph = the largest count) and carry the overflow verdict
+    std::vector<int32_t> ne((size_t)B);
+    HIPCHK(c, hipMemcpyAsync(ne.data(), d_n_edges, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    int emax = 0;
+    for (int v : ne) emax = std::max(emax, v);
+    if (emax > edge_cap) return fail(c, AG_ERR_MAX_NR, "Exceeds max dims: a graph had %d edges, edge_cap=%d", emax, edge_cap);
+    TrainArgs t{};
+    t.state = d_state; t.attrs = d_attrs; t.action = d_action; t.phys = d_phys; t.group = d_group; t.n_inst = n_inst;
+    t.recv = d_recv; t.send = d_send; t.row_ptr = d_row_ptr; t.n_edges = d_n_edges; t.edge_cap = edge_cap;
+    t.B = B; t.N = N; t.n_p = n_p; t.n_his = c->dims.n_his; t.pstep = c->dims.pstep; t.clamp = c->dims.motion_clamp;
+    t.Ep = std::max(1, emax);
+    t.dpos = d_grad_pos; t.dmot = d_grad_motion; t.dstate = d_grad_state;
+    // chunk: the context's chunk if set, else as many candidates as fit a 4-GiB workspace
+    const size_t per_cand = train_work_floats(1, N, t.Ep, t.n_his, t.pstep) * 4 + train_work_ints(1, N, t.Ep) * 4;
+    int Bc = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, (size_t(4) << 30) / per_cand));
+    if (c->chunk > 0) Bc = std::min(Bc, (int)c->chunk);
+    else if (c->opt.chunk > 0) Bc = std::min(Bc, c->opt.chunk);
+    size_t gw_floats = 0;
+    const int ncols[11] = {IN_DIM, NF, NF, c->dims.rel_dim, NF, NF, 2 * NF, 3 * NF, NF, NF, NF};
+    for (int l = 0; l < 11; ++l) gw_floats += (size_t)(l == 10 ? 3 : NF) * (ncols[l] + 1) + 128;
+    const size_t wf = train_work_floats(Bc, N, t.Ep, t.n_his, t.pstep), wi = train_work_ints(Bc, N, t.Ep);
+    CallSlot* sl = nullptr;
+    int rc = slot_acquire(c, st, false, &sl);
+    if (rc) return rc;
+    SlotGuard slot_guard(sl, st, false);
+    rc = ensure_slab(c, *sl, (wf + train_slab_floats() + gw_floats) * 4 + wi * 4 + 8 * 256);
+    if (rc) return rc;
+    float* wsf = sl->slab.take<float>(wf);
+    float* slab = sl->slab.take<float>(train_slab_floats());
+    int* wsi = sl->slab.take<int>(wi);
+    float* acc[22];
+    for (int l = 0; l < 11; ++l) {
+        const int rows = l == 10 ? 3 : NF;
+        acc[2 * l] = sl->slab.take<float>((size_t)rows * ncols[l]);
+        acc[2 * l + 1] = sl->slab.take<float>(rows);
+    }
+    if (sl->slab.used > sl->slab.cap) return fail(c, AG_ERR_INVALID, "internal: workspace carve overflow");
+    for (int l = 0; l < 11; ++l) {
+        const int rows = l == 10 ? 3 : NF;
+        HIPCHK(c, hipMemsetAsync(acc[2 * l], 0, (size_t)rows * ncols[l] * 4, st));
+        HIPCHK(c, hipMemsetAsync(acc[2 * l + 1], 0, (size_t)rows * 4, st));
+    }
+    for (int k = 0; k < 22; ++k) { t.w[k] = d_w[k]; t.g[k] = acc[k]; }
+    for (int b0 = 0; b0 < B; b0 += Bc)
+        HIPCHK(c, train_backward_chunk(t, b0, std::min(Bc, B - b0), wsf, wsi, slab, st));
+    for (int l = 0; l < 11 && d_grad_w; ++l) {
+        const int rows = l == 10 ? 3 : NF;
+        if (d_grad_w[2 * l]) HIPCHK(c, hipMemcpyAsync(d_grad_w[2 * l], acc[2 * l], (size_t)rows * ncols[l] * 4, hipMemcpyDeviceToDevice, st));
+        if (d_grad_w[2 * l + 1]) HIPCHK(c, hipMemcpyAsync(d_grad_w[2 * l + 1], acc[2 * l + 1], (size_t)rows * 4, hipMemcpyDeviceToDevice, st));
+    }
+    HIPCHK(c, hipStreamSynchronize(st));
+    return AG_OK;
+}
+
 }  // extern "C"
 
 namespace {

@@ -333,4 +333,21 @@ hipError_t launch_share_prep(const float* state0, int N_o, int n_his, float* nod
 hipError_t launch_roll_init(const RollArgs& a, const RollBufs& r, const GraphBufs& g, hipStream_t st);
 hipError_t launch_roll_update(const RollArgs& a, const RollBufs& r, const GraphBufs& g, hipStream_t st);
 
+// ---- backward pass (ag_train.hip; ag_backward).  Weights are the 22 plain fp32 tensors in ag_ctx_load_weights order,
+// (out, in) / (out,) row-major; g[k] the matching gradient accumulators (zeroed by the caller, += per chunk in chunk order).
+struct TrainArgs {
+    const float* state; const float* attrs; const float* action; const float* phys; const float* group; int n_inst;
+    const int* recv; const int* send; const int* row_ptr; const int* n_edges; int edge_cap;
+    int B, N, n_p, n_his, pstep; float clamp;
+    int Ep;                     // edge rows per graph in the workspace: max n_edges of the call (>= 1)
+    const float* w[22]; float* g[22];
+    const float* dpos; const float* dmot;   // (B,n_p,3) or null (= zero)
+    float* dstate;                          // (B,n_his,N,3) or null (= not wanted)
+};
+size_t train_slab_floats();
+size_t train_work_floats(int Bc, int N, int Ep, int n_his, int pstep);
+size_t train_work_ints(int Bc, int N, int Ep);
+// candidates [b0, b0+nb) of t; wsf / wsi / slab: train_work_floats(nb,...) floats, train_work_ints(nb,...) ints, train_slab_floats()
+hipError_t train_backward_chunk(const TrainArgs& t, int b0, int nb, float* wsf, int* wsi, float* slab, hipStream_t st);
+
 }  // namespace ag

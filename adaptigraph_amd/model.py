@@ -2,14 +2,17 @@
 (src/dynamics/gnn/model.py:64-342), executing on the HIP engine.
 
 The nn.Module tree exists only so that state_dict keys, load_state_dict, .to() and .eval() behave like the reference;
-no torch op of it is ever run - forward() hands raw device pointers to the C-ABI (inference only, no autograd).
+no torch op of it is ever run - forward() hands raw device pointers to the C-ABI.  With grad enabled and the parameters or
+`state` requiring grad, forward() runs through autograd.DynamicsFunction (ag_forward + ag_backward); otherwise it is the
+inference path.  Parameters are frozen after construction; train(True) unfreezes them and train(False) / eval() freezes them.
 """
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
 
-from .context import Engine, ptr, current_stream, _require_gpu
+from .autograd import DynamicsFunction
+from .context import Engine, ptr, current_stream, _require_gpu, STATE_DICT_ORDER
 from .graph import EdgeList
 
 
@@ -82,6 +85,19 @@ class DynamicsPredictor(nn.Module):
         self._uploaded_key = None
         self._precision = None       # None: the engine default (exact fp32, or AG_PRECISION)
 
+    def train(self, mode=True):
+        """nn.Module.train, and also requires_grad = mode on the 22 parameters (the reference's train.py calls model.train()
+        before each train phase and model.eval() before each valid phase).  requires_grad_() keeps working directly."""
+        super().train(mode)
+        for p in self.parameters():
+            p.requires_grad_(bool(mode))
+        return self
+
+    def ordered_parameters(self):
+        """The 22 parameters in ag_ctx_load_weights order."""
+        mods = dict(self.named_modules())
+        return [getattr(mods[base], s) for base in STATE_DICT_ORDER for s in ("weight", "bias")]
+
     # ------------------------------------------------------------------ engine / weights
     def set_precision(self, mode):
         """'fp32': exact fp32 MFMA (default).  'bf16x3': 3-way bf16 split on the bf16 matrix pipe with fp32 accumulation
@@ -107,9 +123,54 @@ class DynamicsPredictor(nn.Module):
         return self._engine
 
     # ------------------------------------------------------------------ forward (model.py:130-342)
-    @torch.no_grad()
     def forward(self, state, attrs, Rr=None, Rs=None, p_instance=None, action=None, particle_den=None, obj_mask=None,
                 edges: EdgeList | None = None, **kwargs):
+        params = self.ordered_parameters()
+        data = [attrs, p_instance, action, Rr, Rs] + [v for k, v in kwargs.items() if k.endswith("_physics_param")]
+        if torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in [state, *params, *data]):
+            return self._forward_grad(state, attrs, Rr, Rs, p_instance, action, edges, params, kwargs)
+        with torch.no_grad():
+            return self._forward_nograd(state, attrs, Rr, Rs, p_instance, action, edges, kwargs)
+
+    def _inputs(self, dev, state, attrs, Rr, Rs, p_instance, action, edges, kwargs):
+        """Model inputs in the C-ABI's form (model.py:152-282 on the host side): physics parameter per particle, group."""
+        B, N = attrs.size(0), attrs.size(1)
+        n_p, n_inst = p_instance.size(1), p_instance.size(2)
+        n_s = N - n_p
+        physics_keys = [k for k in kwargs.keys() if k.endswith("_physics_param")]
+        assert len(physics_keys) == 1                                            # model.py:186-187
+        pp = kwargs[physics_keys[0]].to(device=dev, dtype=torch.float32)
+        if pp.size(-1) == 1:
+            pp = pp[:, None, :].repeat(1, n_p, 1)                                # model.py:191-197
+        else:
+            pp = pp.reshape(B, n_p, 1)                                           # model.py:204
+        phys = torch.cat([pp[..., 0], torch.zeros(B, n_s, device=dev)], 1).contiguous()   # model.py:206-207
+        assert action is not None                                                # model.py:222
+        group = torch.cat([p_instance.to(torch.float32), torch.zeros(B, n_s, n_inst, device=dev)], 1).contiguous()
+        if edges is None:
+            assert Rr is not None and Rs is not None
+            edges = EdgeList.from_dense(Rr, Rs)
+        assert edges.N == N
+        attrs = attrs.to(torch.float32).contiguous()
+        action = action.to(torch.float32).contiguous()
+        return attrs, action, phys, group, edges, n_p
+
+    def _forward_grad(self, state, attrs, Rr, Rs, p_instance, action, edges, params, kwargs):
+        data = [("attrs", attrs), ("p_instance", p_instance), ("action", action), ("Rr", Rr), ("Rs", Rs)]
+        data += [(k, v) for k, v in kwargs.items() if k.endswith("_physics_param")]
+        for name, t in data:
+            if torch.is_tensor(t) and t.requires_grad:
+                raise NotImplementedError(f"DynamicsPredictor: gradient with respect to {name} is not implemented (gradients "
+                                          "reach state and the parameters only)")
+        dev = _require_gpu(state.device)
+        eng = self.engine(dev)
+        with torch.no_grad():
+            attrs, action, phys, group, edges, n_p = self._inputs(dev, state, attrs, Rr, Rs, p_instance, action, edges, kwargs)
+        state = state.to(torch.float32).contiguous()
+        assert state.shape == (attrs.size(0), self.n_his, attrs.size(1), 3)
+        return DynamicsFunction.apply(eng, edges, n_p, state, attrs, action, phys, group, *params)
+
+    def _forward_nograd(self, state, attrs, Rr, Rs, p_instance, action, edges, kwargs):
         dev = _require_gpu(state.device)
         eng = self.engine(dev)
         B, N = attrs.size(0), attrs.size(1)

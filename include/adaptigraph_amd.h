@@ -29,6 +29,7 @@
  *   - WHICH ENTRY POINTS BLOCK THE HOST, and when (everything else only enqueues):
  *       ag_ctx_load_weights, ag_ctx_set_precision     always (host repack + copies)
  *       ag_forward, ag_rollout                        once, at the end: they return the overflow verdict (AG_ERR_MAX_NR)
+ *       ag_backward                                   at the start (edge counts) and at the end
  *       ag_rollout_work                               for its plan (and a base rollout, if none is kept): it returns host numbers
  *       ag_ctx_rollout_counts (after a device-planned call without prefix sharing), ag_ctx_share_counts   wait for the device
  *       ag_rollout_async, ag_rollout_actions          only when the contact-free prefix is in play (option "share_prefix";
@@ -249,6 +250,22 @@ int ag_forward(ag_ctx* ctx, void* stream, const float* d_state, const float* d_a
                const float* d_phys, const float* d_group, int32_t n_inst, const int32_t* d_recv, const int32_t* d_send,
                const int32_t* d_row_ptr, const int32_t* d_n_edges, int32_t edge_cap, int32_t B, int32_t N, int32_t n_p,
                float* d_pred_pos, float* d_pred_motion);
+
+/* Backward pass of ag_forward (model.py:130-342 under torch autograd), exact fp32 whatever ag_ctx_set_precision says.
+ *   Inputs: those of ag_forward, plus d_w[22]: the 22 fp32 parameter tensors in ag_ctx_load_weights order, plain (out, in) /
+ *   (out,) row-major (the gradient is taken with respect to exactly these; the ctx's loaded weights are not used), and
+ *   d_grad_pos, d_grad_motion (B,n_p,3): dLoss/dpred_pos, dLoss/dpred_motion, either NULL (= zero).
+ *   Outputs (each NULL = not wanted): d_grad_state (B,n_his,N,3) dLoss/dstate; d_grad_w[22] matching d_w.  Gradients reach
+ *   state and the parameters only; attrs, action, phys and group are data.  Edges beyond d_n_edges[b] and particles without
+ *   edges and beyond n_p get zero gradient.  Deterministic: no float atomics, fixed reduction order (two calls on the same
+ *   inputs give the same bits).
+ * Reads d_n_edges on the host first (one stream synchronisation) and returns AG_ERR_MAX_NR ("Exceeds max dims"), with nothing
+ * enqueued, when a graph has more than edge_cap edges.  Synchronises the stream once more at the end. */
+int ag_backward(ag_ctx* ctx, void* stream, const float* d_state, const float* d_attrs, const float* d_action,
+                const float* d_phys, const float* d_group, int32_t n_inst, const int32_t* d_recv, const int32_t* d_send,
+                const int32_t* d_row_ptr, const int32_t* d_n_edges, int32_t edge_cap, int32_t B, int32_t N, int32_t n_p,
+                const float* const* d_w, const float* d_grad_pos, const float* d_grad_motion, float* d_grad_state,
+                float* const* d_grad_w);
 
 /* Replaces the device side of dynamics() / dynamics_masked() (src/planning/forward_dynamics.py:12-205, 209-399):
  * the whole look-ahead x action-repeat loop, graph rebuilt every step, no host sync inside.

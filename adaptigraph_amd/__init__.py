@@ -34,14 +34,14 @@ def _hw_queues_default():
 hw_queues = _hw_queues_default()
 
 from .context import Engine, default_engine
-from .forward_dynamics import dynamics, dynamics_masked, dynamics_mixed, rollout_work
+from .forward_dynamics import dynamics, dynamics_masked, dynamics_masked_diff, dynamics_mixed, rollout_work
 from .graph import (EdgeList, construct_edges_from_states_batch, construct_edges_from_states, construct_edges_index,
                     construct_edges_with_backoff, pad_torch, truncate_graph)
 from .model import DynamicsPredictor
 from .plan_utils import decode_action
-from .losses import chamfer, mean_chamfer, box_loss, rope_penalty, cloth_penalty, granular_penalty
+from .losses import chamfer, chamfer_diff, mean_chamfer, box_loss, rope_penalty, cloth_penalty, granular_penalty
 from .costs import running_cost
-from .physics_param_optimizer import dynamics_error, dynamics_error_sweep
+from .physics_param_optimizer import dynamics_error, dynamics_error_sweep, dynamics_error_grad, optimize_grad
 from .mppi import angle_normalize, clip_actions, sample_action_seq, optimize_action_mppi, mpc_iteration
 from .planner import Planner
 from .rollout import rollout_eval, rollout_eval_step, surface_bounds
@@ -49,4 +49,5 @@ from .rollout import rollout_eval, rollout_eval_step, surface_bounds
 __all__ = ["hw_queues", "Engine", "default_engine", "dynamics", "dynamics_masked", "dynamics_mixed", "rollout_work", "EdgeList", "construct_edges_from_states_batch", "construct_edges_from_states",
            "construct_edges_index", "construct_edges_with_backoff", "pad_torch", "truncate_graph", "DynamicsPredictor", "decode_action", "chamfer",
            "mean_chamfer", "box_loss", "rope_penalty", "cloth_penalty", "granular_penalty", "running_cost", "dynamics_error", "dynamics_error_sweep", "angle_normalize",
-           "clip_actions", "sample_action_seq", "optimize_action_mppi", "mpc_iteration", "Planner", "rollout_eval", "rollout_eval_step", "surface_bounds"]
+           "clip_actions", "sample_action_seq", "optimize_action_mppi", "mpc_iteration", "Planner", "rollout_eval", "rollout_eval_step", "surface_bounds",
+           "dynamics_masked_diff", "chamfer_diff", "dynamics_error_grad", "optimize_grad"]

@@ -949,6 +949,15 @@ int ag_backward(ag_ctx* c, void* stream, const float* d_state, const float* d_at
                 const int32_t* d_row_ptr, const int32_t* d_n_edges, int32_t edge_cap, int32_t B, int32_t N, int32_t n_p,
                 const float* const* d_w, const float* d_grad_pos, const float* d_grad_motion, float* d_grad_state,
                 float* const* d_grad_w) {
+    return ag_backward_inputs(c, stream, d_state, d_attrs, d_action, d_phys, d_group, n_inst, d_recv, d_send, d_row_ptr, d_n_edges,
+                              edge_cap, B, N, n_p, d_w, d_grad_pos, d_grad_motion, d_grad_state, d_grad_w, nullptr, nullptr);
+}
+
+int ag_backward_inputs(ag_ctx* c, void* stream, const float* d_state, const float* d_attrs, const float* d_action,
+                       const float* d_phys, const float* d_group, int32_t n_inst, const int32_t* d_recv, const int32_t* d_send,
+                       const int32_t* d_row_ptr, const int32_t* d_n_edges, int32_t edge_cap, int32_t B, int32_t N, int32_t n_p,
+                       const float* const* d_w, const float* d_grad_pos, const float* d_grad_motion, float* d_grad_state,
+                       float* const* d_grad_w, float* d_grad_phys, float* d_grad_action) {
     if (!c) return AG_ERR_INVALID;
     if (!d_state || !d_attrs || !d_action || !d_phys || !d_group || !d_recv || !d_send || !d_row_ptr || !d_n_edges || !d_w)
         return fail(c, AG_ERR_INVALID, "ag_backward: null pointer");
@@ -974,6 +983,8 @@ int ag_backward(ag_ctx* c, void* stream, const float* d_state, const float* d_at
     t.B = B; t.N = N; t.n_p = n_p; t.n_his = c->dims.n_his; t.pstep = c->dims.pstep; t.clamp = c->dims.motion_clamp;
     t.Ep = std::max(1, emax);
     t.dpos = d_grad_pos; t.dmot = d_grad_motion; t.dstate = d_grad_state;
+    t.dphys = d_grad_phys; t.daction = d_grad_action;
+    for (int k = 0; k < 22 && d_grad_w; ++k) t.want_w = t.want_w || d_grad_w[k] != nullptr;   // else: data gradients only
     // chunk: the context's chunk if set, else as many candidates as fit a 4-GiB workspace
     const size_t per_cand = train_work_floats(1, N, t.Ep, t.n_his, t.pstep) * 4 + train_work_ints(1, N, t.Ep) * 4;
     int Bc = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, (size_t(4) << 30) / per_cand));
@@ -1799,6 +1810,31 @@ int ag_cost_chamfer(ag_ctx* c, void* stream, const float* d_x, const float* d_y,
     c->prof_stream = static_cast<hipStream_t>(stream);
     Scoped p(c, FAM_COST);
     HIPCHK(c, launch_chamfer(d_x, d_y, d_xmask, d_ymask, R, N, M, By, d_out, static_cast<hipStream_t>(stream)));
+    return AG_OK;
+}
+
+int ag_cost_chamfer_backward(ag_ctx* c, void* stream, const float* d_x, const float* d_y, const uint8_t* d_xmask,
+                             const uint8_t* d_ymask, int32_t R, int32_t N, int32_t M, int32_t By, const float* d_grad_out,
+                             float* d_grad_x) {
+    if (!c) return AG_ERR_INVALID;
+    if (!d_x || !d_y || !d_grad_out || !d_grad_x || R < 1 || N < 1 || M < 1 || (By != 1 && By != R))
+        return fail(c, AG_ERR_INVALID, "ag_cost_chamfer_backward: bad arguments R=%d N=%d M=%d By=%d", R, N, M, By);
+    if ((size_t)N + (size_t)M > chamfer_max_points())
+        return fail(c, AG_ERR_UNSUPPORTED, "ag_cost_chamfer_backward: N+M=%d exceeds the LDS tile (%zu points)", N + M, chamfer_max_points());
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    c->prof_stream = st;
+    CallSlot* sl = nullptr;
+    int rc = slot_acquire(c, st, false, &sl);
+    if (rc) return rc;
+    SlotGuard slot_guard(sl, st, false);
+    rc = ensure_slab(c, *sl, (size_t)R * (N + M + 2) * 4 + 4 * 256);
+    if (rc) return rc;
+    int* nn = sl->slab.take<int>((size_t)R * (N + M));
+    float* cnt = sl->slab.take<float>((size_t)R * 2);
+    if (sl->slab.used > sl->slab.cap) return fail(c, AG_ERR_INVALID, "internal: workspace carve overflow");
+    Scoped p(c, FAM_COST);
+    HIPCHK(c, launch_chamfer_backward(d_x, d_y, d_xmask, d_ymask, R, N, M, By, d_grad_out, nn, cnt, d_grad_x, st));
     return AG_OK;
 }
 

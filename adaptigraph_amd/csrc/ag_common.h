@@ -292,6 +292,9 @@ hipError_t launch_state_stats(const float* state, int R, int N, const float* box
 hipError_t launch_penalty(const float* state_pred, const float* action, const float* state_init, int B, int H, int N,
                           int kind, float ratio, float* out, hipStream_t st);
 size_t chamfer_max_points();
+// gradient of chamfer toward x: nn (R, N+M) ints and cnt (R,2) floats are workspace
+hipError_t launch_chamfer_backward(const float* x, const float* y, const uint8_t* xm, const uint8_t* ym, int R, int N, int M,
+                                   int By, const float* gout, int* nn, float* cnt, float* gx, hipStream_t st);
 hipError_t launch_reward(const float* error, const float* pen, const float* stats, const float* emax, const double* bbox4, int B,
                          int H, float* out, hipStream_t st);
 hipError_t launch_cloth_combine(const float* raw, const float* dmax, long n, float* out, hipStream_t st);
@@ -343,6 +346,8 @@ struct TrainArgs {
     const float* w[22]; float* g[22];
     const float* dpos; const float* dmot;   // (B,n_p,3) or null (= zero)
     float* dstate;                          // (B,n_his,N,3) or null (= not wanted)
+    float* dphys; float* daction;           // (B,N), (B,N,3) or null (= not wanted): ag_backward_inputs
+    bool want_w;                            // false: none of the 22 weight gradients is wanted, their GEMMs are skipped
 };
 size_t train_slab_floats();
 size_t train_work_floats(int Bc, int N, int Ep, int n_his, int pstep);

@@ -129,6 +129,79 @@ __global__ __launch_bounds__(CT) void k_chamfer(ChamferDev a) {
     if (tid == 0) a.out[r] = sy / cy + sx / cx;
 }
 
+// ---- gradient of chamfer toward x, as torch autograd defines it on losses.py:4-10: each min routes to its arg-min (the lowest
+// index among equal distances), norm has zero gradient at zero distance, masked-out points get zero.  Two kernels, no atomics:
+// k_chamfer_nn  one workgroup per row, both clouds in LDS as in k_chamfer: the nearest valid y of every x (nn[r][0..N)) and the
+//               nearest valid x of every y (nn[r][N..N+M)), -1 where the point is masked out or the other cloud is empty;
+//               cnt[r] = {valid x, valid y}
+// k_chamfer_grad one thread per x point: its own term, then the y points whose nearest is this x, in ascending y order
+__device__ __forceinline__ int chamfer_nearest(const float* os, int opad, int on, float qx, float qy, float qz) {
+    float best = 3.0e38f; int arg = -1;
+    for (int i = 0; i < on; ++i) {
+        const float dx = os[i] - qx, dy = os[opad + i] - qy, dz = os[2 * opad + i] - qz;
+        const float d = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));   // the forward's expression
+        if (d < best) { best = d; arg = i; }                                        // parked points give +inf
+    }
+    return arg;
+}
+__global__ __launch_bounds__(CT) void k_chamfer_nn(ChamferDev a, int* nn, float* cnt) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    __shared__ float red[CT];
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const int Np = (a.N + 1) & ~1, Mp = (a.M + 1) & ~1;
+    float* xs = sm;
+    float* ys = sm + 3 * Np;
+    const float* xr = a.x + (long)r * a.N * 3;
+    const float* yr = a.y + (long)(a.By == 1 ? 0 : r) * a.M * 3;
+    const uint8_t* xm = a.xm ? a.xm + (long)r * a.N : nullptr;
+    const uint8_t* ym = a.ym ? a.ym + (long)(a.By == 1 ? 0 : r) * a.M : nullptr;
+    const float BIG = 3.0e38f;
+    float cx = 0.f, cy = 0.f;
+    for (int i = tid; i < Np; i += CT) {
+        const bool v = i < a.N && (xm ? xm[i] != 0 : true);
+        xs[i] = v ? xr[3 * i] : BIG; xs[Np + i] = v ? xr[3 * i + 1] : BIG; xs[2 * Np + i] = v ? xr[3 * i + 2] : BIG;
+        cx += v ? 1.f : 0.f;
+    }
+    for (int j = tid; j < Mp; j += CT) {
+        const bool v = j < a.M && (ym ? ym[j] != 0 : true);
+        ys[j] = v ? yr[3 * j] : BIG; ys[Mp + j] = v ? yr[3 * j + 1] : BIG; ys[2 * Mp + j] = v ? yr[3 * j + 2] : BIG;
+        cy += v ? 1.f : 0.f;
+    }
+    __syncthreads();
+    int* row = nn + (long)r * (a.N + a.M);
+    for (int i = tid; i < a.N; i += CT)
+        row[i] = xs[i] < BIG ? chamfer_nearest(ys, Mp, a.M, xs[i], xs[Np + i], xs[2 * Np + i]) : -1;
+    for (int j = tid; j < a.M; j += CT)
+        row[a.N + j] = ys[j] < BIG ? chamfer_nearest(xs, Np, a.N, ys[j], ys[Mp + j], ys[2 * Mp + j]) : -1;
+    const float sx = block_sum(cx, red), sy = block_sum(cy, red);   // counts: exact in fp32
+    if (tid == 0) { cnt[2 * r] = sx; cnt[2 * r + 1] = sy; }
+}
+__device__ __forceinline__ void chamfer_pull(const float* xi, const float* yj, float w, float (&g)[3]) {
+    const float dx = xi[0] - yj[0], dy = xi[1] - yj[1], dz = xi[2] - yj[2];
+    const float dist = sqrtf(dx * dx + dy * dy + dz * dz);
+    if (!(dist > 0.f)) return;                                       // torch: the norm's gradient at zero is zero
+    const float s = w / dist;
+    g[0] += dx * s; g[1] += dy * s; g[2] += dz * s;
+}
+__global__ void k_chamfer_grad(ChamferDev a, const int* nn, const float* cnt, const float* gout, float* gx) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (long)a.R * a.N) return;
+    const int r = (int)(t / a.N), i = (int)(t % a.N);
+    const int* row = nn + (long)r * (a.N + a.M);
+    const float* xi = a.x + t * 3;
+    const float* yr = a.y + (long)(a.By == 1 ? 0 : r) * a.M * 3;
+    float g[3] = {0.f, 0.f, 0.f};
+    const int j0 = row[i];
+    if (j0 >= 0) {                                                   // (j0 < 0: x_i is masked out, nothing reaches it)
+        const float go = gout[r];
+        chamfer_pull(xi, yr + 3 * min(j0, a.M - 1), go / cnt[2 * r], g);          // mean over the valid x of min over y
+        const float wy = go / cnt[2 * r + 1];                        // mean over the valid y of min over x
+        for (int j = 0; j < a.M; ++j)
+            if (row[a.N + j] == i) chamfer_pull(xi, yr + 3 * j, wy, g);
+    }
+    gx[t * 3] = g[0]; gx[t * 3 + 1] = g[1]; gx[t * 3 + 2] = g[2];
+}
+
 // ---- per-row particle statistics of a (R,N,3) state tensor: box_loss (losses.py:26-35) and the x/z bounds that
 // running_cost turns into the bounding-box penalty (plan.py:41-51).  out (R,5) = [box_loss, xmin, xmax, zmin, zmax]
 struct StatsDev { const float* state; float* out; int R, N; int has_box; float bx0, bx1, bz0, bz1; };
@@ -285,6 +358,26 @@ hipError_t launch_chamfer(const float* x, const float* y, const uint8_t* xm, con
         if (dev_id < 64) attr_devices |= 1ull << dev_id;
     }
     hipLaunchKernelGGL(k_chamfer, dim3(R), dim3(CT), lds, st, a);
+    return hipGetLastError();
+}
+hipError_t launch_chamfer_backward(const float* x, const float* y, const uint8_t* xm, const uint8_t* ym, int R, int N, int M,
+                                   int By, const float* gout, int* nn, float* cnt, float* gx, hipStream_t st) {
+    ChamferDev a{x, y, xm, ym, nullptr, R, N, M, By};
+    const size_t lds = (size_t)(3 * ((N + 1) & ~1) + 3 * ((M + 1) & ~1)) * 4;
+    static unsigned long long attr_devices = 0;              // per-device function attribute (see launch_chamfer)
+    int dev_id = 0;
+    if (hipGetDevice(&dev_id) != hipSuccess) dev_id = 0;
+    if (dev_id >= 64 || !(attr_devices >> dev_id & 1ull)) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_chamfer_nn),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048);
+        if (e != hipSuccess) return e;
+        if (dev_id < 64) attr_devices |= 1ull << dev_id;
+    }
+    hipLaunchKernelGGL(k_chamfer_nn, dim3(R), dim3(CT), lds, st, a, nn, cnt);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_chamfer_grad, dim3((unsigned)(((long)R * N + CT - 1) / CT)), dim3(CT), 0, st, a, (const int*)nn,
+                       (const float*)cnt, gout, gx);
     return hipGetLastError();
 }
 hipError_t launch_state_stats(const float* state, int R, int N, const float* box4, float* out, hipStream_t st) {

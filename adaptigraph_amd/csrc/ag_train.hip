@@ -8,7 +8,8 @@
 //   dW = dY^T * [X | 1]      weight + bias gradient         reduced over rows: split-K slabs, summed in slab order in fp64 (k_reduce)
 // No float atomics anywhere: node sums walk the receiver CSR (row_ptr) and a per-graph sender CSR built here by a stable
 // counting sort (k_send_csr), in ascending edge order.  Two calls on the same inputs are bit-identical, and a row's input
-// gradient does not depend on which other rows share its launch.
+// gradient does not depend on which other rows share its launch.  ag_backward_inputs adds one more dX GEMM: the particle
+// encoder's input gradient dH1 * W0, whose columns are dLoss/dphys and dLoss/daction.
 #include "ag_common.h"
 #include <algorithm>
 #include <cstdint>
@@ -274,10 +275,20 @@ __global__ void k_dstate(const float* dsnt, const float* dpos, int B, int N, int
     }
 }
 
+// Data gradients from dXn = dH1 * W0 (rows x 6, columns [attr(2), phys, action(3)]): column 2 is dLoss/dphys of the object
+// particles (the forward pads the tool rows with a constant zero, model.py:206-207, so rows i >= n_p get zero), columns 3..5
+// dLoss/daction of every row (model.py:223).  Either output may be null.
+__global__ void k_input_grad(const float* dxn, int B, int N, int n_p, float* gphys, float* gaction) {
+    const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= (long)B * N) return;
+    if (gphys) gphys[r] = (int)(r % N) < n_p ? dxn[r * 6 + 2] : 0.f;
+    if (gaction) { gaction[r * 3] = dxn[r * 6 + 3]; gaction[r * 3 + 1] = dxn[r * 6 + 4]; gaction[r * 3 + 2] = dxn[r * 6 + 5]; }
+}
+
 inline unsigned blocks(long n, int t = 256) { return (unsigned)((n + t - 1) / t); }
 
 // ---------------------------------------------------------------------------------------------------------- host helpers
-struct Ctx { hipStream_t st; float* slab; double* part; };
+struct Ctx { hipStream_t st; float* slab; double* part; bool want_w; };   // want_w false: no weight gradient is wanted, linear_dw is skipped
 
 // C (M x N) = A (M x K) * B (K x N) with the epilogue of GemmArgs
 hipError_t gemm(hipStream_t st, GemmArgs a) {
@@ -315,7 +326,7 @@ hipError_t linear_dx(hipStream_t st, const float* dY, long lddy, long rows, int 
 // gW[:, col0:col0+in] += dY^T X and (if gb) gb += column sums of dY, over `rows` rows: split-K slabs reduced in slab order
 hipError_t linear_dw(const Ctx& c, const float* dY, long lddy, long rows, int out, const float* X, long ldx, int in, float* gW,
                      int ldw, int col0, float* gb) {
-    if (rows <= 0) return hipSuccess;
+    if (rows <= 0 || !c.want_w) return hipSuccess;
     const int ncols = in + (gb ? 1 : 0);
     // short fma chains: slabs of 32 rows (one K tile), more only beyond 1024 slabs (32,768 rows)
     const int kslab = (int)(TK * ((rows + (long)TK * kMaxSlabs - 1) / ((long)TK * kMaxSlabs)));
@@ -359,7 +370,7 @@ hipError_t train_backward_chunk(const TrainArgs& t, int b0, int nb, float* wsf, 
     const long n = (long)nb * N, ne = (long)nb * Ep;
     const float* const* W = t.w;
     float* const* G = t.g;
-    Ctx c{st, slab, reinterpret_cast<double*>(slab + (size_t)kMaxSlabs * NF * (NF + 1))};
+    Ctx c{st, slab, reinterpret_cast<double*>(slab + (size_t)kMaxSlabs * NF * (NF + 1)), t.want_w};
     size_t off = 0;
     auto take = [&](size_t k) { float* p = wsf + off; off += (k + 63) / 64 * 64; return p; };
     float* xn = take(n * 6); float* ph1 = take(n * NF); float* ph2 = take(n * NF); float* penc = take(n * NF);
@@ -446,6 +457,12 @@ hipError_t train_backward_chunk(const TrainArgs& t, int b0, int nb, float* wsf, 
     TRY(linear_dw(c, dq, NF, n, NF, ph1, NF, NF, G[2], NF, 0, G[3]));
     TRY(linear_dx(st, dq, NF, n, NF, W[2], NF, 0, NF, T, NF, 0, ph1, NF));
     TRY(linear_dw(c, T, NF, n, NF, xn, 6, 6, G[0], 6, 0, G[1]));
+    // ---- data gradients (ag_backward_inputs): dXn = dH1 * W0 into dq, which nothing reads any more (model.py:206-223)
+    if (t.dphys || t.daction) {
+        TRY(linear_dx(st, T, NF, n, NF, W[0], 6, 0, 6, dq, 6, 0, nullptr, 0));
+        LAUNCH(k_input_grad, n, dq, nb, N, n_p, t.dphys ? t.dphys + (long)b0 * N : nullptr,
+               t.daction ? t.daction + (long)b0 * N * 3 : nullptr);
+    }
     // ---- relation encoder (model.py:303); dren already carries the ReLU mask of renc
     TRY(linear_dw(c, dren, NF, ne, NF, rh2, NF, NF, G[10], NF, 0, G[11]));
     TRY(linear_dx(st, dren, NF, ne, NF, W[10], NF, 0, NF, dtmp, NF, 0, rh2, NF));

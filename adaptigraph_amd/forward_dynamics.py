@@ -29,6 +29,7 @@ import torch
 
 from . import _lib
 from .context import ptr, current_stream, _require_gpu
+from .graph import construct_edges_index
 from .model import DynamicsPredictor
 from .plan_utils import decode_action
 
@@ -240,6 +241,88 @@ def dynamics_masked(state_init, state_mask, action, model, device, ppm_optimizer
     out = _run(model, dev, task, ppm_optimizer, physics_param, B, 1, N_o, 1, state0, mask_u8, xz, delta, repeat,
                sync=_sync, overflow_flag=_overflow_flag)
     return {"state_seqs": out[:, 0], "action_seqs": decoded[:, 0].to(action.device)}
+
+
+def _masked_mean_y(pos, maskf, cnt):
+    """forward_dynamics.py:233 / :360: the tool height = mean y of the valid object particles.  Summed in float64 and rounded
+    once, so that a row's value does not depend on how torch tiles the reduction for the batch it happens to sit in."""
+    return ((pos[:, :, 1] * maskf).to(torch.float64).sum(1) / cnt).to(torch.float32)
+
+
+def dynamics_masked_diff(state_init, state_mask, action, model, device, ppm_optimizer, physics_param=None, _edges_out=None):
+    """dynamics_masked under torch autograd: the same arguments and result dictionary, differentiable toward the physics
+    parameter (and toward state_init where it requires grad).  forward_dynamics.py:209-399 restated step by step instead of the
+    fused rollout: per step the engine's batch edge builder on the DETACHED positions (index lists; edges are constants, as they
+    are under the reference's autograd), DynamicsPredictor.forward_diff (ag_forward / ag_backward_inputs), the tool height as the
+    masked mean of the prediction and the history shift as torch ops; state_seqs[b] is the prediction of step action_repeat[b].
+    Like the reference every row is stepped to the batch maximum of action_repeat (:351) and a graph with more than max_nR edges
+    raises Exception("Exceeds max dims").
+
+    physics_param[material]: the reference's (dim,) tensor shared by all rows, or (B,1) / (B,n_p): one value per row / per
+    particle.  _edges_out: a list that receives every step's EdgeList (tests)."""
+    task = ppm_optimizer.task_config
+    dev = _require_gpu(device)
+    if not isinstance(model, DynamicsPredictor):
+        raise TypeError("model must be an adaptigraph_amd.DynamicsPredictor")
+    eng = model.engine(dev)
+    n_his, max_n, max_nR = int(task["n_his"]), int(task["max_n"]), int(task["max_nR"])
+    assert n_his == model.n_his, "task_config['n_his'] (forward_dynamics.py:16) must be the model's n_his"
+    B, N_o, M = state_init.shape[0], state_init.shape[1], ppm_optimizer.eef_num
+    action_cpu = action.detach().to("cpu", torch.float32)[:, None]                         # :218
+    decoded, repeat = decode_action(action_cpu, push_length=task["push_length"])
+    xz, delta = _tool_layout(decoded, action_cpu[:, :, 2], task)
+    assert xz.shape[2] == M
+    repeat = repeat[:, 0].to(dev)
+    n_steps = int(repeat.max().item())
+    xz, delta = xz[:, 0].to(dev), delta[:, 0].to(dev)
+    grip = float(0.01 * task["sim_real_ratio"]) if task["gripper_enable"] else None
+
+    state = state_init.to(device=dev, dtype=torch.float32)                                 # :225
+    mask = state_mask.detach().to(dev).to(torch.bool)
+    maskf, cnt = mask.to(torch.float32), mask.sum(1).to(torch.float64)
+
+    def tools_at(x, z, pos):                                                               # :233-273, :360-365
+        y = _masked_mean_y(pos, maskf, cnt)
+        if grip is not None:
+            y = y + grip
+        return torch.stack([x, y[:, None].expand(B, M), z], -1)
+
+    eef = tools_at(xz[..., 0], xz[..., 1], state)
+    states = torch.cat([state[:, None].expand(B, n_his, N_o, 3), eef[:, None].expand(B, n_his, M, 3)], 2)   # :278-280
+    act = torch.cat([torch.zeros((B, N_o, 3), device=dev), delta], 1)                      # :282-283
+    attrs = torch.zeros((B, N_o + M, 2), device=dev)                                       # :285-288
+    attrs[:, :N_o, 0] = maskf
+    attrs[:, N_o:, 1] = 1.0
+    p_instance = torch.zeros((B, N_o, max_n), device=dev)                                  # :292-300 (one instance: a prefix)
+    p_instance[:, :, 0] = (torch.arange(N_o, device=dev)[None, :] < mask.sum(1)[:, None]).to(torch.float32)
+    tool_mask = torch.zeros((B, N_o + M), dtype=torch.bool, device=dev)                    # :302-307
+    tool_mask[:, N_o:] = True
+    full_mask = torch.cat([mask, tool_mask[:, N_o:]], 1)
+
+    material_dims = ppm_optimizer.material_dims
+    physics_param = ppm_optimizer.physics_param if physics_param is None else physics_param
+    assert len(material_dims) == 1          # the model asserts exactly one *_physics_param key (model.py:186-187)
+    (name, _dim), = material_dims.items()
+    pp = physics_param[name].to(device=dev, dtype=torch.float32)                           # :337-339
+    if pp.dim() == 1:
+        pp = pp[None].expand(B, pp.numel())
+    assert pp.dim() == 2 and pp.shape[0] == B and pp.shape[1] in (1, N_o), \
+        f"physics parameter of shape {tuple(pp.shape)}: expected (dim,), ({B}, 1) or ({B}, {N_o})"
+
+    seqs = torch.zeros((B, N_o, 3), device=dev)                                            # :231
+    for ai in range(1, n_steps + 1):                                                       # :351
+        edges = construct_edges_index(states[:, -1].detach(), ppm_optimizer.adj_thresh, full_mask, tool_mask,
+                                      topk=int(task["topk"]), connect_tools_all=bool(task["connect_tools_all"]),
+                                      edge_cap=max_nR, engine=eng)                         # :366-370 (:316-319 for the first)
+        if _edges_out is not None:
+            _edges_out.append(edges)
+        pred, _ = model.forward_diff(state=states, attrs=attrs, p_instance=p_instance, action=act, edges=edges,
+                                     **{name + "_physics_param": pp})                      # :354 (overflow -> "Exceeds max dims")
+        seqs = torch.where((repeat == ai)[:, None, None], pred, seqs)                      # :356-357
+        last = states[:, -1, N_o:] + act[:, N_o:]                                          # :361
+        cur = torch.cat([pred, tools_at(last[..., 0], last[..., 2], pred)], 1)            # :363-367
+        states = torch.cat([states[:, 1:], cur[:, None]], 1)                               # :372
+    return {"state_seqs": seqs, "action_seqs": decoded[:, 0].to(action.device)}
 
 
 @torch.no_grad()

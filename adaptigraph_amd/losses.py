@@ -42,6 +42,45 @@ def chamfer(x, y, x_mask=None, y_mask=None):
     return out
 
 
+class _ChamferFunction(torch.autograd.Function):
+    """ag_cost_chamfer forward, ag_cost_chamfer_backward backward; gradient toward x only."""
+
+    @staticmethod
+    def forward(ctx, x, y, xm, ym):
+        dev = x.device
+        eng = default_engine(dev)
+        R, N, _ = x.shape
+        By, M, _ = y.shape
+        out = torch.empty(R, device=dev, dtype=torch.float32)
+        eng.check(eng.lib.ag_cost_chamfer(eng.ctx, current_stream(dev), ptr(x), ptr(y), ptr(xm), ptr(ym), R, N, M, By, ptr(out)))
+        ctx.save_for_backward(x, y, xm, ym)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        x, y, xm, ym = ctx.saved_tensors
+        dev = x.device
+        eng = default_engine(dev)
+        R, N, _ = x.shape
+        By, M, _ = y.shape
+        g_out = g_out.to(torch.float32).contiguous()
+        g_x = torch.empty_like(x)
+        eng.check(eng.lib.ag_cost_chamfer_backward(eng.ctx, current_stream(dev), ptr(x), ptr(y), ptr(xm), ptr(ym), R, N, M, By,
+                                                   ptr(g_out), ptr(g_x)))
+        return g_x, None, None, None
+
+
+def chamfer_diff(x, y, x_mask=None, y_mask=None):
+    """chamfer() under torch autograd: the same forward (ag_cost_chamfer, same bits) and the gradient toward x that autograd
+    gives on losses.py:4-10 (each min routes to its arg-min, zero at zero distance, zero for masked-out points).  y is data."""
+    dev = _require_gpu(x.device)
+    x = x.to(torch.float32).contiguous()
+    y = y.detach().to(device=dev, dtype=torch.float32).contiguous()
+    xm = x_mask.to(dev).to(torch.bool).contiguous().view(torch.uint8) if x_mask is not None else None
+    ym = y_mask.to(dev).to(torch.bool).contiguous().view(torch.uint8) if y_mask is not None else None
+    return _ChamferFunction.apply(x, y, xm, ym)
+
+
 def mean_chamfer(state_pred, state_real, state_pred_mask, state_real_mask):
     """losses.py:12-24: per-pair masked chamfer, returned as a numpy float64 array like the reference."""
     out = chamfer(state_pred, state_real, state_pred_mask, state_real_mask)

@@ -4,14 +4,15 @@
 The nn.Module tree exists only so that state_dict keys, load_state_dict, .to() and .eval() behave like the reference;
 no torch op of it is ever run - forward() hands raw device pointers to the C-ABI.  With grad enabled and the parameters or
 `state` requiring grad, forward() runs through autograd.DynamicsFunction (ag_forward + ag_backward); otherwise it is the
-inference path.  Parameters are frozen after construction; train(True) unfreezes them and train(False) / eval() freezes them.
+inference path.  forward_diff() is the same forward, differentiable toward `action` and the physics parameter as well
+(ag_backward_inputs): the entry of the gradient-based physics-parameter fit; forward() keeps refusing data gradients.  Parameters are frozen after construction; train(True) unfreezes them and train(False) / eval() freezes them.
 """
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
 
-from .autograd import DynamicsFunction
+from .autograd import DynamicsFunction, DynamicsDiffFunction
 from .context import Engine, ptr, current_stream, _require_gpu, STATE_DICT_ORDER
 from .graph import EdgeList
 
@@ -20,6 +21,19 @@ def _mlp3(n_in, n_hidden, n_out):
     # same parameter names as the reference's Encoder.model (indices 0, 2, 4 are the Linear layers)
     return nn.Sequential(nn.Linear(n_in, n_hidden), nn.ReLU(), nn.Linear(n_hidden, n_hidden), nn.ReLU(),
                          nn.Linear(n_hidden, n_out), nn.ReLU())
+
+
+class _ExpandRows(torch.autograd.Function):
+    """(B,1) -> (B,n_p), model.py:191-197.  Backward: the sum over the n_p columns in float64, rounded once - a row's gradient
+    then does not depend on how torch would tile an fp32 reduction for the batch the row sits in."""
+
+    @staticmethod
+    def forward(ctx, pp, n_p):
+        return pp.expand(pp.shape[0], n_p).contiguous()
+
+    @staticmethod
+    def backward(ctx, g):
+        return g.to(torch.float64).sum(1, keepdim=True).to(torch.float32), None
 
 
 class _Holder(nn.Module):
@@ -169,6 +183,43 @@ class DynamicsPredictor(nn.Module):
         state = state.to(torch.float32).contiguous()
         assert state.shape == (attrs.size(0), self.n_his, attrs.size(1), 3)
         return DynamicsFunction.apply(eng, edges, n_p, state, attrs, action, phys, group, *params)
+
+    def forward_diff(self, state, attrs, Rr=None, Rs=None, p_instance=None, action=None, particle_den=None, obj_mask=None,
+                     edges: EdgeList | None = None, **kwargs):
+        """forward() with gradients toward state, action, the physics parameter ((B,1) or (B,n_p), model.py:186-207) and, where
+        they require grad, the parameters: same kernels and bits forward, ag_backward_inputs backward.  The (B,N) gradient of the
+        per-particle parameter comes back in the caller's shape: (B,1) is the sum over the n_p object rows in a fixed order.
+        attrs and p_instance are data: NotImplementedError if they require grad.  Edges are constants."""
+        for name, t in (("attrs", attrs), ("p_instance", p_instance), ("Rr", Rr), ("Rs", Rs)):
+            if torch.is_tensor(t) and t.requires_grad:
+                raise NotImplementedError(f"DynamicsPredictor.forward_diff: gradient with respect to {name} is not implemented "
+                                          "(gradients reach state, action, the physics parameter and the parameters)")
+        params = self.ordered_parameters()
+        dev = _require_gpu(state.device)
+        eng = self.engine(dev)
+        B, N = attrs.size(0), attrs.size(1)
+        n_p, n_inst = p_instance.size(1), p_instance.size(2)
+        n_s = N - n_p
+        physics_keys = [k for k in kwargs.keys() if k.endswith("_physics_param")]
+        assert len(physics_keys) == 1                                            # model.py:186-187
+        pp = kwargs[physics_keys[0]].to(device=dev, dtype=torch.float32)
+        if pp.size(-1) == 1:
+            pp = _ExpandRows.apply(pp.reshape(B, 1), n_p)                        # model.py:191-197
+        else:
+            pp = pp.reshape(B, n_p)                                              # model.py:204
+        phys = torch.cat([pp, torch.zeros(B, n_s, device=dev)], 1).contiguous()  # model.py:206-207
+        assert action is not None                                                # model.py:222
+        with torch.no_grad():
+            group = torch.cat([p_instance.to(torch.float32), torch.zeros(B, n_s, n_inst, device=dev)], 1).contiguous()
+            if edges is None:
+                assert Rr is not None and Rs is not None
+                edges = EdgeList.from_dense(Rr, Rs)
+            attrs = attrs.to(torch.float32).contiguous()
+        assert edges.N == N
+        action = action.to(device=dev, dtype=torch.float32).contiguous()
+        state = state.to(torch.float32).contiguous()
+        assert state.shape == (B, self.n_his, N, 3)
+        return DynamicsDiffFunction.apply(eng, edges, n_p, state, attrs, action, phys, group, *params)
 
     def _forward_nograd(self, state, attrs, Rr, Rs, p_instance, action, edges, kwargs):
         dev = _require_gpu(state.device)

@@ -29,7 +29,7 @@
  *   - WHICH ENTRY POINTS BLOCK THE HOST, and when (everything else only enqueues):
  *       ag_ctx_load_weights, ag_ctx_set_precision     always (host repack + copies)
  *       ag_forward, ag_rollout                        once, at the end: they return the overflow verdict (AG_ERR_MAX_NR)
- *       ag_backward                                   at the start (edge counts) and at the end
+ *       ag_backward, ag_backward_inputs               at the start (edge counts) and at the end
  *       ag_rollout_work                               for its plan (and a base rollout, if none is kept): it returns host numbers
  *       ag_ctx_rollout_counts (after a device-planned call without prefix sharing), ag_ctx_share_counts   wait for the device
  *       ag_rollout_async, ag_rollout_actions          only when the contact-free prefix is in play (option "share_prefix";
@@ -255,7 +255,8 @@ int ag_forward(ag_ctx* ctx, void* stream, const float* d_state, const float* d_a
  *   Inputs: those of ag_forward, plus d_w[22]: the 22 fp32 parameter tensors in ag_ctx_load_weights order, plain (out, in) /
  *   (out,) row-major (the gradient is taken with respect to exactly these; the ctx's loaded weights are not used), and
  *   d_grad_pos, d_grad_motion (B,n_p,3): dLoss/dpred_pos, dLoss/dpred_motion, either NULL (= zero).
- *   Outputs (each NULL = not wanted): d_grad_state (B,n_his,N,3) dLoss/dstate; d_grad_w[22] matching d_w.  Gradients reach
+ *   Outputs (each NULL = not wanted): d_grad_state (B,n_his,N,3) dLoss/dstate; d_grad_w[22] matching d_w
+ *   (when d_grad_w is NULL or all of its entries are, the weight-gradient contractions are skipped).  Gradients reach
  *   state and the parameters only; attrs, action, phys and group are data.  Edges beyond d_n_edges[b] and particles without
  *   edges and beyond n_p get zero gradient.  Deterministic: no float atomics, fixed reduction order (two calls on the same
  *   inputs give the same bits).
@@ -266,6 +267,17 @@ int ag_backward(ag_ctx* ctx, void* stream, const float* d_state, const float* d_
                 const int32_t* d_row_ptr, const int32_t* d_n_edges, int32_t edge_cap, int32_t B, int32_t N, int32_t n_p,
                 const float* const* d_w, const float* d_grad_pos, const float* d_grad_motion, float* d_grad_state,
                 float* const* d_grad_w);
+
+/* ag_backward plus the data gradients of the particle encoder's input (model.py:206-223): d_grad_phys (B,N) dLoss/dphys (zero
+ * for the tool rows n >= n_p, which the forward pads with a constant zero) and d_grad_action (B,N,3) dLoss/daction, each NULL =
+ * not wanted.  One implementation: ag_backward is this call with both NULL, and every other output carries the same bits either
+ * way.  Same rules: exact fp32, no float atomics, fixed reduction order; a row's data gradient does not depend on which other
+ * rows share the call.  Edges are constants: nothing is differentiated through the graph construction. */
+int ag_backward_inputs(ag_ctx* ctx, void* stream, const float* d_state, const float* d_attrs, const float* d_action,
+                       const float* d_phys, const float* d_group, int32_t n_inst, const int32_t* d_recv, const int32_t* d_send,
+                       const int32_t* d_row_ptr, const int32_t* d_n_edges, int32_t edge_cap, int32_t B, int32_t N, int32_t n_p,
+                       const float* const* d_w, const float* d_grad_pos, const float* d_grad_motion, float* d_grad_state,
+                       float* const* d_grad_w, float* d_grad_phys, float* d_grad_action);
 
 /* Replaces the device side of dynamics() / dynamics_masked() (src/planning/forward_dynamics.py:12-205, 209-399):
  * the whole look-ahead x action-repeat loop, graph rebuilt every step, no host sync inside.
@@ -335,6 +347,14 @@ int ag_rollout_work(ag_ctx* ctx, void* stream, const ag_rollout_params* p, const
  * d_out (R,).  N + M must fit the LDS tile (<= ~13k points). */
 int ag_cost_chamfer(ag_ctx* ctx, void* stream, const float* d_x, const float* d_y, const uint8_t* d_xmask,
                     const uint8_t* d_ymask, int32_t R, int32_t N, int32_t M, int32_t By, float* d_out);
+
+/* Gradient of ag_cost_chamfer toward x as torch autograd defines it on losses.py:4-10: inputs of ag_cost_chamfer plus
+ * d_grad_out (R,) dLoss/dout -> d_grad_x (R,N,3), fully written.  Each min routes to its arg-min (lowest index among equal
+ * distances), the norm has zero gradient at zero distance, masked-out x points get zero.  No atomics: repeated calls give the
+ * same bits.  Asynchronous on the stream. */
+int ag_cost_chamfer_backward(ag_ctx* ctx, void* stream, const float* d_x, const float* d_y, const uint8_t* d_xmask,
+                             const uint8_t* d_ymask, int32_t R, int32_t N, int32_t M, int32_t By, const float* d_grad_out,
+                             float* d_grad_x);
 
 /* Particle statistics of d_state (R,N,3) -> d_out (R,5) = [box_loss, xmin, xmax, zmin, zmax]: box_loss (losses.py:26-35)
  * against h_box4 = {xmin, xmax, zmin, zmax} (NULL: entry 0 is 0), and the x/z bounds running_cost needs (plan.py:41-44). */

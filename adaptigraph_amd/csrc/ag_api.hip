@@ -4,6 +4,7 @@
 #include "ag_common.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstddef>
 #include <cstdio>
@@ -117,6 +118,7 @@ struct ag_ctx {
     long long steps_enqueued = 0, steps_bound = 0;      // model forwards (per chunk) enqueued by the last rollout call / what the bound alone gives
     const int* d_share_nns = nullptr;                 // edges the base encode ran over (workspace of the last rollout call), or null
     float* d_cself = nullptr;    // (256, NFP): rows 0/1 = C of an object / tool self-loop edge (see GraphBufs)
+    char* d_self_mini = nullptr; // the constant 2-particle graph those rows are computed on (enqueue_self_rows)
     // in-library streams of a call: alternate chunks run on them so that the HBM-bound kernels of one chunk overlap the
     // MFMA-bound chains of the other (fork/join with events around every rollout call)
     int n_streams = 2;
@@ -283,135 +285,6 @@ struct Scoped {
     ~Scoped() { prof_mark(c, fam, 1); }
 };
 
-// ---------------------------------------------------------------------------------------------- weight packing
-// MFMA A-operand image of a layer: [chunk q][m-block][lane][4 steps]; lane l supplies out-feature 32*mb + (l&31)
-// for input slot k(s, l>>5).  See ag_mlp.hip header.
-int slot_of(int s, int h) {
-    const int t = s < 64 ? s / 16 : 4, r = s < 64 ? s % 16 : s - 64;
-    return 32 * t + (r & 3) + 8 * (r >> 2) + 4 * h;
-}
-void pack_layer(float* dst, const float* W, int ld, int col0, int out_dim, int in_dim, const float* bias, int MB) {
-    for (int q = 0; q < KCH; ++q)
-        for (int mb = 0; mb < MB; ++mb)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int e = 0; e < 4; ++e) {
-                    const int k = slot_of(4 * q + e, lane >> 5), m = 32 * mb + (lane & 31);
-                    float v = 0.f;
-                    if (m < out_dim) {
-                        if (k < in_dim) v = W[(size_t)m * ld + col0 + k];
-                        else if (k == ONE_F && bias) v = bias[m];
-                    }
-                    dst[((size_t)(q * MB + mb) * 64 + lane) * 4 + e] = v;
-                }
-}
-void pack_first(float* dst, const float* W, int in_dim, const float* bias, int nch) {
-    for (int q = 0; q < nch; ++q)
-        for (int mb = 0; mb < 5; ++mb)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int e = 0; e < 4; ++e) {
-                    const int k = 2 * (4 * q + e) + (lane >> 5), m = 32 * mb + (lane & 31);
-                    float v = 0.f;
-                    if (m < NF) {
-                        if (k < in_dim) v = W[(size_t)m * in_dim + k];
-                        else if (k == in_dim) v = bias[m];
-                    }
-                    dst[((size_t)(q * 5 + mb) * 64 + lane) * 4 + e] = v;
-                }
-}
-
-// ---- latency-mode chains (ag_lat.hip): A-operand image of v_mfma_f32_16x16x4_f32, [chunk of 4 k-steps][tile][lane][4].
-// Register r of tile T in lane group g stands for feature 16T + 8(r>>1) + 4(g&1) + 2(r&1) + (g>>1): the k sequence of the
-// 32-row chains (slot_of) cut into steps of four, so that both kernel families round identically.  >= 152: dead slot.
-int feat_lat(int T, int g, int r) {
-    const int f = 16 * T + 8 * (r >> 1) + 4 * (g & 1) + 2 * (r & 1) + (g >> 1);
-    return f < 152 ? f : -1;
-}
-void pack_layer_lat(float* dst, const float* W, int ld, int col0, int out_dim, int in_dim, const float* bias, bool head) {
-    const int ntile = head ? 1 : 10;
-    for (int c = 0; c < 10; ++c)
-        for (int mt = 0; mt < ntile; ++mt)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int e = 0; e < 4; ++e) {
-                    const int s = 4 * c + e;
-                    float v = 0.f;
-                    if (s < 38) {
-                        const int T = s < 36 ? s / 4 : 9, r = s < 36 ? s % 4 : s - 36;
-                        const int k = feat_lat(T, lane >> 4, r), i = lane & 15;
-                        // D row 4g + r of an output tile = A row i: the head keeps its 3 outputs in rows 0..2
-                        const int m = head ? i : feat_lat(mt, i >> 2, i & 3);
-                        if (m >= 0 && m < out_dim && k >= 0) {
-                            if (k < in_dim) v = W[(size_t)m * ld + col0 + k];
-                            else if (k == ONE_F && bias) v = bias[m];
-                        }
-                    }
-                    dst[((size_t)(c * ntile + mt) * 64 + lane) * 4 + e] = v;
-                }
-}
-void pack_first_lat(float* dst, const float* W, int in_dim, const float* bias, int nchunks) {
-    for (int c = 0; c < nchunks; ++c)
-        for (int mt = 0; mt < 10; ++mt)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int e = 0; e < 4; ++e) {
-                    const int k = 4 * (4 * c + e) + (lane >> 4), i = lane & 15, m = feat_lat(mt, i >> 2, i & 3);
-                    float v = 0.f;
-                    if (m >= 0 && m < NF) {
-                        if (k < in_dim) v = W[(size_t)m * in_dim + k];
-                        else if (k == in_dim) v = bias[m];
-                    }
-                    dst[((size_t)(c * 10 + mt) * 64 + lane) * 4 + e] = v;
-                }
-}
-
-// ---- bf16x3 weight image (see ag_mlp.hip): every weight is split exactly into three bf16 pieces
-uint16_t bf16_rn(float f) {
-    uint32_t u; memcpy(&u, &f, 4);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-float bf16_f(uint16_t h) { uint32_t u = (uint32_t)h << 16; float f; memcpy(&f, &u, 4); return f; }
-void split3(float w, uint16_t out[3]) {
-    out[0] = bf16_rn(w);
-    const float r = w - bf16_f(out[0]);
-    out[1] = bf16_rn(r);
-    const float q = r - bf16_f(out[1]);
-    out[2] = bf16_rn(q);
-}
-// image index (uint16 units) of element j of lane `lane`, part `part`, m-block mb, k-step ks (MB m-blocks per k-step)
-size_t b3_idx(int ks, int MB, int mb, int part, int lane, int j) { return ((((size_t)ks * MB + mb) * 3 + part) * 64 + lane) * 8 + j; }
-void pack_layer_b3(uint16_t* dst, const float* W, int ld, int col0, int out_dim, int in_dim, const float* bias, int MB) {
-    for (int ks = 0; ks < 10; ++ks)                        // k-step ks = 2*tile + u
-        for (int mb = 0; mb < MB; ++mb)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int j = 0; j < 8; ++j) {
-                    const int t = ks >> 1, u = ks & 1, h = lane >> 5;
-                    const int k = 32 * t + 16 * u + (j & 3) + 8 * (j >> 2) + 4 * h, m = 32 * mb + (lane & 31);
-                    float v = 0.f;
-                    if (m < out_dim) {
-                        if (k < in_dim) v = W[(size_t)m * ld + col0 + k];
-                        else if (k == ONE_F && bias) v = bias[m];
-                    }
-                    uint16_t p3[3];
-                    split3(v, p3);
-                    for (int part = 0; part < 3; ++part) dst[b3_idx(ks, MB, mb, part, lane, j)] = p3[part];
-                }
-}
-void pack_first_b3(uint16_t* dst, const float* W, int in_dim, const float* bias) {
-    for (int ks = 0; ks < 2; ++ks)
-        for (int mb = 0; mb < 5; ++mb)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int j = 0; j < 8; ++j) {
-                    const int k = 16 * ks + 8 * (lane >> 5) + j, m = 32 * mb + (lane & 31);
-                    float v = 0.f;
-                    if (m < NF) {
-                        if (k < in_dim) v = W[(size_t)m * in_dim + k];
-                        else if (k == in_dim) v = bias[m];
-                    }
-                    uint16_t p3[3];
-                    split3(v, p3);
-                    for (int part = 0; part < 3; ++part) dst[b3_idx(ks, 5, mb, part, lane, j)] = p3[part];
-                }
-}
-
 // ---------------------------------------------------------------------------------------------- workspace
 struct Work {
     GraphBufs g{};
@@ -572,30 +445,40 @@ int run_model(ag_ctx* c, const GraphBufs& g, float* pred_pos, float* pred_motion
 
 // C rows of the two kinds of self-loop edge (object: attrs 1,0; tool: attrs 0,1), through the real edge chain of the
 // ACTIVE precision mode on a 2-particle, 2-edge graph {(0,0),(1,1)} - bitwise what k_edge_enc produces for such edges.
-int compute_self_rows(ag_ctx* c) {
+// The 2-graph's inputs are constants: uploaded once per context (d_self_mini); enqueue_self_rows only launches the edge chain on
+// `st`, so ag_ctx_load_weights_device / ag_adam_step refresh the rows without a wait.
+struct SelfMini { float node_in[2 * NODE_IN]; float feat12[2 * F15_PITCH]; float group[2]; int recv[2]; int send[2]; int n_edges; int pad; };
+int enqueue_self_rows(ag_ctx* c, hipStream_t st) {
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->d_cself) HIPCHK(c, dev_alloc(c, reinterpret_cast<void**>(&c->d_cself), 256 * NFP * 4));
-    struct Mini { float node_in[2 * NODE_IN]; float feat12[2 * F15_PITCH]; float group[2]; int recv[2]; int send[2]; int n_edges; int pad; } h{};
-    h.node_in[0] = 1.f; h.node_in[6] = 1.f;                         // object particle
-    h.node_in[NODE_IN + 1] = 1.f; h.node_in[NODE_IN + 6] = 1.f;     // tool particle
-    h.group[0] = 1.f;
-    h.recv[0] = 0; h.recv[1] = 1; h.send[0] = 0; h.send[1] = 1; h.n_edges = 2;
-    char* d = nullptr;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&d), sizeof(Mini)));
-    HIPCHK(c, hipMemcpy(d, &h, sizeof(Mini), hipMemcpyHostToDevice));
+    if (!c->d_self_mini) {
+        SelfMini h{};
+        h.node_in[0] = 1.f; h.node_in[6] = 1.f;                         // object particle
+        h.node_in[NODE_IN + 1] = 1.f; h.node_in[NODE_IN + 6] = 1.f;     // tool particle
+        h.group[0] = 1.f;
+        h.recv[0] = 0; h.recv[1] = 1; h.send[0] = 0; h.send[1] = 1; h.n_edges = 2;
+        HIPCHK(c, dev_alloc(c, reinterpret_cast<void**>(&c->d_self_mini), sizeof(SelfMini)));
+        HIPCHK(c, hipMemcpy(c->d_self_mini, &h, sizeof(SelfMini), hipMemcpyHostToDevice));
+    }
+    char* d = c->d_self_mini;
     GraphBufs g{};
     g.n_his = c->dims.n_his;
-    g.node_in = reinterpret_cast<float*>(d + offsetof(Mini, node_in));
-    g.feat12 = reinterpret_cast<float*>(d + offsetof(Mini, feat12));
-    g.group = reinterpret_cast<float*>(d + offsetof(Mini, group));
-    g.recv = reinterpret_cast<int*>(d + offsetof(Mini, recv));
-    g.send = reinterpret_cast<int*>(d + offsetof(Mini, send));
-    g.n_edges = reinterpret_cast<int*>(d + offsetof(Mini, n_edges));
+    g.node_in = reinterpret_cast<float*>(d + offsetof(SelfMini, node_in));
+    g.feat12 = reinterpret_cast<float*>(d + offsetof(SelfMini, feat12));
+    g.group = reinterpret_cast<float*>(d + offsetof(SelfMini, group));
+    g.recv = reinterpret_cast<int*>(d + offsetof(SelfMini, recv));
+    g.send = reinterpret_cast<int*>(d + offsetof(SelfMini, send));
+    g.n_edges = reinterpret_cast<int*>(d + offsetof(SelfMini, n_edges));
     g.C = c->d_cself; g.B = 1; g.N = 2; g.n_p = 1; g.n_inst = 1; g.edge_cap = 2; g.c_cap = 256;
     g.wb3 = c->precision == 1 ? c->d_wb3 : nullptr;
-    hipError_t e = launch_edge_enc(c->d_w, g, nullptr);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    (void)hipFree(d);
+    hipError_t e = launch_edge_enc(c->d_w, g, st);
+    if (e != hipSuccess) return fail(c, AG_ERR_HIP, "self-loop C rows: %s", hipGetErrorString(e));
+    return AG_OK;
+}
+int compute_self_rows(ag_ctx* c) {
+    int rc = enqueue_self_rows(c, nullptr);
+    if (rc) return rc;
+    hipError_t e = hipDeviceSynchronize();
     if (e != hipSuccess) return fail(c, AG_ERR_HIP, "self-loop C rows: %s", hipGetErrorString(e));
     return AG_OK;
 }
@@ -628,6 +511,30 @@ int build_edges(ag_ctx* c, hipStream_t st, EdgeArgs& a) {
     a.block_min_rows = c->opt.edge_block_min;
     c->prof_stream = st;
     HIPCHK(c, launch_edge_build(a, st, prof_mark, c));
+    return AG_OK;
+}
+
+// DynamicsPredictor.forward over the batch, in launch chunks of Bc on a workspace carved for Bc (ag_forward, and every step of
+// ag_train_step: same kernels, same bits).  n_eff: the guarded per-graph edge counts (launch_edge_guard)
+int enqueue_forward(ag_ctx* c, const Work& w, int Bc, const float* d_state, const float* d_attrs, const float* d_action,
+                    const float* d_phys, const float* d_group, int n_inst, const int32_t* d_recv, const int32_t* d_send,
+                    const int32_t* d_row_ptr, const int* n_eff, int edge_cap, int B, int N, int n_p, float* d_pred_pos,
+                    float* d_pred_motion, hipStream_t st) {
+    int rc = AG_OK;
+    for (int b0 = 0; b0 < B; b0 += Bc) {
+        const int nb = std::min(Bc, B - b0);
+        GraphBufs g = w.g;
+        g.B = nb; g.n_p = n_p; g.n_his = c->dims.n_his;
+        g.wb3 = c->precision == 1 ? c->d_wb3 : nullptr;
+        g.group = const_cast<float*>(d_group) + (size_t)b0 * N * n_inst;
+        g.recv = d_recv + (size_t)b0 * edge_cap; g.send = d_send + (size_t)b0 * edge_cap;
+        g.row_ptr = d_row_ptr + (size_t)b0 * (N + 1); g.n_edges = n_eff + b0; g.n_guard = n_eff + b0;
+        { Scoped p(c, FAM_PREP);
+          HIPCHK(c, launch_prep(d_state + (size_t)b0 * c->dims.n_his * N * 3, d_attrs + (size_t)b0 * N * 2,
+                                d_action + (size_t)b0 * N * 3, d_phys + (size_t)b0 * N, g, st)); }
+        rc = run_model(c, g, d_pred_pos + (size_t)b0 * n_p * 3, d_pred_motion + (size_t)b0 * n_p * 3, st);
+        if (rc) return rc;
+    }
     return AG_OK;
 }
 
@@ -674,6 +581,7 @@ int ag_ctx_destroy(ag_ctx* c) {
     if (c->d_wb3) (void)hipFree(c->d_wb3);
     if (c->d_wlat) (void)hipFree(c->d_wlat);
     if (c->d_cself) (void)hipFree(c->d_cself);
+    if (c->d_self_mini) (void)hipFree(c->d_self_mini);
     delete c;
     return AG_OK;
 }
@@ -756,68 +664,17 @@ int ag_ctx_load_weights(ag_ctx* c, const float* const* t, int32_t n) {
     if (!c) return AG_ERR_INVALID;
     if (!t || n != AG_NUM_WEIGHT_TENSORS) return fail(c, AG_ERR_INVALID, "expected %d weight tensors", AG_NUM_WEIGHT_TENSORS);
     for (int i = 0; i < n; ++i) if (!t[i]) return fail(c, AG_ERR_INVALID, "weight tensor %d is null", i);
-    using WL = WeightLayout;
-    std::vector<float> blob((size_t)WL::TOTAL, 0.f);
-    float* b = blob.data();
-    // particle encoder 0..5, relation encoder 6..11
-    pack_first(b + WL::N_L1, t[0], IN_DIM, t[1], NODE_L1_CHUNKS);
-    pack_layer(b + WL::N_L2, t[2], NF, 0, NF, NF, t[3], 5);
-    pack_layer(b + WL::N_L3, t[4], NF, 0, NF, NF, t[5], 5);
-    pack_first(b + WL::E_L1, t[6], c->dims.rel_dim, t[7], EDGE_L1_CHUNKS);
-    pack_layer(b + WL::E_L2, t[8], NF, 0, NF, NF, t[9], 5);
-    pack_layer(b + WL::E_L3, t[10], NF, 0, NF, NF, t[11], 5);
-    // particle propagator W_pp = [Wa | Wb] (150 x 300), bias with Wa
-    pack_layer(b + WL::N_WA, t[12], 2 * NF, 0, NF, NF, t[13], 5);
-    pack_layer(b + WL::P_WB, t[12], 2 * NF, NF, NF, NF, nullptr, 5);
-    // relation propagator W_rp = [W1 | W2 | W3] (150 x 450), bias with W1
-    pack_layer(b + WL::E_W1, t[14], 3 * NF, 0, NF, NF, t[15], 5);
-    pack_layer(b + WL::N_W2, t[14], 3 * NF, NF, NF, NF, nullptr, 5);
-    pack_layer(b + WL::N_W3, t[14], 3 * NF, 2 * NF, NF, NF, nullptr, 5);
-    // predictor
-    pack_layer(b + WL::P_P0, t[16], NF, 0, NF, NF, t[17], 5);
-    pack_layer(b + WL::P_P1, t[18], NF, 0, NF, NF, t[19], 5);
-    pack_layer(b + WL::P_P2, t[20], NF, 0, 3, NF, t[21], 1);
+    // the three images come from one table of the packed blocks (ag_optim.hip), shared with ag_ctx_load_weights_device
+    const bool his4 = c->dims.n_his == 4;   // bf16x3 (opt-in precision mode) and latency-mode images: n_his = 4 models only
+    std::vector<float> blob((size_t)WeightLayout::TOTAL, 0.f);
+    std::vector<uint16_t> img(his4 ? (size_t)B3_PHASES * B3_PHASE_BYTES / 2 : 0, 0);
+    std::vector<float> wl(his4 ? lat_weights_floats() : 0, 0.f);
+    pack_weights_host(c->dims.rel_dim, t, blob.data(), his4 ? img.data() : nullptr, his4 ? wl.data() : nullptr);
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpy(c->d_w, b, blob.size() * 4, hipMemcpyHostToDevice));
-    // bf16x3 image (opt-in precision mode, ag_ctx_set_precision; n_his = 4 models only)
-    if (c->dims.n_his == 4) {
-        std::vector<uint16_t> img((size_t)B3_PHASES * B3_PHASE_BYTES / 2, 0);
-        auto ph = [&](int phase) { return img.data() + (size_t)phase * B3_PHASE_BYTES / 2; };
-        // phase indices = WLB in ag_mlp.hip
-        pack_first_b3(ph(0), t[6], REL_DIM, t[7]);
-        pack_layer_b3(ph(1), t[8], NF, 0, NF, NF, t[9], 5);
-        pack_layer_b3(ph(6), t[10], NF, 0, NF, NF, t[11], 5);
-        pack_layer_b3(ph(11), t[14], 3 * NF, 0, NF, NF, t[15], 5);
-        pack_first_b3(ph(16), t[0], IN_DIM, t[1]);
-        pack_layer_b3(ph(17), t[2], NF, 0, NF, NF, t[3], 5);
-        pack_layer_b3(ph(22), t[4], NF, 0, NF, NF, t[5], 5);
-        pack_layer_b3(ph(27), t[12], 2 * NF, 0, NF, NF, t[13], 5);
-        pack_layer_b3(ph(32), t[14], 3 * NF, NF, NF, NF, nullptr, 5);
-        pack_layer_b3(ph(37), t[14], 3 * NF, 2 * NF, NF, NF, nullptr, 5);
-        pack_layer_b3(ph(42), t[12], 2 * NF, NF, NF, NF, nullptr, 5);
-        pack_layer_b3(ph(47), t[16], NF, 0, NF, NF, t[17], 5);
-        pack_layer_b3(ph(52), t[18], NF, 0, NF, NF, t[19], 5);
-        pack_layer_b3(ph(57), t[20], NF, 0, 3, NF, t[21], 1);
+    HIPCHK(c, hipMemcpy(c->d_w, blob.data(), blob.size() * 4, hipMemcpyHostToDevice));
+    if (his4) {
         if (!c->d_wb3) HIPCHK(c, dev_alloc(c, reinterpret_cast<void**>(&c->d_wb3), img.size() * 2));
         HIPCHK(c, hipMemcpy(c->d_wb3, img.data(), img.size() * 2, hipMemcpyHostToDevice));
-    }
-    if (c->dims.n_his == 4) {   // latency-mode image
-        std::vector<float> wl(lat_weights_floats(), 0.f);
-        float* L = wl.data();
-        pack_first_lat(L + lat_weights_offset(0), t[6], REL_DIM, t[7], 2);
-        pack_layer_lat(L + lat_weights_offset(1), t[8], NF, 0, NF, NF, t[9], false);
-        pack_layer_lat(L + lat_weights_offset(2), t[10], NF, 0, NF, NF, t[11], false);
-        pack_layer_lat(L + lat_weights_offset(3), t[14], 3 * NF, 0, NF, NF, t[15], false);        // W1 + b_rp
-        pack_layer_lat(L + lat_weights_offset(4), t[12], 2 * NF, NF, NF, NF, nullptr, false);     // Wb
-        pack_layer_lat(L + lat_weights_offset(5), t[14], 3 * NF, NF, NF, NF, nullptr, false);     // W2
-        pack_layer_lat(L + lat_weights_offset(6), t[14], 3 * NF, 2 * NF, NF, NF, nullptr, false); // W3
-        pack_layer_lat(L + lat_weights_offset(7), t[16], NF, 0, NF, NF, t[17], false);            // predictor 0
-        pack_layer_lat(L + lat_weights_offset(8), t[18], NF, 0, NF, NF, t[19], false);            // predictor 1
-        pack_layer_lat(L + lat_weights_offset(9), t[20], NF, 0, 3, NF, t[21], true);              // predictor 2 (3 outputs)
-        pack_first_lat(L + lat_weights_offset(10), t[0], IN_DIM, t[1], 1);                         // particle encoder 0 (r06)
-        pack_layer_lat(L + lat_weights_offset(11), t[2], NF, 0, NF, NF, t[3], false);             // particle encoder 2
-        pack_layer_lat(L + lat_weights_offset(12), t[4], NF, 0, NF, NF, t[5], false);             // particle encoder 4
-        pack_layer_lat(L + lat_weights_offset(13), t[12], 2 * NF, 0, NF, NF, t[13], false);       // Wa + b_pp
         if (!c->d_wlat) HIPCHK(c, dev_alloc(c, reinterpret_cast<void**>(&c->d_wlat), wl.size() * 4));
         HIPCHK(c, hipMemcpy(c->d_wlat, wl.data(), wl.size() * 4, hipMemcpyHostToDevice));
     }
@@ -923,20 +780,9 @@ int ag_forward(ag_ctx* c, void* stream, const float* d_state, const float* d_att
     if (sl->slab.used > sl->slab.cap) return fail(c, AG_ERR_INVALID, "internal: workspace carve overflow");
     HIPCHK(c, hipMemsetAsync(sl->d_words, 0, 4, st));
     HIPCHK(c, launch_edge_guard(d_n_edges, B, edge_cap, n_eff, sl->d_words, st));
-    for (int b0 = 0; b0 < B; b0 += Bc) {
-        const int nb = std::min(Bc, B - b0);
-        GraphBufs g = w.g;
-        g.B = nb; g.n_p = n_p; g.n_his = c->dims.n_his;
-        g.wb3 = c->precision == 1 ? c->d_wb3 : nullptr;
-        g.group = const_cast<float*>(d_group) + (size_t)b0 * N * n_inst;
-        g.recv = d_recv + (size_t)b0 * edge_cap; g.send = d_send + (size_t)b0 * edge_cap;
-        g.row_ptr = d_row_ptr + (size_t)b0 * (N + 1); g.n_edges = n_eff + b0; g.n_guard = n_eff + b0;
-        { Scoped p(c, FAM_PREP);
-          HIPCHK(c, launch_prep(d_state + (size_t)b0 * c->dims.n_his * N * 3, d_attrs + (size_t)b0 * N * 2,
-                                d_action + (size_t)b0 * N * 3, d_phys + (size_t)b0 * N, g, st)); }
-        rc = run_model(c, g, d_pred_pos + (size_t)b0 * n_p * 3, d_pred_motion + (size_t)b0 * n_p * 3, st);
-        if (rc) return rc;
-    }
+    rc = enqueue_forward(c, w, Bc, d_state, d_attrs, d_action, d_phys, d_group, n_inst, d_recv, d_send, d_row_ptr, n_eff, edge_cap,
+                         B, N, n_p, d_pred_pos, d_pred_motion, st);
+    if (rc) return rc;
     int seen = 0;
     HIPCHK(c, hipMemcpyAsync(&seen, sl->d_words, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
@@ -1024,6 +870,173 @@ int ag_backward_inputs(ag_ctx* c, void* stream, const float* d_state, const floa
         if (d_grad_w[2 * l + 1]) HIPCHK(c, hipMemcpyAsync(d_grad_w[2 * l + 1], acc[2 * l + 1], (size_t)rows * 4, hipMemcpyDeviceToDevice, st));
     }
     HIPCHK(c, hipStreamSynchronize(st));
+    return AG_OK;
+}
+
+// the three weight images from 22 plain device tensors, by kernels on `st`; no host copy, no wait (first call: allocations)
+static int load_weights_device(ag_ctx* c, hipStream_t st, const float* const* d_w) {
+    const bool his4 = c->dims.n_his == 4;
+    if (his4 && !c->d_wb3) {
+        HIPCHK(c, dev_alloc(c, reinterpret_cast<void**>(&c->d_wb3), (size_t)B3_PHASES * B3_PHASE_BYTES));
+        HIPCHK(c, hipMemset(c->d_wb3, 0, (size_t)B3_PHASES * B3_PHASE_BYTES));
+    }
+    if (his4 && !c->d_wlat) {
+        HIPCHK(c, dev_alloc(c, reinterpret_cast<void**>(&c->d_wlat), lat_weights_floats() * 4));
+        HIPCHK(c, hipMemset(c->d_wlat, 0, lat_weights_floats() * 4));
+    }
+    HIPCHK(c, launch_pack_weights(c->dims.rel_dim, d_w, c->d_w, his4 ? reinterpret_cast<uint16_t*>(c->d_wb3) : nullptr,
+                                  his4 ? c->d_wlat : nullptr, st));
+    c->have_w = true;
+    ++c->weights_version;
+    return enqueue_self_rows(c, st);
+}
+
+int ag_ctx_load_weights_device(ag_ctx* c, void* stream, const float* const* d_w) {
+    if (!c) return AG_ERR_INVALID;
+    if (!d_w) return fail(c, AG_ERR_INVALID, "ag_ctx_load_weights_device: null pointer");
+    for (int k = 0; k < 22; ++k)
+        if (!d_w[k]) return fail(c, AG_ERR_INVALID, "ag_ctx_load_weights_device: weight tensor %d is null", k);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    CallSlot* sl = nullptr;
+    int rc = slot_acquire(c, st, false, &sl);
+    if (rc) return rc;
+    SlotGuard slot_guard(sl, st, false);
+    return load_weights_device(c, st, d_w);
+}
+
+int ag_adam_step(ag_ctx* c, void* stream, float* const* d_w, const float* const* d_grad, float* const* d_exp_avg,
+                 float* const* d_exp_avg_sq, int32_t step, double lr, double beta1, double beta2, double eps, double weight_decay,
+                 int32_t* d_status) {
+    if (!c) return AG_ERR_INVALID;
+    if (!d_w || !d_grad || !d_exp_avg || !d_exp_avg_sq || !d_status) return fail(c, AG_ERR_INVALID, "ag_adam_step: null pointer");
+    for (int k = 0; k < 22; ++k)
+        if (!d_w[k] || !d_grad[k] || !d_exp_avg[k] || !d_exp_avg_sq[k]) return fail(c, AG_ERR_INVALID, "ag_adam_step: null tensor %d", k);
+    if (step < 1 || !(lr >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !(weight_decay >= 0.0))
+        return fail(c, AG_ERR_INVALID, "ag_adam_step: step %d, lr %g, betas (%g, %g), eps %g, weight_decay %g", step, lr, beta1, beta2, eps,
+                    weight_decay);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    CallSlot* sl = nullptr;
+    int rc = slot_acquire(c, st, false, &sl);
+    if (rc) return rc;
+    SlotGuard slot_guard(sl, st, false);
+    AdamArgs a{};
+    weight_tensor_sizes(c->dims.rel_dim, a.n);
+    for (int k = 0; k < 22; ++k) { a.w[k] = d_w[k]; a.g[k] = d_grad[k]; a.m[k] = d_exp_avg[k]; a.v[k] = d_exp_avg_sq[k]; }
+    // torch.optim.Adam forms the bias corrections and the step size as Python floats (doubles); a kernel sees them rounded to fp32
+    const double bc1 = 1.0 - std::pow(beta1, (double)step), bc2 = 1.0 - std::pow(beta2, (double)step);
+    a.wd = (float)weight_decay; a.one_minus_b1 = (float)(1.0 - beta1); a.b2 = (float)beta2; a.one_minus_b2 = (float)(1.0 - beta2);
+    a.bc2_sqrt = (float)std::sqrt(bc2); a.eps = (float)eps; a.neg_step_size = (float)(-(lr / bc1));
+    a.status = d_status;
+    HIPCHK(c, launch_adam(a, st));
+    return load_weights_device(c, st, d_w);
+}
+
+int ag_train_step(ag_ctx* c, void* stream, const float* d_state, const float* d_attrs, const float* d_action, const float* d_phys,
+                  const float* d_group, int32_t n_inst, const int32_t* d_recv, const int32_t* d_send, const int32_t* d_row_ptr,
+                  const int32_t* d_n_edges, int32_t edge_cap, int32_t B, int32_t N, int32_t n_p, const float* const* d_w,
+                  int32_t n_future, const float* d_state_future, const float* d_eef_future, const float* d_action_future,
+                  int32_t store_rest_state, int32_t edge_rows, int32_t want_grad, float* const* d_grad_w, float* d_loss,
+                  float* d_pred, int32_t* d_status) {
+    if (!c) return AG_ERR_INVALID;
+    if (!c->have_w) return fail(c, AG_ERR_NO_WEIGHTS, "ag_train_step before ag_ctx_load_weights / ag_ctx_load_weights_device");
+    if (!d_state || !d_attrs || !d_action || !d_phys || !d_group || !d_recv || !d_send || !d_row_ptr || !d_n_edges || !d_state_future ||
+        !d_loss || !d_status)
+        return fail(c, AG_ERR_INVALID, "ag_train_step: null pointer");
+    if (B < 1 || N < 1 || n_p < 1 || n_p > N || n_inst < 1 || edge_cap < 1 || edge_rows < 1 || n_future < 1)
+        return fail(c, AG_ERR_INVALID, "ag_train_step: bad sizes B=%d N=%d n_p=%d n_inst=%d edge_cap=%d edge_rows=%d n_future=%d", B, N, n_p,
+                    n_inst, edge_cap, edge_rows, n_future);
+    if (n_future > 1 && (!d_eef_future || !d_action_future)) return fail(c, AG_ERR_INVALID, "ag_train_step: n_future > 1 needs eef_future and action_future");
+    if (want_grad) {
+        if (!d_w || !d_grad_w) return fail(c, AG_ERR_INVALID, "ag_train_step: want_grad needs d_w and d_grad_w");
+        for (int k = 0; k < 22; ++k)
+            if (!d_w[k] || !d_grad_w[k]) return fail(c, AG_ERR_INVALID, "ag_train_step: null parameter or gradient tensor %d", k);
+        if (c->dims.pstep > 7) return fail(c, AG_ERR_UNSUPPORTED, "ag_train_step: pstep %d not served by the backward", c->dims.pstep);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    c->prof_stream = st;
+    const int n_his = c->dims.n_his, rest = store_rest_state ? 1 : 0;
+    const int cap = std::min(edge_cap, edge_rows);            // a graph beyond it is presented empty and reported in d_status[0]
+    // forward workspace and launch chunk exactly as ag_forward's: the same kernels are chosen, the predictions are its bits
+    const int c_cap = (int)round_up(edge_cap, 256);
+    const int Bc = clamp_chunk_for_offsets(auto_chunk(c, B, N), N, c_cap);
+    // backward: edge rows per graph = the caller's bound, launch chunk as ag_backward's
+    TrainArgs t{};
+    t.attrs = d_attrs; t.phys = d_phys; t.group = d_group; t.n_inst = n_inst;
+    t.recv = d_recv; t.send = d_send; t.row_ptr = d_row_ptr; t.edge_cap = edge_cap;
+    t.B = B; t.N = N; t.n_p = n_p; t.n_his = n_his; t.pstep = c->dims.pstep; t.clamp = c->dims.motion_clamp;
+    t.Ep = cap; t.want_w = true;
+    size_t wf = 0, wi = 0;
+    int Bb = 1;
+    if (want_grad) {
+        const size_t per_cand = train_work_floats(1, N, t.Ep, n_his, t.pstep) * 4 + train_work_ints(1, N, t.Ep) * 4;
+        Bb = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, (size_t(4) << 30) / per_cand));
+        if (c->chunk > 0) Bb = std::min(Bb, (int)c->chunk);
+        else if (c->opt.chunk > 0) Bb = std::min(Bb, c->opt.chunk);
+        wf = train_work_floats(Bb, N, t.Ep, n_his, t.pstep); wi = train_work_ints(Bb, N, t.Ep);
+    }
+    const size_t n_state = (size_t)B * n_his * N * 3, n_act = (size_t)B * N * 3, n_pred = (size_t)B * n_p * 3;
+    size_t bytes = work_bytes(Bc, N, n_inst, edge_cap, c_cap, 1, false, false, false, n_p, 0) + (size_t)B * 4;
+    bytes += ((size_t)(n_future - 1) * (n_state + n_act) + (size_t)(n_future + 2) * n_pred + 2 * n_state) * 4 + train_glue_doubles() * 8;
+    bytes += (wf + (want_grad ? train_slab_floats() : 0) + wi) * 4 + 32 * 256;
+    CallSlot* sl = nullptr;
+    int rc = slot_acquire(c, st, false, &sl);
+    if (rc) return rc;
+    SlotGuard slot_guard(sl, st, false);
+    rc = ensure_slab(c, *sl, bytes);
+    if (rc) return rc;
+    Work w{};
+    rc = carve_work(c, sl->slab, w, Bc, N, n_inst, edge_cap, c_cap, 1, false, false, false, n_p, 0);
+    if (rc) return rc;
+    int* n_eff = sl->slab.take<int>((size_t)B);
+    float* S = sl->slab.take<float>((size_t)(n_future - 1) * n_state);     // model inputs of steps 1.. (step 0: the caller's)
+    float* A = sl->slab.take<float>((size_t)(n_future - 1) * n_act);
+    float* P = d_pred ? d_pred : sl->slab.take<float>((size_t)n_future * n_pred);
+    float* motion = sl->slab.take<float>(n_pred);
+    double* part = sl->slab.take<double>(train_glue_doubles());
+    float* dpos = nullptr; float* D[2] = {nullptr, nullptr}; float* wsf = nullptr; float* slab = nullptr; int* wsi = nullptr;
+    if (want_grad) {
+        dpos = sl->slab.take<float>(n_pred);
+        if (n_future > 1) { D[0] = sl->slab.take<float>(n_state); D[1] = sl->slab.take<float>(n_state); }
+        wsf = sl->slab.take<float>(wf); slab = sl->slab.take<float>(train_slab_floats()); wsi = sl->slab.take<int>(wi);
+    }
+    if (sl->slab.used > sl->slab.cap) return fail(c, AG_ERR_INVALID, "internal: workspace carve overflow");
+    HIPCHK(c, launch_edge_guard(d_n_edges, B, cap, n_eff, d_status, st));
+    auto state_of = [&](int fi) { return fi == 0 ? d_state : S + (size_t)(fi - 1) * n_state; };
+    auto action_of = [&](int fi) { return fi == 0 ? d_action : A + (size_t)(fi - 1) * n_act; };
+    // ---- train.py:94-119: n_future chained forwards, MSE of each prediction, the next model input from it
+    for (int fi = 0; fi < n_future; ++fi) {
+        float* pred = P + (size_t)fi * n_pred;
+        rc = enqueue_forward(c, w, Bc, state_of(fi), d_attrs, action_of(fi), d_phys, d_group, n_inst, d_recv, d_send, d_row_ptr, n_eff,
+                             edge_cap, B, N, n_p, pred, motion, st);
+        if (rc) return rc;
+        HIPCHK(c, launch_step_loss(pred, d_state_future, B, n_p, n_future, fi, part, d_loss, st));
+        if (fi + 1 < n_future)
+            HIPCHK(c, launch_next_state(state_of(fi), pred, d_eef_future, d_action_future, B, N, n_p, n_his, n_future, fi, rest,
+                                        S + (size_t)fi * n_state, A + (size_t)fi * n_act, st));
+    }
+    if (!want_grad) return AG_OK;
+    // ---- train.py:122 loss_sum.backward(): last step first; the weight gradients accumulate in the caller's tensors in that order
+    int n22[22];
+    weight_tensor_sizes(c->dims.rel_dim, n22);
+    for (int k = 0; k < 22; ++k) {
+        HIPCHK(c, hipMemsetAsync(d_grad_w[k], 0, (size_t)n22[k] * 4, st));
+        t.w[k] = d_w[k]; t.g[k] = d_grad_w[k];
+    }
+    t.n_edges = n_eff; t.dpos = dpos;
+    for (int fi = n_future - 1; fi >= 0; --fi) {
+        const float* dnext = fi + 1 < n_future ? D[1] : nullptr;     // total dLoss/dstate of step fi + 1
+        HIPCHK(c, launch_pred_grad(P + (size_t)fi * n_pred, d_state_future, dnext, B, N, n_p, n_his, n_future, fi, dpos, st));
+        t.state = state_of(fi); t.action = action_of(fi);
+        t.dstate = fi > 0 ? D[0] : nullptr;                          // step 0's input is data
+        for (int b0 = 0; b0 < B; b0 += Bb) HIPCHK(c, train_backward_chunk(t, b0, std::min(Bb, B - b0), wsf, wsi, slab, st));
+        if (fi > 0) {
+            if (dnext) HIPCHK(c, launch_dstate_carry(D[0], dnext, B, N, n_his, rest, st));
+            std::swap(D[0], D[1]);
+        }
+    }
     return AG_OK;
 }
 

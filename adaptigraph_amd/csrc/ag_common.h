@@ -355,4 +355,27 @@ size_t train_work_ints(int Bc, int N, int Ep);
 // candidates [b0, b0+nb) of t; wsf / wsi / slab: train_work_floats(nb,...) floats, train_work_ints(nb,...) ints, train_slab_floats()
 hipError_t train_backward_chunk(const TrainArgs& t, int b0, int nb, float* wsf, int* wsi, float* slab, hipStream_t st);
 
+// ---- device-resident training step (ag_optim.hip).  The weight images of the forward chains (fp32 MFMA blob of WeightLayout::TOTAL
+// floats; bf16x3 image of B3_PHASES phases and latency image, n_his = 4 models only, else null) from the 22 plain tensors in
+// ag_ctx_load_weights order: on the host, and by kernels on `st` from device tensors - the same table and element functions.
+void pack_weights_host(int rel_dim, const float* const* t, float* blob, uint16_t* b3, float* lat);
+hipError_t launch_pack_weights(int rel_dim, const float* const* d_t, float* d_blob, uint16_t* d_b3, float* d_lat, hipStream_t st);
+void weight_tensor_sizes(int rel_dim, int* n22);   // floats of each of the 22 tensors
+// Adam over the 22 tensors in one launch; scalars pre-rounded to fp32 by the caller from double (ag_adam_step)
+struct AdamArgs {
+    float* w[22]; const float* g[22]; float* m[22]; float* v[22]; int n[22];
+    float wd, one_minus_b1, b2, one_minus_b2, bc2_sqrt, eps, neg_step_size;
+    int* status;                // [0] != 0: skip; else [1] += 1
+};
+hipError_t launch_adam(const AdamArgs& a, hipStream_t st);
+// glue of the chained step (train.py:86-124); fut = state_future (B,n_future,n_p,3), part = train_glue_doubles() doubles
+size_t train_glue_doubles();
+hipError_t launch_step_loss(const float* pred, const float* fut, int B, int n_p, int n_future, int fi, double* part, float* loss,
+                            hipStream_t st);
+hipError_t launch_next_state(const float* state, const float* pred, const float* eef, const float* act_f, int B, int N, int n_p,
+                             int n_his, int n_future, int fi, int rest, float* state_next, float* action_next, hipStream_t st);
+hipError_t launch_pred_grad(const float* pred, const float* fut, const float* dnext, int B, int N, int n_p, int n_his, int n_future,
+                            int fi, float* dpos, hipStream_t st);
+hipError_t launch_dstate_carry(float* d, const float* dnext, int B, int N, int n_his, int rest, hipStream_t st);
+
 }  // namespace ag

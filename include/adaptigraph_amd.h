@@ -30,6 +30,8 @@
  *       ag_ctx_load_weights, ag_ctx_set_precision     always (host repack + copies)
  *       ag_forward, ag_rollout                        once, at the end: they return the overflow verdict (AG_ERR_MAX_NR)
  *       ag_backward, ag_backward_inputs               at the start (edge counts) and at the end
+ *       ag_ctx_load_weights_device, ag_adam_step, ag_train_step   NEVER: they only enqueue on the caller's stream; an overflowed
+ *           graph is reported in device memory (d_status), which the caller reads when it chooses to
  *       ag_rollout_work                               for its plan (and a base rollout, if none is kept): it returns host numbers
  *       ag_ctx_rollout_counts (after a device-planned call without prefix sharing), ag_ctx_share_counts   wait for the device
  *       ag_rollout_async, ag_rollout_actions          only when the contact-free prefix is in play (option "share_prefix";
@@ -278,6 +280,46 @@ int ag_backward_inputs(ag_ctx* ctx, void* stream, const float* d_state, const fl
                        const int32_t* d_row_ptr, const int32_t* d_n_edges, int32_t edge_cap, int32_t B, int32_t N, int32_t n_p,
                        const float* const* d_w, const float* d_grad_pos, const float* d_grad_motion, float* d_grad_state,
                        float* const* d_grad_w, float* d_grad_phys, float* d_grad_action);
+
+/* ---- Device-resident training step (reference src/dynamics/train/train.py:86-124).  None of the three waits for the GPU. ---- */
+
+/* ag_ctx_load_weights from 22 plain fp32 DEVICE tensors (same order and layout): every weight image the context keeps - the
+ * fp32 MFMA image and, for n_his = 4 models, the bf16x3 and the latency-mode images - is built by kernels on `stream`,
+ * bit-identical to the host-packed ones, and the self-loop constant rows are re-derived behind them.  No host copy, no wait
+ * (the first call allocates the images it finds missing).  The tensors are read when the kernels run.  The images belong to
+ * the context, not to a call slot, and are rewritten in place: while this call (or ag_adam_step, which ends with it) is in flight
+ * no other call on this context may be in flight on another stream. */
+int ag_ctx_load_weights_device(ag_ctx* ctx, void* stream, const float* const* d_w);
+
+/* One torch.optim.Adam step (single-tensor formula; no amsgrad, no maximize) over the 22 parameter tensors in one launch:
+ *   g += weight_decay * w;  m += (g - m) * (1 - beta1);  v = v * beta2 + (1 - beta2) * g * g;
+ *   w -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps),   bc_i = 1 - beta_i^step formed here in double (step >= 1).
+ * d_status (int32 x 4, device): when d_status[0] != 0 (ag_train_step found an overflowed graph) nothing is touched; otherwise
+ * d_status[1] += 1, the count of applied steps.  Ends by enqueuing ag_ctx_load_weights_device(d_w). */
+int ag_adam_step(ag_ctx* ctx, void* stream, float* const* d_w, const float* const* d_grad, float* const* d_exp_avg,
+                 float* const* d_exp_avg_sq, int32_t step, double lr, double beta1, double beta2, double eps, double weight_decay,
+                 int32_t* d_status);
+
+/* The training loop body (train.py:94-122) as one enqueue-only call: n_future chained forwards (each the kernels and bits of
+ * ag_forward on the context's loaded weights), per step the MSE of the prediction against d_state_future[:, fi] (summed in
+ * fp64 in a fixed order, rounded once) and the next model input (last frame = d_eef_future[:, fi] with the object rows replaced by
+ * the prediction, history shifted by one, frame 0 kept when store_rest_state; action = d_action_future[:, fi]); then, when
+ * want_grad, the backward through the chain, last step first.
+ *   Inputs: those of ag_backward (d_w[22] = the plain parameters the gradient is taken toward; they must hold the values the
+ *   context's weights were loaded from), d_state_future (B,n_future,n_p,3), d_eef_future, d_action_future (B,n_future-1,N,3; may
+ *   be NULL when n_future == 1), edge_rows = the caller's bound on the largest d_n_edges[b] (sizes the backward workspace).
+ *   Outputs: d_grad_w[22] (overwritten; ignored when want_grad == 0), d_loss (n_future + 1 floats: per-step MSE, then their
+ *   sum), d_pred (n_future,B,n_p,3) or NULL, d_status (int32 x 4): [0] receives (atomic max, never cleared here) the edge count of
+ *   a graph with more than min(edge_cap, edge_rows) edges - such a graph is walked as an empty one, nothing reads unwritten
+ *   indices, and ag_adam_step skips its update; [1] is ag_adam_step's; [2], [3] reserved.
+ * Returns AG_OK for an overflowed graph: the caller maps d_status[0] != 0 to AG_ERR_MAX_NR when it reads it.  No float atomics:
+ * two calls on the same inputs give the same bits. */
+int ag_train_step(ag_ctx* ctx, void* stream, const float* d_state, const float* d_attrs, const float* d_action, const float* d_phys,
+                  const float* d_group, int32_t n_inst, const int32_t* d_recv, const int32_t* d_send, const int32_t* d_row_ptr,
+                  const int32_t* d_n_edges, int32_t edge_cap, int32_t B, int32_t N, int32_t n_p, const float* const* d_w,
+                  int32_t n_future, const float* d_state_future, const float* d_eef_future, const float* d_action_future,
+                  int32_t store_rest_state, int32_t edge_rows, int32_t want_grad, float* const* d_grad_w, float* d_loss,
+                  float* d_pred, int32_t* d_status);
 
 /* Replaces the device side of dynamics() / dynamics_masked() (src/planning/forward_dynamics.py:12-205, 209-399):
  * the whole look-ahead x action-repeat loop, graph rebuilt every step, no host sync inside.

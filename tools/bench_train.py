@@ -3,11 +3,15 @@
 with config/dynamics/rope.yaml: batch 128, 100 object particles + 1 tool, topk 10, max_nR 1000, n_future 3), i.e. three chained
 forwards, loss_sum.backward() and one Adam step (lr 1e-3).
 
-Two variants on the same GPU in the same process, alternated round by round:
-  engine   adaptigraph_amd.DynamicsPredictor under autograd (ag_forward + ag_backward)
+Three variants on the same GPU in the same process, alternated round by round:
+  engine   adaptigraph_amd.DynamicsPredictor under autograd (ag_forward + ag_backward) + torch.optim.Adam
+  fused    adaptigraph_amd.TrainStep.step with max_edges given (ag_train_step + ag_adam_step: enqueue only)
   torch    tests/train_restate.py in fp32 under torch autograd (index gathers + index_add; the reference itself stays on the host)
 and the model FLOPs per iteration from the shapes (forward as the reference computes it: the relation propagator on the
-concatenated 450-wide input; backward = 2x forward, plus one recomputed forward for the engine).
+concatenated 450-wide input; backward = 2x forward, plus one recomputed forward for the engine and the fused step).  Host
+waits per iteration are DECLARED, not observed: the tool counts its calls of the C-ABI entries and multiplies by what the blocking
+table of include/adaptigraph_amd.h says each one waits (ag_forward 1, ag_backward 2, ag_ctx_load_weights 1, the fused entries 0).
+That the fused step really does not wait is what tests/test_gpu_train_step.py::test_step_returns_while_the_stream_is_busy shows.
 
   python tools/bench_train.py [--rounds 5] [--iters 5] [--warmup 3] [--out FILE]
   python tools/bench_train.py --only engine --rounds 1 --iters 3    (e.g. under rocprofv3 --kernel-trace --stats)
@@ -80,6 +84,38 @@ def engine_variant(dev, data, W):
     return it
 
 
+def fused_variant(dev, data, W):
+    model = ag.DynamicsPredictor(CFG, {"material_index": {"rope": 0}, "rope": {"physics_params": [{"name": "s", "use": True}]}},
+                                 {"n_his": 4, "materials": ["rope"]}, dev)
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in W.items()})
+    ts = ag.TrainStep(model.to(dev), lr=0.001, n_future=3)
+    batch = {k: data[k] for k in ("state", "attrs", "action", "p_instance", "phys_physics_param", "edges", "state_future",
+                                  "eef_future", "action_future")}
+    max_edges = int(data["ne"].max())
+
+    def it():
+        return ts.step(batch, max_edges=max_edges)
+    return it
+
+
+WAITS = {"ag_forward": 1, "ag_backward": 2, "ag_ctx_load_weights": 1, "ag_train_step": 0, "ag_adam_step": 0,
+         "ag_ctx_load_weights_device": 0}
+CALLS = {k: 0 for k in WAITS}
+
+
+def count_calls():
+    """Wrap the C-ABI entries of the loaded library with call counters (the library object is shared by every Engine)."""
+    from adaptigraph_amd import _lib
+    lib = _lib.load()
+    for name in WAITS:
+        fn = getattr(lib, name)
+
+        def wrapped(*a, _fn=fn, _name=name):
+            CALLS[_name] += 1
+            return _fn(*a)
+        setattr(lib, name, wrapped)
+
+
 def torch_variant(dev, data, W):
     Wt = {k: torch.from_numpy(v).to(dev).requires_grad_(True) for k, v in W.items()}
     opt = torch.optim.Adam(list(Wt.values()), lr=0.001)
@@ -118,46 +154,57 @@ def main():
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=128)
-    ap.add_argument("--only", choices=["engine", "torch"], default=None)
+    ap.add_argument("--only", choices=["engine", "fused", "torch"], default=None)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     data = make_batch(dev, B=a.batch)
     W = TR.make_weights(0)
-    variants = {"engine": engine_variant(dev, data, W), "torch": torch_variant(dev, data, W)}
-    if a.only:
-        variants = {a.only: variants[a.only]}
+    count_calls()
+    makers = {"engine": engine_variant, "fused": fused_variant, "torch": torch_variant}
+    variants = {k: mk(dev, data, W) for k, mk in makers.items() if a.only in (None, k)}
     for fn in variants.values():
         for _ in range(a.warmup):
             fn()
     torch.cuda.synchronize()
     times = {k: [] for k in variants}
     losses = {}
+    waits = {k: 0 for k in variants}
     for _ in range(a.rounds):
         for k, fn in variants.items():
             torch.cuda.synchronize()
+            before = dict(CALLS)
             t0 = time.perf_counter()
             for _ in range(a.iters):
                 loss = fn()
             torch.cuda.synchronize()
             times[k].append((time.perf_counter() - t0) * 1e3 / a.iters)
+            waits[k] += sum((CALLS[n] - before[n]) * WAITS[n] for n in WAITS)
             losses[k] = float(loss)
     B, N = data["attrs"].shape[:2]
     E = float(data["ne"].mean())
     fwd = model_flops(B, N, data["n_p"], E)
-    flops = {"engine": 3 * (4 * fwd), "torch": 3 * (3 * fwd)}   # n_future forwards; backward 2x; engine recomputes once more
+    flops = {"engine": 3 * (4 * fwd), "fused": 3 * (4 * fwd), "torch": 3 * (3 * fwd)}   # n_future forwards; backward 2x; the engine paths recompute once more
     res = {"tool": "bench_train", "config": dict(B=B, N=N, n_p=data["n_p"], topk=10, max_nR=1000, edges_mean=E,
                                                  edges_max=int(data["ne"].max()), n_future=3, pstep=3, optimizer="Adam lr 1e-3"),
            "device": torch.cuda.get_device_name(dev), "rounds": a.rounds, "iters_per_round": a.iters,
            "model_gflop_per_forward": fwd / 1e9,
            "note": "FLOPs from shapes: forward as the reference computes it (relation propagator on the 450-wide concatenation); "
-                   "backward 2x forward; the engine also recomputes one forward inside its backward"}
+                   "backward 2x forward; the engine and the fused step also recompute one forward inside the backward; host_waits_per_iter_declared = calls x the header's blocking table, not a measurement"}
     for k in variants:
         ms = float(np.median(times[k]))
         res[k] = {"ms_per_iter_median": ms, "ms_per_iter_rounds": [round(x, 3) for x in times[k]], "last_loss": losses[k],
                   "gflop_per_iter": flops[k] / 1e9, "achieved_tflops": flops[k] / (ms * 1e-3) / 1e12}
+        if k != "torch":
+            res[k]["host_waits_per_iter_declared"] = waits[k] / (a.rounds * a.iters)
     if "engine" in res and "torch" in res:
         res["torch_over_engine"] = res["torch"]["ms_per_iter_median"] / res["engine"]["ms_per_iter_median"]
+    if "fused" in res and "torch" in res:
+        res["torch_over_fused"] = res["torch"]["ms_per_iter_median"] / res["fused"]["ms_per_iter_median"]
+    if "fused" in res and "engine" in res:
+        res["engine_over_fused"] = res["engine"]["ms_per_iter_median"] / res["fused"]["ms_per_iter_median"]
+        r = res["engine"]["ms_per_iter_rounds"]
+        res["engine_round_spread_ms"] = max(r) - min(r)
     line = json.dumps(res)
     print(line)
     if a.out:

@@ -41,7 +41,8 @@ from .model import DynamicsPredictor
 from .plan_utils import decode_action
 from .losses import chamfer, chamfer_diff, mean_chamfer, box_loss, rope_penalty, cloth_penalty, granular_penalty
 from .costs import running_cost
-from .physics_param_optimizer import dynamics_error, dynamics_error_sweep, dynamics_error_grad, optimize_grad
+from .physics_param_optimizer import (dynamics_error, dynamics_error_sweep, dynamics_error_grad, optimize_grad, PhysParamFit,
+                                      optimize_grad_device, dynamics_error_grad_device)
 from .mppi import angle_normalize, clip_actions, sample_action_seq, optimize_action_mppi, mpc_iteration
 from .planner import Planner
 from .rollout import rollout_eval, rollout_eval_step, surface_bounds
@@ -51,4 +52,5 @@ __all__ = ["hw_queues", "Engine", "default_engine", "dynamics", "dynamics_masked
            "construct_edges_index", "construct_edges_with_backoff", "pad_torch", "truncate_graph", "DynamicsPredictor", "decode_action", "chamfer",
            "mean_chamfer", "box_loss", "rope_penalty", "cloth_penalty", "granular_penalty", "running_cost", "dynamics_error", "dynamics_error_sweep", "angle_normalize",
            "clip_actions", "sample_action_seq", "optimize_action_mppi", "mpc_iteration", "Planner", "rollout_eval", "rollout_eval_step", "surface_bounds",
-           "dynamics_masked_diff", "chamfer_diff", "dynamics_error_grad", "optimize_grad", "TrainStep"]
+           "dynamics_masked_diff", "chamfer_diff", "dynamics_error_grad", "optimize_grad", "TrainStep", "PhysParamFit",
+           "optimize_grad_device", "dynamics_error_grad_device"]

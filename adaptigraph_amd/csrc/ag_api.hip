@@ -1040,6 +1040,178 @@ int ag_train_step(ag_ctx* c, void* stream, const float* d_state, const float* d_
     return AG_OK;
 }
 
+int ag_ppm_grad_step(ag_ctx* c, void* stream, const ag_rollout_params* p, const float* d_state0, const uint8_t* d_obj_mask,
+                     const float* d_eef_xz, const float* d_eef_delta, const int32_t* h_repeat, const int32_t* d_repeat,
+                     const float* d_phys, const float* d_obs, const uint8_t* d_obs_mask, int32_t N_t, const float* d_row_weight,
+                     const float* const* d_w, int32_t edge_rows, int32_t want_grad, float* d_state_seqs, float* d_err,
+                     float* d_grad_phys, int32_t* d_status) {
+    if (!c) return AG_ERR_INVALID;
+    if (!c->have_w) return fail(c, AG_ERR_NO_WEIGHTS, "ag_ppm_grad_step before ag_ctx_load_weights / ag_ctx_load_weights_device");
+    if (!p || !d_state0 || !d_obj_mask || !d_eef_xz || !d_eef_delta || !h_repeat || !d_repeat || !d_phys || !d_obs || !d_obs_mask ||
+        !d_state_seqs || !d_err || !d_status)
+        return fail(c, AG_ERR_INVALID, "ag_ppm_grad_step: null pointer");
+    const int B = p->B, N_o = p->N_o, M = p->M, N = N_o + M;
+    if (B < 1 || N_o < 1 || M < 0 || p->H != 1 || p->y_mode != 1 || N_t < 1 || edge_rows < 1 || p->max_nR < 1)
+        return fail(c, AG_ERR_INVALID, "ag_ppm_grad_step: bad sizes B=%d N_o=%d M=%d H=%d y_mode=%d N_t=%d edge_rows=%d max_nR=%d", B, N_o, M,
+                    p->H, p->y_mode, N_t, edge_rows, p->max_nR);
+    if ((size_t)N_o + (size_t)N_t > chamfer_max_points())
+        return fail(c, AG_ERR_UNSUPPORTED, "ag_ppm_grad_step: N_o+N_t=%d exceeds the chamfer LDS tile (%zu points)", N_o + N_t, chamfer_max_points());
+    int rc = check_topk(c, N, p->topk);
+    if (rc) return rc;
+    if (want_grad) {
+        if (!d_w || !d_grad_phys || !d_row_weight) return fail(c, AG_ERR_INVALID, "ag_ppm_grad_step: want_grad needs d_w, d_row_weight and d_grad_phys");
+        for (int k = 0; k < 22; ++k)
+            if (!d_w[k]) return fail(c, AG_ERR_INVALID, "ag_ppm_grad_step: null parameter tensor %d", k);
+        if (c->dims.pstep > 7) return fail(c, AG_ERR_UNSUPPORTED, "ag_ppm_grad_step: pstep %d not served by the backward", c->dims.pstep);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    c->prof_stream = st;
+    const int n_his = c->dims.n_his;
+    // the step count and the live prefix of every step come from the host-resident repeat counts: no read-back
+    int S = 0;
+    for (int b = 0; b < B; ++b) S = std::max(S, (int)h_repeat[b]);
+    std::vector<int> live((size_t)S + 2, 0);                  // live[s] = rows [0, live[s]) hold every row with repeat >= s
+    for (int b = 0; b < B; ++b)
+        for (int s = 1; s <= std::min(S, (int)h_repeat[b]); ++s) live[s] = b + 1;
+    const int cap = std::min(p->max_nR, edge_rows);           // a graph beyond it is presented empty and reported in d_status[0]
+    const int c_cap = (int)round_up(cap, 256);
+    const int Bc = clamp_chunk_for_offsets(auto_chunk(c, B, N), N, c_cap);
+    const int slices = pick_slices(c, B, N), ell = edge_ell_stride(N, p->topk);
+    TrainArgs t{};
+    t.n_inst = 1; t.edge_cap = cap; t.N = N; t.n_p = N_o; t.n_his = n_his; t.pstep = c->dims.pstep; t.clamp = c->dims.motion_clamp;
+    t.Ep = cap; t.want_w = false;
+    size_t wf = 0, wi = 0;
+    int Bb = 1;
+    if (want_grad) {
+        const size_t per_cand = train_work_floats(1, N, t.Ep, n_his, t.pstep) * 4 + train_work_ints(1, N, t.Ep) * 4;
+        Bb = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, (size_t(4) << 30) / per_cand));
+        if (c->chunk > 0) Bb = std::min(Bb, (int)c->chunk);
+        else if (c->opt.chunk > 0) Bb = std::min(Bb, c->opt.chunk);
+        wf = train_work_floats(Bb, N, t.Ep, n_his, t.pstep); wi = train_work_ints(Bb, N, t.Ep);
+    }
+    // workspace: [forward | builder scratch | model inputs | per-step inputs and edge lists | chamfer and backward]
+    const size_t rows = (size_t)B * N, n_state = (size_t)B * n_his * N * 3, n_pred = (size_t)B * N_o * 3;
+    const size_t nS = want_grad ? (size_t)std::max(S, 1) : 2, nE = want_grad ? (size_t)std::max(S, 1) : 1;
+    const size_t e_ints = 2 * (size_t)B * cap + (size_t)B * (N + 1) + 2 * (size_t)B;
+    size_t bytes = work_bytes(Bc, N, 1, cap, c_cap, 1, false, false, false, N_o, 0);
+    bytes += (rows * (size_t)(std::max(1, ell) + 1) + (size_t)B * (slices + 1)) * 4;
+    bytes += rows * 7 * 4 + 2 * rows + 2 * (size_t)B * 4 + 2 * n_pred * 4;
+    bytes += nS * n_state * 4 + nE * e_ints * 4;
+    if (want_grad) bytes += ((size_t)B * (N_o + N_t + 2) + 2 * n_pred + 2 * n_state + rows + wf + wi) * 4;
+    bytes += (32 + 5 * nE) * 256;
+    CallSlot* sl = nullptr;
+    rc = slot_acquire(c, st, false, &sl);
+    if (rc) return rc;
+    SlotGuard slot_guard(sl, st, false);
+    rc = ensure_slab(c, *sl, bytes);
+    if (rc) return rc;
+    Work w{};
+    rc = carve_work(c, sl->slab, w, Bc, N, 1, cap, c_cap, 1, false, false, false, N_o, 0);
+    if (rc) return rc;
+    Slab& sb = sl->slab;
+    EdgeArgs ea{};
+    ea.ell = sb.take<int>(rows * (size_t)std::max(1, ell)); ea.deg = sb.take<int>(rows);
+    ea.slice_tot = sb.take<int>((size_t)B * slices); ea.cta_flag = sb.take<int>(B);
+    PpmBufs pb{};
+    pb.B = B; pb.N_o = N_o; pb.M = M; pb.n_his = n_his;
+    pb.state0 = d_state0; pb.obj_mask = d_obj_mask; pb.eef_xz = d_eef_xz; pb.eef_delta = d_eef_delta; pb.phys = d_phys;
+    pb.repeat = d_repeat; pb.grip = p->gripper_offset; pb.grip_on = p->gripper_enable;
+    pb.attrs = sb.take<float>(rows * 2); pb.action = sb.take<float>(rows * 3); pb.group = sb.take<float>(rows);
+    pb.physN = sb.take<float>(rows); pb.mask = sb.take<uint8_t>(rows); pb.tool = sb.take<uint8_t>(rows);
+    pb.ymean = sb.take<float>(B); pb.cnt = sb.take<int>(B);
+    float* pred = sb.take<float>(n_pred); float* motion = sb.take<float>(n_pred);
+    float* states = sb.take<float>(nS * n_state);
+    std::vector<int*> e_recv(nE), e_send(nE), e_rptr(nE), e_n(nE), e_eff(nE);
+    for (size_t k = 0; k < nE; ++k) {
+        e_recv[k] = sb.take<int>((size_t)B * cap); e_send[k] = sb.take<int>((size_t)B * cap);
+        e_rptr[k] = sb.take<int>((size_t)B * (N + 1)); e_n[k] = sb.take<int>(B); e_eff[k] = sb.take<int>(B);
+    }
+    int* nn = nullptr; float* cntf = nullptr; float* gseq = nullptr; float* dpos = nullptr; float* D[2] = {nullptr, nullptr};
+    float* gphys = nullptr; float* wsf = nullptr; int* wsi = nullptr;
+    if (want_grad) {
+        nn = sb.take<int>((size_t)B * (N_o + N_t)); cntf = sb.take<float>((size_t)B * 2); gseq = sb.take<float>(n_pred);
+        dpos = sb.take<float>(n_pred); D[0] = sb.take<float>(n_state); D[1] = sb.take<float>(n_state);
+        gphys = sb.take<float>(rows); wsf = sb.take<float>(wf); wsi = sb.take<int>(wi);
+    }
+    if (sb.used > sb.cap) return fail(c, AG_ERR_INVALID, "internal: workspace carve overflow");
+    auto state_of = [&](int s) { return states + (want_grad ? (size_t)(s - 1) : (size_t)((s - 1) & 1)) * n_state; };
+    auto eslot = [&](int s) { return want_grad ? (size_t)(s - 1) : (size_t)0; };
+    ea.mask = pb.mask; ea.tool = pb.tool; ea.thr = p->adj_thresh; ea.N = N; ea.topk = p->topk; ea.cta = p->connect_tools_all ? 1 : 0;
+    ea.edge_cap = cap; ea.max_nR = cap; ea.slices = slices; ea.pos_bstride = (long)n_his * N * 3;
+    ea.block_min_rows = c->opt.edge_block_min;
+
+    // ---- forward_dynamics.py:225-372: the masked rollout, every step's model input and edge lists kept for the backward
+    HIPCHK(c, hipMemsetAsync(d_state_seqs, 0, n_pred * 4, st));
+    HIPCHK(c, launch_ppm_mean_y(pb, d_state0, B, st));
+    HIPCHK(c, launch_ppm_init(pb, state_of(1), st));
+    for (int s = 1; s <= S; ++s) {
+        const int L = live[s], Ln = live[s + 1];
+        const size_t k = eslot(s);
+        float* cur = state_of(s);
+        ea.pos = cur + (size_t)(n_his - 1) * N * 3; ea.B = L;
+        ea.recv = e_recv[k]; ea.send = e_send[k]; ea.row_ptr = e_rptr[k]; ea.n_edges = e_n[k];
+        HIPCHK(c, launch_edge_build(ea, st, prof_mark, c));
+        HIPCHK(c, launch_edge_guard(e_n[k], L, cap, e_eff[k], d_status, st));
+        rc = enqueue_forward(c, w, Bc, cur, pb.attrs, pb.action, pb.physN, pb.group, 1, e_recv[k], e_send[k], e_rptr[k], e_eff[k], cap,
+                             L, N, N_o, pred, motion, st);
+        if (rc) return rc;
+        if (Ln > 0) HIPCHK(c, launch_ppm_mean_y(pb, pred, Ln, st));
+        HIPCHK(c, launch_ppm_advance(pb, cur, pred, s, L, Ln, Ln > 0 ? state_of(s + 1) : cur, d_state_seqs, st));
+    }
+    // ---- the masked chamfer to the observed clouds (physics_param_optimizer.py:219-226)
+    { Scoped pr(c, FAM_COST);
+      HIPCHK(c, launch_chamfer(d_state_seqs, d_obs, d_obj_mask, d_obs_mask, B, N_o, N_t, B, d_err, st)); }
+    if (!want_grad) return AG_OK;
+    HIPCHK(c, hipMemsetAsync(d_grad_phys, 0, (size_t)B * N_o * 4, st));
+    { Scoped pr(c, FAM_COST);
+      HIPCHK(c, launch_chamfer_backward(d_state_seqs, d_obs, d_obj_mask, d_obs_mask, B, N_o, N_t, B, d_row_weight, nn, cntf, gseq, st)); }
+    // ---- backward through the chain, last step first; edges are constants
+    // (pb.cnt still holds the valid counts: a row's mask never changes)
+    for (int k = 0; k < 22; ++k) { t.w[k] = d_w[k]; t.g[k] = nullptr; }
+    t.attrs = pb.attrs; t.action = pb.action; t.phys = pb.physN; t.group = pb.group; t.dpos = dpos; t.dphys = gphys;
+    for (int s = S; s >= 1; --s) {
+        const int L = live[s], Ln = live[s + 1];
+        const size_t k = eslot(s);
+        HIPCHK(c, launch_ppm_pred_grad(pb, gseq, Ln > 0 ? D[1] : nullptr, s, L, Ln, dpos, st));
+        t.state = state_of(s); t.recv = e_recv[k]; t.send = e_send[k]; t.row_ptr = e_rptr[k]; t.n_edges = e_eff[k]; t.B = L;
+        t.dstate = s > 1 ? D[0] : nullptr;                      // step 1's input is data
+        // no split-K slab: want_w = false makes every linear_dw return before it touches one (wsf stands in for the pointer; a
+        // caller that turns want_w on must carve train_slab_floats() as ag_train_step does)
+        for (int b0 = 0; b0 < L; b0 += Bb) HIPCHK(c, train_backward_chunk(t, b0, std::min(Bb, L - b0), wsf, wsi, wsf, st));
+        HIPCHK(c, launch_ppm_accum(gphys, L, N, N_o, d_grad_phys, st));
+        if (s > 1) {
+            if (Ln > 0) HIPCHK(c, launch_dstate_carry(D[0], D[1], Ln, N, n_his, 0, st));
+            std::swap(D[0], D[1]);
+        }
+    }
+    return AG_OK;
+}
+
+int ag_ppm_adam_step(ag_ctx* c, void* stream, const float* d_err, const float* d_grad_phys, int32_t n_starts, int32_t n_rows,
+                     int32_t N_o, int32_t start_major, int32_t apply_update, double lr, double bias_correction1,
+                     double bias_correction2, double lo, double hi, float* d_x, double* d_exp_avg, double* d_exp_avg_sq,
+                     int32_t hist_cap, float* d_hist_x, double* d_hist_err, double* d_best, double* d_grad_start, float* d_phys,
+                     int32_t* d_status) {
+    if (!c) return AG_ERR_INVALID;
+    if (!d_err || !d_x || !d_hist_x || !d_hist_err || !d_best || !d_grad_start || !d_status)
+        return fail(c, AG_ERR_INVALID, "ag_ppm_adam_step: null pointer");
+    if (n_starts < 1 || n_rows < 1 || N_o < 1 || hist_cap < 0)
+        return fail(c, AG_ERR_INVALID, "ag_ppm_adam_step: bad sizes n_starts=%d n_rows=%d N_o=%d hist_cap=%d", n_starts, n_rows, N_o, hist_cap);
+    if (apply_update && (!d_grad_phys || !d_exp_avg || !d_exp_avg_sq || !d_phys || !(lr >= 0.0) || !(bias_correction1 > 0.0) ||
+                         !(bias_correction2 > 0.0) || !(lo <= hi)))
+        return fail(c, AG_ERR_INVALID, "ag_ppm_adam_step: update needs gradient, moments and d_phys; lr %g, bias corrections (%g, %g), bounds [%g, %g]",
+                    lr, bias_correction1, bias_correction2, lo, hi);
+    HIPCHK(c, hipSetDevice(c->device));
+    PpmAdamArgs a{};
+    a.err = d_err; a.grad = d_grad_phys; a.K = n_starts; a.n = n_rows; a.N_o = N_o; a.start_major = start_major ? 1 : 0;
+    a.hist_cap = hist_cap; a.apply = apply_update ? 1 : 0; a.x = d_x; a.m = d_exp_avg; a.v = d_exp_avg_sq; a.hist_x = d_hist_x;
+    a.hist_e = d_hist_err; a.best = d_best; a.gk = d_grad_start; a.phys = d_phys; a.lr = lr; a.bc1 = bias_correction1;
+    a.bc2 = bias_correction2; a.lo = lo; a.hi = hi; a.status = d_status;
+    HIPCHK(c, launch_ppm_adam(a, static_cast<hipStream_t>(stream)));
+    return AG_OK;
+}
+
 }  // extern "C"
 
 namespace {

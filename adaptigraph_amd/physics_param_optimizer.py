@@ -2,16 +2,22 @@
 (reference src/planning/physics_param_optimizer.py:178-226) = masked rollout of the past interactions + mean chamfer
 to what really happened.  Same signature; dynamics_masked and mean_chamfer run on the HIP engine.  The host optimisers
 (skopt.gp_minimize / cma) stay in the reference.  r05: dynamics_error_sweep evaluates a population / sweep of
-parameters in one go (independent evaluations dealt to streams, one read-back)."""
+parameters in one go (independent evaluations dealt to streams, one read-back).  optimize_grad fits the parameter by Adam on
+the autograd path; PhysParamFit / optimize_grad_device run the same fit resident on the GPU (ag_ppm_grad_step +
+ag_ppm_adam_step: an iteration only enqueues, one read-back at the end)."""
 from __future__ import annotations
 
 import copy
+import ctypes as C
 
 import numpy as np
 import torch
 
-from .context import side_streams as _sweep_streams
-from .forward_dynamics import dynamics_masked, dynamics_masked_diff
+from . import _lib
+from .context import side_streams as _sweep_streams, ptr, current_stream, _require_gpu
+from .forward_dynamics import dynamics_masked, dynamics_masked_diff, _tool_layout
+from .model import DynamicsPredictor
+from .plan_utils import decode_action
 from .losses import mean_chamfer, chamfer_diff
 
 
@@ -207,3 +213,224 @@ def optimize_grad(ppm_optimizer, actions, state_init_list, state_pred_list, stat
     if return_res:
         return best_x, best_err, init_error, {"params": np.stack(hist_x), "errors": np.stack(hist_e), "best_start": best_k}
     return best_x, best_err, init_error
+
+
+def adam_best_update(x32, errors, grads, m, v, it, lr, best):
+    """One iteration of optimize_grad's loop body as the device kernel states it (ag_ppm_adam_step), on the host in float64:
+    x32 (K,dim) float32 evaluated parameters, their errors (K,) and gradients (K,dim), Adam moments m, v, iteration it (0-based),
+    best = (x, err, k) so far -> (new x32, m, v, best).  Pure host function (tests restate optimize_grad against it)."""
+    errors = np.asarray(errors, np.float64)
+    bx, be, bk = best
+    for k in range(len(errors)):                                                 # ascending k: the first minimum wins
+        if errors[k] < be:
+            bx, be, bk = np.array(x32[k], np.float32, copy=True), errors[k], k
+    m = 0.9 * m + 0.1 * grads
+    v = 0.999 * v + 0.001 * grads * grads
+    step = lr * (m / (1 - 0.9 ** (it + 1))) / (np.sqrt(v / (1 - 0.999 ** (it + 1))) + 1e-8)
+    x = np.clip(np.asarray(x32, np.float32).astype(np.float64) - step, *PARAM_BOUNDS)
+    return x.astype(np.float32), m, v, (bx, be, bk)
+
+
+class _DeviceProblem:
+    """The fit's problem on the device in the form ag_ppm_grad_step takes: K copies of the n interactions, interaction-major
+    (row = i * K + k) with the interactions in descending order of action_repeat, so that every step of the call runs over
+    exactly the rows that still have a forward left.  Uploaded once."""
+
+    def __init__(self, ppm_optimizer, state_init_list, state_real_list, actions, K, sort=True):
+        self.ppm, self.K = ppm_optimizer, int(K)
+        task = ppm_optimizer.task_config
+        self.dev = dev = _require_gpu(ppm_optimizer.device)
+        model = ppm_optimizer.model
+        if not isinstance(model, DynamicsPredictor):
+            raise TypeError("model must be an adaptigraph_amd.DynamicsPredictor")
+        assert int(task["n_his"]) == model.n_his, "task_config['n_his'] (forward_dynamics.py:16) must be the model's n_his"
+        names = list(ppm_optimizer.material_dims.keys())
+        assert len(names) == 1, "only support single material now"
+        self.name = names[0]
+        before, before_valid, after, after_valid, pushes = _problem(ppm_optimizer, state_init_list, state_real_list, actions)
+        action_cpu = pushes[:, None]                                             # forward_dynamics.py:218
+        decoded, repeat = decode_action(action_cpu, push_length=task["push_length"])
+        xz, delta = _tool_layout(decoded, action_cpu[:, :, 2], task)
+        self.n, self.N_o, self.M = before.shape[0], before.shape[1], ppm_optimizer.eef_num
+        assert xz.shape[2] == self.M
+        rep = repeat[:, 0].to(torch.int64).numpy()
+        self.order = np.argsort(-rep, kind="stable") if sort else np.arange(self.n)   # row block j holds interaction order[j]
+        idx = torch.from_numpy(np.repeat(self.order, self.K))
+        take = lambda t: t.to(dev)[idx.to(dev)].contiguous()                      # noqa: E731
+        self.state0, self.obs = take(before), take(after)
+        self.obj_mask, self.obs_mask = take(before_valid).view(torch.uint8), take(after_valid).view(torch.uint8)
+        self.xz, self.delta = take(xz[:, 0].to(torch.float32)), take(delta[:, 0].to(torch.float32))
+        self.h_repeat = np.ascontiguousarray(rep[np.repeat(self.order, self.K)].astype(np.int32))
+        self.d_repeat = torch.from_numpy(self.h_repeat).to(dev)
+        self.R, self.N_t = self.n * self.K, after.shape[1]
+        self.row_w = torch.full((self.R,), 1.0 / self.n, device=dev, dtype=torch.float32)   # d(mean over the interactions)
+        self.w = [p.detach() for p in model.ordered_parameters()]
+        for t in self.w:
+            assert t.device == dev and t.dtype == torch.float32 and t.is_contiguous(), "model parameters must be fp32 on the device"
+        from .autograd import _vp_array
+        self._w_arr = _vp_array(self.w)
+        self.seqs = torch.empty((self.R, self.N_o, 3), device=dev, dtype=torch.float32)
+        self.err = torch.empty((self.R,), device=dev, dtype=torch.float32)
+        self.grad = torch.zeros((self.R, self.N_o), device=dev, dtype=torch.float32)
+        self.max_nR = int(task["max_nR"])
+        self.edge_rows = None
+
+    def run(self, phys, status, want_grad):
+        """enqueue ag_ppm_grad_step on the current stream: phys (R,N_o) device fp32 -> self.seqs, self.err, self.grad"""
+        ppm, task, dev = self.ppm, self.ppm.task_config, self.dev
+        eng = ppm.model.engine(dev)
+        grip = bool(task["gripper_enable"])
+        N = self.N_o + self.M
+        k = min(N, int(task["topk"]))
+        bound = N * (k + self.M) if k < N else N * N                              # the builder's structural bound
+        edge_rows = int(self.edge_rows) if self.edge_rows is not None else bound
+        p = _lib.AgRolloutParams(self.R, 1, self.N_o, self.M, int(task["topk"]), int(bool(task["connect_tools_all"])),
+                                 int(self.max_nR), 1, float(ppm.adj_thresh), float(0.01 * task["sim_real_ratio"]) if grip else 0.0,
+                                 int(grip), 0.0)
+        eng.check(eng.lib.ag_ppm_grad_step(
+            eng.ctx, current_stream(dev), C.byref(p), ptr(self.state0), ptr(self.obj_mask), ptr(self.xz), ptr(self.delta),
+            C.c_void_p(self.h_repeat.ctypes.data), ptr(self.d_repeat), ptr(phys), ptr(self.obs), ptr(self.obs_mask), self.N_t,
+            ptr(self.row_w), self._w_arr, max(1, edge_rows), int(want_grad), ptr(self.seqs), ptr(self.err), ptr(self.grad),
+            ptr(status)))
+        return eng
+
+
+class PhysParamFit:
+    """optimize_grad's iteration resident on the GPU.  fit = PhysParamFit(ppm_optimizer, actions, state_init_list,
+    state_real_list, n_starts=8, lr=0.05); fit.step() x iterations; fit.evaluate(); best, err, init_err = fit.result().
+
+    The problem is uploaded and stacked n_starts-fold once.  step() enqueues ag_ppm_grad_step (masked rollout, chamfer, backward
+    toward the parameter) and ag_ppm_adam_step (per-start reduction, history, best-so-far, Adam in double, clamp) and returns:
+    nothing between two iterations waits for the GPU, neither the parameter nor its gradient passes through the host.  Parameter,
+    Adam moments, history and the status words live on the device for the life of the object.  iterations: rows of the device
+    history beyond the first (evaluations past it still compete for the result, they are just not recorded).  starts: (K,dim)
+    starting points instead of optimize_grad's _starting_points.  max_nR (attribute, from the task config) may be changed between
+    steps; edge_rows (attribute, None = the builder's structural bound) bounds the edge rows of the backward workspace."""
+
+    def __init__(self, ppm_optimizer, actions, state_init_list, state_real_list, n_starts=8, lr=0.05, iterations=50, starts=None):
+        names = list(ppm_optimizer.material_dims.keys())
+        assert len(names) == 1, "only support single material now"
+        if starts is None:
+            current = ppm_optimizer.physics_param[names[0]].detach().to("cpu", torch.float64).numpy().reshape(-1)
+            starts = _starting_points(current, n_starts)
+        x = np.asarray(starts, np.float64).astype(np.float32)
+        assert x.ndim == 2 and x.shape[1] == 1, "one value per start: the model takes one physics parameter per particle (model.py:92-95)"
+        self.K, self.dim, self.lr = x.shape[0], x.shape[1], float(lr)
+        self.problem = pr = _DeviceProblem(ppm_optimizer, state_init_list, state_real_list, actions, self.K)
+        dev = self.device = pr.dev
+        self.hist_cap = max(1, int(iterations) + 1)
+        self.x = torch.from_numpy(x[:, 0].copy()).to(dev)
+        self.exp_avg = torch.zeros(self.K, device=dev, dtype=torch.float64)
+        self.exp_avg_sq = torch.zeros(self.K, device=dev, dtype=torch.float64)
+        self.hist_x = torch.zeros((self.hist_cap, self.K), device=dev, dtype=torch.float32)
+        self.hist_err = torch.zeros((self.hist_cap, self.K), device=dev, dtype=torch.float64)
+        self.best = torch.tensor([np.inf, 0.0, 0.0, np.inf], device=dev, dtype=torch.float64)
+        self.last_grad = torch.zeros(self.K, device=dev, dtype=torch.float64)      # per start, of the latest step()
+        self.phys = self.x[None, :, None].expand(pr.n, self.K, pr.N_o).reshape(pr.R, pr.N_o).contiguous()
+        self._status = torch.zeros(4, dtype=torch.int32, device=dev)               # [0] overflow flag, [1] evaluations, [2] updates
+        self._step = 0                                                              # host counter of enqueued evaluations
+        self._updates = 0                                                           # ... of enqueued Adam updates (bias corrections)
+
+    max_nR = property(lambda self: self.problem.max_nR, lambda self, v: setattr(self.problem, "max_nR", int(v)))
+    edge_rows = property(lambda self: self.problem.edge_rows, lambda self, v: setattr(self.problem, "edge_rows", v))
+
+    def _run(self, apply):
+        pr = self.problem
+        eng = pr.run(self.phys, self._status, want_grad=apply)
+        it = self._updates                                                          # evaluate() in between does not count
+        eng.check(eng.lib.ag_ppm_adam_step(
+            eng.ctx, current_stream(self.device), ptr(pr.err), ptr(pr.grad) if apply else None, self.K, pr.n, pr.N_o, 0, int(apply),
+            self.lr, 1.0 - 0.9 ** (it + 1), 1.0 - 0.999 ** (it + 1), PARAM_BOUNDS[0], PARAM_BOUNDS[1], ptr(self.x), ptr(self.exp_avg),
+            ptr(self.exp_avg_sq), self.hist_cap, ptr(self.hist_x), ptr(self.hist_err), ptr(self.best), ptr(self.last_grad),
+            ptr(self.phys), ptr(self._status)))
+        self._step += 1
+        self._updates += int(apply)
+
+    def step(self):
+        """One iteration: evaluate the current parameters with their gradient, record, Adam.  Enqueue only.  An iteration with a
+        graph beyond max_nR is skipped on the device - parameters, moments and history stay - as is every following one until
+        result() has reported it."""
+        self._run(True)
+
+    def evaluate(self):
+        """Forward and loss only at the current parameters: recorded and competing for the result, no update.  Enqueue only."""
+        self._run(False)
+
+    def result(self, return_res=False):
+        """The one read-back (waits for what was enqueued): (physics_param (dim,) float32, error, init_error[, res]) as
+        optimize_grad returns them.  Raises Exception("Exceeds max dims"), as the reference's dynamics_masked does, when an
+        evaluation since the last result() was skipped; the counters are then back at the recorded evaluations and applied
+        updates and the flag is cleared, so the object is where it was before the first skipped step."""
+        host = torch.cat([self._status.to(torch.float64), self.best, self.hist_x.reshape(-1).to(torch.float64),
+                          self.hist_err.reshape(-1)]).cpu().numpy()
+        if host[0] != 0:
+            self._step, self._updates = int(host[1]), int(host[2])
+            self._status[0] = 0
+            raise Exception("Exceeds max dims")                                   # src/dynamics/utils.py:63-65
+        n = min(int(host[1]), self.hist_cap)
+        best_x = np.full((self.dim,), host[5], np.float32)
+        if not return_res:
+            return best_x, host[4], host[7]
+        hk = self.hist_cap * self.K
+        params = host[8:8 + hk].astype(np.float32).reshape(self.hist_cap, self.K, 1)[:n]
+        errors = host[8 + hk:8 + 2 * hk].reshape(self.hist_cap, self.K)[:n].copy()
+        return best_x, host[4], host[7], {"params": params, "errors": errors, "best_start": int(host[6])}
+
+
+def optimize_grad_device(ppm_optimizer, actions, state_init_list, state_pred_list, state_real_list, iterations=50, n_starts=8,
+                         lr=0.05, return_res=False):
+    """optimize_grad on PhysParamFit: the same arguments, starting points, Adam, clamp, rule that every evaluated parameter
+    competes for the result, and return tuple - but an iteration only enqueues and the result is read back once at the end."""
+    if iterations < 0:
+        iterations = 200                                                         # :78-79
+    if iterations == 0:
+        fit = PhysParamFit(ppm_optimizer, actions, state_init_list, state_real_list, n_starts=1, lr=lr, iterations=0)
+        fit.evaluate()
+        return fit.result()[1]                                                   # :87-88
+    fit = PhysParamFit(ppm_optimizer, actions, state_init_list, state_real_list, n_starts=n_starts, lr=lr, iterations=iterations)
+    for _ in range(iterations):
+        fit.step()
+    fit.evaluate()
+    return fit.result(return_res)
+
+
+def dynamics_error_grad_device(physics_param, ppm_optimizer, state_init_list, state_real_list, actions, _out=None):
+    """dynamics_error_grad through ONE ag_ppm_grad_step: the same arguments ((dim,), (B,1) or (B,n_p) parameter) and the same
+    (error, grad) - float64, the gradient shaped like the parameter.  Raises Exception("Exceeds max dims") like it.
+    _out: a dict that receives the captured 'state_seqs' (B,n_p,3) and the per-row 'chamfer' (B,) as device tensors (tests)."""
+    pr = _DeviceProblem(ppm_optimizer, state_init_list, state_real_list, actions, 1, sort=False)
+    physics_param = _as_param_dict(physics_param, ppm_optimizer)
+    (name, value), = physics_param.items()
+    value = value.detach().to("cpu", torch.float32)
+    shape = tuple(value.shape)
+    if value.dim() <= 1:
+        assert value.numel() == 1, "one value: the model takes one physics parameter per particle (model.py:92-95)"
+        rows = value.reshape(1, 1).expand(pr.n, pr.N_o)
+    else:
+        assert value.shape[0] == pr.n and value.shape[1] in (1, pr.N_o), \
+            f"physics parameter of shape {shape}: expected (dim,), ({pr.n}, 1) or ({pr.n}, {pr.N_o})"
+        rows = value.expand(pr.n, pr.N_o)
+    phys = rows.contiguous().to(pr.dev)
+    status = torch.zeros(4, dtype=torch.int32, device=pr.dev)
+    pr.run(phys, status, want_grad=True)
+    host = torch.cat([status.to(torch.float32), pr.err, pr.grad.reshape(-1)]).cpu().numpy()   # the one wait
+    if host[0] != 0:
+        raise Exception("Exceeds max dims")                                       # utils.py:63-65
+    if _out is not None:
+        _out.update(state_seqs=pr.seqs, chamfer=pr.err)
+    error = host[4:4 + pr.n].astype(np.float64).mean()
+    g = host[4 + pr.n:].astype(np.float64).reshape(pr.n, pr.N_o)
+    if value.dim() <= 1:
+        col = g[:, 0].copy()
+        for i in range(1, pr.N_o):                                               # fixed order
+            col += g[:, i]
+        total = col[0]
+        for i in range(1, pr.n):
+            total += col[i]
+        return error, np.full(shape, total, np.float64)
+    if value.shape[1] == 1:
+        col = g[:, 0].copy()
+        for i in range(1, pr.N_o):
+            col += g[:, i]
+        return error, col.reshape(pr.n, 1)
+    return error, g

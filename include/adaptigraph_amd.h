@@ -30,7 +30,7 @@
  *       ag_ctx_load_weights, ag_ctx_set_precision     always (host repack + copies)
  *       ag_forward, ag_rollout                        once, at the end: they return the overflow verdict (AG_ERR_MAX_NR)
  *       ag_backward, ag_backward_inputs               at the start (edge counts) and at the end
- *       ag_ctx_load_weights_device, ag_adam_step, ag_train_step   NEVER: they only enqueue on the caller's stream; an overflowed
+ *       ag_ctx_load_weights_device, ag_adam_step, ag_train_step, ag_ppm_grad_step, ag_ppm_adam_step   NEVER: they only enqueue on the caller's stream; an overflowed
  *           graph is reported in device memory (d_status), which the caller reads when it chooses to
  *       ag_rollout_work                               for its plan (and a base rollout, if none is kept): it returns host numbers
  *       ag_ctx_rollout_counts (after a device-planned call without prefix sharing), ag_ctx_share_counts   wait for the device
@@ -320,6 +320,54 @@ int ag_train_step(ag_ctx* ctx, void* stream, const float* d_state, const float* 
                   int32_t n_future, const float* d_state_future, const float* d_eef_future, const float* d_action_future,
                   int32_t store_rest_state, int32_t edge_rows, int32_t want_grad, float* const* d_grad_w, float* d_loss,
                   float* d_pred, int32_t* d_status);
+
+/* ---- Device-resident physics-parameter fit (reference src/planning/physics_param_optimizer.py:178-226 under autograd).  Neither
+ * call waits for the GPU. ---- */
+
+/* One evaluation of the fit's objective and its gradient toward the physics parameter, enqueue only: dynamics_masked
+ * (forward_dynamics.py:209-399) on R = p->B rows (p->H must be 1, p->y_mode 1; p->physics_param is unused), the masked chamfer of
+ * each row's captured cloud to its observed cloud, and - when want_grad - the backward through the chain.  Edges are constants
+ * of the gradient, as under the reference's autograd.
+ *   d_state0 (R,N_o,3), d_obj_mask (R,N_o): per-row padded start clouds and masks; d_eef_xz (R,M,2), d_eef_delta (R,M,3): the
+ *   shim's host decode, as for ag_rollout; h_repeat (R) HOST int32 = action_repeat: the step count S = max repeat and every
+ *   step's live prefix come from it without a read-back, d_repeat (R) the same values on the device (the capture reads them).
+ *   Step s runs over rows [0, L_s), L_s = 1 + the last row with repeat >= s: a caller that orders its rows by descending repeat
+ *   steps every row exactly repeat times; any order gives the same outputs (the reference steps every row S times and discards).
+ *   d_phys (R,N_o) the per-particle parameter; d_obs (R,N_t,3), d_obs_mask (R,N_t) the observed clouds; d_row_weight (R) the
+ *   weight of each row's chamfer distance in the loss; d_w[22] the plain parameters (the values the context's weights were
+ *   loaded from); edge_rows the caller's bound on a graph's edge count (sizes the workspace:
+ *   per step B*(n_his*N*3 + 2*cap + N + 3) words kept for the backward, cap = min(max_nR, edge_rows), N = N_o + M, plus one
+ *   backward chunk of ag_train_step's size).
+ *   Per step: the batch edge builder on the last frame, the forward of ag_forward (same kernels, same bits), capture into
+ *   d_state_seqs where repeat == s, tool rows = last + delta with y = the masked mean y of the prediction (fp64, fixed order,
+ *   rounded once) + gripper offset, history shift.  Backward, last step first: dLoss/dpred = chamfer gradient where captured +
+ *   the object rows of the next step's dLoss/dstate + its tool rows' y / valid count on every valid object row's y; the backward
+ *   of ag_backward_inputs without the weight gradients; d_grad_phys accumulates the steps' dLoss/dphys in that order.
+ *   Outputs: d_state_seqs (R,N_o,3), d_err (R) the chamfer distances, d_grad_phys (R,N_o) (want_grad), d_status (int32 x 4):
+ *   [0] receives (atomic max, never cleared here) the edge count of a graph with more than min(max_nR, edge_rows) edges - such a
+ *   graph is walked as an empty one and ag_ppm_adam_step skips; [1], [2] are ag_ppm_adam_step's.
+ * Returns AG_OK for an overflowed graph.  No float atomics; a row's outputs do not depend on which other rows share the call. */
+int ag_ppm_grad_step(ag_ctx* ctx, void* stream, const ag_rollout_params* p, const float* d_state0, const uint8_t* d_obj_mask,
+                     const float* d_eef_xz, const float* d_eef_delta, const int32_t* h_repeat, const int32_t* d_repeat,
+                     const float* d_phys, const float* d_obs, const uint8_t* d_obs_mask, int32_t N_t, const float* d_row_weight,
+                     const float* const* d_w, int32_t edge_rows, int32_t want_grad, float* d_state_seqs, float* d_err,
+                     float* d_grad_phys, int32_t* d_status);
+
+/* The optimiser's side of one iteration, one small launch over n_starts starts of n_rows rows each (row of start k, interaction
+ * i = k*n_rows + i when start_major, else i*n_starts + k).  Does nothing while d_status[0] != 0.  Otherwise, with it =
+ * d_status[1]: per start the mean of its rows' d_err and the sum of its rows' d_grad_phys over rows and particles, in fp64 in a
+ * fixed order (-> d_grad_start (n_starts); left as it is when d_grad_phys is NULL); d_hist_x / d_hist_err (hist_cap,n_starts)
+ * row `it` = the evaluated parameter d_x and its error (it < hist_cap); d_best = [lowest error so far, its parameter, its
+ * start, the first error of start 0]; when apply_update: Adam in double (beta 0.9 / 0.999, eps 1e-8; the bias corrections
+ * 1 - beta^step are formed by the caller), clamp to [lo, hi], round to fp32 into d_x and into that start's rows of d_phys
+ * (R,N_o); d_status[1] = it + 1, and d_status[2] += 1 when the update was applied (the count the caller's next bias
+ * corrections continue from).
+ * d_best[0] must start at +inf, the moments at zero. */
+int ag_ppm_adam_step(ag_ctx* ctx, void* stream, const float* d_err, const float* d_grad_phys, int32_t n_starts, int32_t n_rows,
+                     int32_t N_o, int32_t start_major, int32_t apply_update, double lr, double bias_correction1,
+                     double bias_correction2, double lo, double hi, float* d_x, double* d_exp_avg, double* d_exp_avg_sq,
+                     int32_t hist_cap, float* d_hist_x, double* d_hist_err, double* d_best, double* d_grad_start, float* d_phys,
+                     int32_t* d_status);
 
 /* Replaces the device side of dynamics() / dynamics_masked() (src/planning/forward_dynamics.py:12-205, 209-399):
  * the whole look-ahead x action-repeat loop, graph rebuilt every step, no host sync inside.

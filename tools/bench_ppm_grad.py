@@ -3,10 +3,13 @@
 n_starts x 20 rows) at n_starts 1 and 8 on a 20-interaction rope problem (clouds and pushes drawn like the
 ppm_dynamics_error fixture's), and for scale one dynamics_error call on the same problem (the gradient-free path: the fused
 rollout + chamfer).  Reported, not asserted: the per-call host synchronisations of ag_forward / ag_backward_inputs (DESIGN.md
-section 3.10) are part of the number.
+section 3.10) are part of the number.  fit1 / fit8: one PhysParamFit.step() (ag_ppm_grad_step + ag_ppm_adam_step, enqueue only;
+the timed window ends in a device synchronise) on the same problem, alternated with grad1 / grad8 in the same process.
 
   python tools/bench_ppm_grad.py [--rounds 5] [--iters 5] [--warmup 2] [--out FILE]
-  python tools/bench_ppm_grad.py --only grad8 --rounds 1 --iters 3     (e.g. under rocprofv3 --kernel-trace --stats)
+  python tools/bench_ppm_grad.py --only fit8 --rounds 1 --iters 3     (e.g. under rocprofv3 --kernel-trace --stats)
+  python tools/bench_ppm_grad.py --only fit8 --edge-rows 1100         (fit legs with PhysParamFit.edge_rows = 1100 instead of
+                                                                       the builder's structural bound N * (topk + M))
 """
 import argparse
 import json
@@ -59,14 +62,25 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--only", choices=["grad1", "grad8", "error"])
+    ap.add_argument("--only", choices=["grad1", "grad8", "fit1", "fit8", "error"])
+    ap.add_argument("--edge-rows", type=int)
     ap.add_argument("--out")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     ppm, inits, reals, acts = make_problem(dev)
     problem = PPO._problem(ppm, inits, reals, acts)
+    fits = {}
+
+    def fit_step(k):                                # the fit object is built once: the upload is not part of an iteration
+        if k not in fits:
+            fits[k] = ag.PhysParamFit(ppm, acts, inits, reals, n_starts=k, iterations=0)
+            fits[k].edge_rows = a.edge_rows
+        fits[k].step()
+
     legs = {"grad1": lambda: PPO._stacked_eval(PPO._starting_points([0.5], 1), ppm, problem),
+            "fit1": lambda: fit_step(1),
             "grad8": lambda: PPO._stacked_eval(PPO._starting_points([0.5], 8), ppm, problem),
+            "fit8": lambda: fit_step(8),
             "error": lambda: ag.dynamics_error([0.5], ppm, inits, reals, acts)}
     if a.only:
         legs = {a.only: legs[a.only]}
@@ -82,7 +96,9 @@ def main():
                 fn()
             torch.cuda.synchronize()
             times[k].append((time.perf_counter() - t0) / a.iters * 1e3)
-    res = {"interactions": len(acts), "rounds": a.rounds, "iters": a.iters, "device": torch.cuda.get_device_name(0),
+    for fit in fits.values():
+        fit.result()                                # raises if a step was skipped (a graph beyond max_nR)
+    res = {"interactions": len(acts), "edge_rows": a.edge_rows, "rounds": a.rounds, "iters": a.iters, "device": torch.cuda.get_device_name(0),
            "ms": {k: {"median": float(np.median(v)), "min": float(min(v)), "max": float(max(v))} for k, v in times.items()}}
     line = json.dumps(res)
     print(line)

@@ -31,7 +31,7 @@ EXPORTS = ["ag_abi_version", "ag_ctx_create", "ag_ctx_destroy", "ag_last_error",
            "ag_edges_apply_tool_rule", "ag_mppi_sample", "ag_mppi_update", "ag_mppi_clip",
            "ag_ctx_set_option", "ag_ctx_get_option", "ag_ctx_rollout_counts", "ag_rollout_actions", "ag_ctx_share_counts", "ag_ctx_launch_counts", "ag_cost_reward", "ag_cost_cloth_combine",
            "ag_ctx_alloc_counts", "ag_rollout_work", "ag_backward", "ag_backward_inputs", "ag_cost_chamfer_backward",
-           "ag_ctx_load_weights_device", "ag_adam_step", "ag_train_step", "ag_ppm_grad_step", "ag_ppm_adam_step"]
+           "ag_ctx_load_weights_device", "ag_adam_step", "ag_train_step", "ag_ppm_grad_step", "ag_ppm_adam_step", "ag_train_step_part"]
 
 OPTIONS = ["streams", "chunk", "latency", "ragged", "ell_graph", "self_dedupe", "repeat_sort", "edge_wgs", "edge_block_min",
            "enc_persist", "stagger_us", "device_decode", "zigzag", "share_first", "share_prefix", "stream_min_rows", "pipeline_fork"]
@@ -90,6 +90,7 @@ def load():
     lib.ag_adam_step.argtypes = [vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i32, f64, f64, f64, f64, f64, vp]
     lib.ag_train_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, C.POINTER(vp),
                                   i32, vp, vp, vp, i32, i32, i32, C.POINTER(vp), vp, vp, vp]
+    lib.ag_train_step_part.argtypes = lib.ag_train_step.argtypes + [i32, i32]
     lib.ag_ppm_grad_step.argtypes = [vp, vp, C.POINTER(AgRolloutParams), vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, C.POINTER(vp),
                                      i32, i32, vp, vp, vp, vp]
     lib.ag_ppm_adam_step.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, f64, f64, f64, f64, f64, vp, vp, vp, i32, vp, vp, vp,

@@ -939,6 +939,18 @@ int ag_train_step(ag_ctx* c, void* stream, const float* d_state, const float* d_
                   int32_t n_future, const float* d_state_future, const float* d_eef_future, const float* d_action_future,
                   int32_t store_rest_state, int32_t edge_rows, int32_t want_grad, float* const* d_grad_w, float* d_loss,
                   float* d_pred, int32_t* d_status) {
+    return ag_train_step_part(c, stream, d_state, d_attrs, d_action, d_phys, d_group, n_inst, d_recv, d_send, d_row_ptr, d_n_edges,
+                              edge_cap, B, N, n_p, d_w, n_future, d_state_future, d_eef_future, d_action_future, store_rest_state,
+                              edge_rows, want_grad, d_grad_w, d_loss, d_pred, d_status, B, 0);
+}
+
+// B_total = B, accumulate = 0 is ag_train_step: the same launches with the same arguments, so the same bits
+int ag_train_step_part(ag_ctx* c, void* stream, const float* d_state, const float* d_attrs, const float* d_action, const float* d_phys,
+                       const float* d_group, int32_t n_inst, const int32_t* d_recv, const int32_t* d_send, const int32_t* d_row_ptr,
+                       const int32_t* d_n_edges, int32_t edge_cap, int32_t B, int32_t N, int32_t n_p, const float* const* d_w,
+                       int32_t n_future, const float* d_state_future, const float* d_eef_future, const float* d_action_future,
+                       int32_t store_rest_state, int32_t edge_rows, int32_t want_grad, float* const* d_grad_w, float* d_loss,
+                       float* d_pred, int32_t* d_status, int32_t B_total, int32_t accumulate) {
     if (!c) return AG_ERR_INVALID;
     if (!c->have_w) return fail(c, AG_ERR_NO_WEIGHTS, "ag_train_step before ag_ctx_load_weights / ag_ctx_load_weights_device");
     if (!d_state || !d_attrs || !d_action || !d_phys || !d_group || !d_recv || !d_send || !d_row_ptr || !d_n_edges || !d_state_future ||
@@ -947,6 +959,7 @@ int ag_train_step(ag_ctx* c, void* stream, const float* d_state, const float* d_
     if (B < 1 || N < 1 || n_p < 1 || n_p > N || n_inst < 1 || edge_cap < 1 || edge_rows < 1 || n_future < 1)
         return fail(c, AG_ERR_INVALID, "ag_train_step: bad sizes B=%d N=%d n_p=%d n_inst=%d edge_cap=%d edge_rows=%d n_future=%d", B, N, n_p,
                     n_inst, edge_cap, edge_rows, n_future);
+    if (B_total < B) return fail(c, AG_ERR_INVALID, "ag_train_step_part: B_total=%d is below B=%d", B_total, B);
     if (n_future > 1 && (!d_eef_future || !d_action_future)) return fail(c, AG_ERR_INVALID, "ag_train_step: n_future > 1 needs eef_future and action_future");
     if (want_grad) {
         if (!d_w || !d_grad_w) return fail(c, AG_ERR_INVALID, "ag_train_step: want_grad needs d_w and d_grad_w");
@@ -967,7 +980,7 @@ int ag_train_step(ag_ctx* c, void* stream, const float* d_state, const float* d_
     t.attrs = d_attrs; t.phys = d_phys; t.group = d_group; t.n_inst = n_inst;
     t.recv = d_recv; t.send = d_send; t.row_ptr = d_row_ptr; t.edge_cap = edge_cap;
     t.B = B; t.N = N; t.n_p = n_p; t.n_his = n_his; t.pstep = c->dims.pstep; t.clamp = c->dims.motion_clamp;
-    t.Ep = cap; t.want_w = true;
+    t.Ep = cap; t.want_w = true; t.wide = accumulate != 0;
     size_t wf = 0, wi = 0;
     int Bb = 1;
     if (want_grad) {
@@ -1012,7 +1025,7 @@ int ag_train_step(ag_ctx* c, void* stream, const float* d_state, const float* d_
         rc = enqueue_forward(c, w, Bc, state_of(fi), d_attrs, action_of(fi), d_phys, d_group, n_inst, d_recv, d_send, d_row_ptr, n_eff,
                              edge_cap, B, N, n_p, pred, motion, st);
         if (rc) return rc;
-        HIPCHK(c, launch_step_loss(pred, d_state_future, B, n_p, n_future, fi, part, d_loss, st));
+        HIPCHK(c, launch_step_loss(pred, d_state_future, B, n_p, n_future, fi, B_total, accumulate ? 1 : 0, part, d_loss, st));
         if (fi + 1 < n_future)
             HIPCHK(c, launch_next_state(state_of(fi), pred, d_eef_future, d_action_future, B, N, n_p, n_his, n_future, fi, rest,
                                         S + (size_t)fi * n_state, A + (size_t)fi * n_act, st));
@@ -1022,13 +1035,13 @@ int ag_train_step(ag_ctx* c, void* stream, const float* d_state, const float* d_
     int n22[22];
     weight_tensor_sizes(c->dims.rel_dim, n22);
     for (int k = 0; k < 22; ++k) {
-        HIPCHK(c, hipMemsetAsync(d_grad_w[k], 0, (size_t)n22[k] * 4, st));
+        if (!accumulate) HIPCHK(c, hipMemsetAsync(d_grad_w[k], 0, (size_t)n22[k] * 4, st));   // else: the earlier parts' sums stay
         t.w[k] = d_w[k]; t.g[k] = d_grad_w[k];
     }
     t.n_edges = n_eff; t.dpos = dpos;
     for (int fi = n_future - 1; fi >= 0; --fi) {
         const float* dnext = fi + 1 < n_future ? D[1] : nullptr;     // total dLoss/dstate of step fi + 1
-        HIPCHK(c, launch_pred_grad(P + (size_t)fi * n_pred, d_state_future, dnext, B, N, n_p, n_his, n_future, fi, dpos, st));
+        HIPCHK(c, launch_pred_grad(P + (size_t)fi * n_pred, d_state_future, dnext, B, N, n_p, n_his, n_future, fi, B_total, dpos, st));
         t.state = state_of(fi); t.action = action_of(fi);
         t.dstate = fi > 0 ? D[0] : nullptr;                          // step 0's input is data
         for (int b0 = 0; b0 < B; b0 += Bb) HIPCHK(c, train_backward_chunk(t, b0, std::min(Bb, B - b0), wsf, wsi, slab, st));

@@ -348,6 +348,7 @@ struct TrainArgs {
     float* dstate;                          // (B,n_his,N,3) or null (= not wanted)
     float* dphys; float* daction;           // (B,N), (B,N,3) or null (= not wanted): ag_backward_inputs
     bool want_w;                            // false: none of the 22 weight gradients is wanted, their GEMMs are skipped
+    bool wide;                              // true: g[k] holds an earlier part's gradients; each reduction adds them in fp64, one rounding
 };
 size_t train_slab_floats();
 size_t train_work_floats(int Bc, int N, int Ep, int n_his, int pstep);
@@ -368,14 +369,16 @@ struct AdamArgs {
     int* status;                // [0] != 0: skip; else [1] += 1
 };
 hipError_t launch_adam(const AdamArgs& a, hipStream_t st);
-// glue of the chained step (train.py:86-124); fut = state_future (B,n_future,n_p,3), part = train_glue_doubles() doubles
+// glue of the chained step (train.py:86-124); fut = state_future (B,n_future,n_p,3), part = train_glue_doubles() doubles.
+// B_total: rows of the whole optimiser step, the mean's denominator (= B for a one-call step); accumulate: loss[] holds the
+// earlier parts' shares and is added to (in fp64, one rounding)
 size_t train_glue_doubles();
-hipError_t launch_step_loss(const float* pred, const float* fut, int B, int n_p, int n_future, int fi, double* part, float* loss,
-                            hipStream_t st);
+hipError_t launch_step_loss(const float* pred, const float* fut, int B, int n_p, int n_future, int fi, int B_total, int accumulate,
+                            double* part, float* loss, hipStream_t st);
 hipError_t launch_next_state(const float* state, const float* pred, const float* eef, const float* act_f, int B, int N, int n_p,
                              int n_his, int n_future, int fi, int rest, float* state_next, float* action_next, hipStream_t st);
 hipError_t launch_pred_grad(const float* pred, const float* fut, const float* dnext, int B, int N, int n_p, int n_his, int n_future,
-                            int fi, float* dpos, hipStream_t st);
+                            int fi, int B_total, float* dpos, hipStream_t st);
 hipError_t launch_dstate_carry(float* d, const float* dnext, int B, int N, int n_his, int rest, hipStream_t st);
 
 // ---- device-resident physics-parameter fit (ag_ppm.hip; ag_ppm_grad_step, ag_ppm_adam_step): the glue of the masked rollout

@@ -1,4 +1,4 @@
-// Device-resident training step (ag_ctx_load_weights_device, ag_adam_step, ag_train_step): what lives between the model
+// Device-resident training step (ag_ctx_load_weights_device, ag_adam_step, ag_train_step, ag_train_step_part): what lives between the model
 // forwards and the backward chunks of ag_train.hip, gfx950 only.
 //   * the weight images of the forward chains from the 22 plain fp32 tensors.  ONE table (kPackBlocks) lists the 14 packed blocks
 //     of the 11 layers; every image element is one call of an element function (pack_elem_*) that the host packer
@@ -287,12 +287,16 @@ __global__ __launch_bounds__(256) void k_mse_part(const float* pred, const float
     }
     if (threadIdx.x == 0) part[blockIdx.x] = sh[0];
 }
-// loss[fi] = mean, rounded once; after the last step loss[n_future] = the fp32 sum of the steps in step order (train.py:103)
-__global__ void k_mse_final(const double* part, long n, int fi, int n_future, float* loss) {
+// loss[fi] = sum / n (n = the elements of the whole step: this call's share of the mean), rounded once; accumulate: the earlier
+// parts' loss[fi] joins in fp64 before that rounding.  After the last step loss[n_future] = the fp32 sum of the steps in step
+// order (train.py:103)
+__global__ void k_mse_final(const double* part, long n, int fi, int n_future, int accumulate, float* loss) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     double s = 0.0;
     for (int k = 0; k < kLossBlocks; ++k) s += part[k];
-    loss[fi] = (float)(s / (double)n);
+    s = s / (double)n;
+    if (accumulate) s += (double)loss[fi];
+    loss[fi] = (float)s;
     if (fi == n_future - 1) {
         float t = 0.f;
         for (int k = 0; k < n_future; ++k) t += loss[k];
@@ -348,12 +352,12 @@ inline unsigned blocks(long n) { return (unsigned)((n + 255) / 256); }
 
 size_t train_glue_doubles() { return kLossBlocks; }
 
-hipError_t launch_step_loss(const float* pred, const float* fut, int B, int n_p, int n_future, int fi, double* part, float* loss,
-                            hipStream_t st) {
+hipError_t launch_step_loss(const float* pred, const float* fut, int B, int n_p, int n_future, int fi, int B_total, int accumulate,
+                            double* part, float* loss, hipStream_t st) {
     hipLaunchKernelGGL(k_mse_part, dim3(kLossBlocks), dim3(256), 0, st, pred, fut, B, n_p, n_future, fi, part);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_mse_final, dim3(1), dim3(64), 0, st, part, (long)B * n_p * 3, fi, n_future, loss);
+    hipLaunchKernelGGL(k_mse_final, dim3(1), dim3(64), 0, st, part, (long)B_total * n_p * 3, fi, n_future, accumulate, loss);
     return hipGetLastError();
 }
 hipError_t launch_next_state(const float* state, const float* pred, const float* eef, const float* act_f, int B, int N, int n_p,
@@ -363,8 +367,8 @@ hipError_t launch_next_state(const float* state, const float* pred, const float*
     return hipGetLastError();
 }
 hipError_t launch_pred_grad(const float* pred, const float* fut, const float* dnext, int B, int N, int n_p, int n_his, int n_future,
-                            int fi, float* dpos, hipStream_t st) {
-    const float scale = (float)(2.0 / ((double)B * n_p * 3));
+                            int fi, int B_total, float* dpos, hipStream_t st) {
+    const float scale = (float)(2.0 / ((double)B_total * n_p * 3));
     hipLaunchKernelGGL(k_pred_grad, dim3(blocks((long)B * n_p * 3)), dim3(256), 0, st, pred, fut, dnext, B, N, n_p, n_his, n_future,
                        fi, scale, dpos);
     return hipGetLastError();

@@ -91,7 +91,8 @@ __global__ __launch_bounds__(256) void k_gemm(GemmArgs a) {
 }
 
 // Weight-gradient reduction of the split-K slabs, fixed order, fp64: part[g][i] = sum of slabs 32g .. 32g+31 (k_reduce_part), then
-// dst_w[m*ldw + col0 + n] (n < n_w) or dst_b[m] (n == n_w) += sum over g ascending, rounded once (k_reduce)
+// dst_w[m*ldw + col0 + n] (n < n_w) or dst_b[m] (n == n_w) += sum over g ascending, rounded once (k_reduce).  wide: the old value
+// joins the fp64 sum before that one rounding (a later part of an accumulated step, ag_train_step_part); else it is added in fp32
 constexpr int kSlabGroup = 32;
 __global__ void k_reduce_part(const float* slab, int elems, int nz, double* part) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -101,14 +102,15 @@ __global__ void k_reduce_part(const float* slab, int elems, int nz, double* part
     for (int z = g * kSlabGroup; z < z1; ++z) s += (double)slab[(long)z * elems + i];
     part[(long)g * elems + i] = s;
 }
-__global__ void k_reduce(const double* part, int M, int Ncols, int ng, float* dst_w, int ldw, int col0, int n_w, float* dst_b) {
+__global__ void k_reduce(const double* part, int M, int Ncols, int ng, float* dst_w, int ldw, int col0, int n_w, float* dst_b, int wide) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= M * Ncols) return;
     const int m = i / Ncols, n = i % Ncols;
     double s = 0.0;
     for (int g = 0; g < ng; ++g) s += part[(long)g * M * Ncols + i];
-    if (n < n_w) dst_w[(long)m * ldw + col0 + n] += (float)s;
-    else if (dst_b) dst_b[m] += (float)s;
+    float* d = n < n_w ? dst_w + (long)m * ldw + col0 + n : (dst_b ? dst_b + m : nullptr);
+    if (!d) return;
+    *d = wide ? (float)((double)*d + s) : *d + (float)s;
 }
 
 __device__ inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
@@ -288,7 +290,7 @@ __global__ void k_input_grad(const float* dxn, int B, int N, int n_p, float* gph
 inline unsigned blocks(long n, int t = 256) { return (unsigned)((n + t - 1) / t); }
 
 // ---------------------------------------------------------------------------------------------------------- host helpers
-struct Ctx { hipStream_t st; float* slab; double* part; bool want_w; };   // want_w false: no weight gradient is wanted, linear_dw is skipped
+struct Ctx { hipStream_t st; float* slab; double* part; bool want_w; bool wide; };   // want_w false: no weight gradient is wanted, linear_dw is skipped; wide: k_reduce
 
 // C (M x N) = A (M x K) * B (K x N) with the epilogue of GemmArgs
 hipError_t gemm(hipStream_t st, GemmArgs a) {
@@ -341,7 +343,7 @@ hipError_t linear_dw(const Ctx& c, const float* dY, long lddy, long rows, int ou
     const int elems = out * ncols, ng = (nz + kSlabGroup - 1) / kSlabGroup;
     hipLaunchKernelGGL(k_reduce_part, dim3(blocks(elems), (unsigned)ng), dim3(256), 0, c.st, c.slab, elems, nz, c.part);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_reduce, dim3(blocks(elems)), dim3(256), 0, c.st, c.part, out, ncols, ng, gW, ldw, col0, in, gb);
+    hipLaunchKernelGGL(k_reduce, dim3(blocks(elems)), dim3(256), 0, c.st, c.part, out, ncols, ng, gW, ldw, col0, in, gb, c.wide ? 1 : 0);
     return hipGetLastError();
 }
 
@@ -370,7 +372,7 @@ hipError_t train_backward_chunk(const TrainArgs& t, int b0, int nb, float* wsf, 
     const long n = (long)nb * N, ne = (long)nb * Ep;
     const float* const* W = t.w;
     float* const* G = t.g;
-    Ctx c{st, slab, reinterpret_cast<double*>(slab + (size_t)kMaxSlabs * NF * (NF + 1)), t.want_w};
+    Ctx c{st, slab, reinterpret_cast<double*>(slab + (size_t)kMaxSlabs * NF * (NF + 1)), t.want_w, t.wide};
     size_t off = 0;
     auto take = [&](size_t k) { float* p = wsf + off; off += (k + 63) / 64 * 64; return p; };
     float* xn = take(n * 6); float* ph1 = take(n * NF); float* ph2 = take(n * NF); float* penc = take(n * NF);

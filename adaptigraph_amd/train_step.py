@@ -5,6 +5,12 @@ step() enqueues ag_train_step (n_future chained forwards, MSE, next-state assemb
 between two iterations waits for the GPU, no weight travels through the host.  Master weights, Adam's m and v, the gradients and
 the status words live on the device for the life of the object.  The autograd path (DynamicsPredictor.forward + loss.backward()
 + torch.optim) is untouched; this is a second way next to it.
+
+One optimiser step may also be built from PARTS (accumulate ... apply, or step_parts): micro-batches of one rank, buckets of a
+mixed-size batch with a tight max_edges each, or the shards of a data-parallel batch (group=).  Every part runs
+ag_train_step_part with the row count of the WHOLE step as the MSE denominator, so its loss and gradients are its share of the
+full batch's (MSELoss is a mean over B * n_p * 3 and n_p is the same in every part: loss = sum over parts of B_part / B_total *
+loss_part, exactly); the shares are summed on the device in call order and Adam is applied once.
 """
 from __future__ import annotations
 
@@ -59,10 +65,65 @@ def adam_state_from_torch(sd, order):
     return steps.pop(), m, v, hyper
 
 
-class TrainStep:
-    """ts = TrainStep(model, lr=1e-3, n_future=3); loss = ts.step(data, max_edges=k); ...; ts.check(); ts.sync_to_module()."""
+class StepParts:
+    """Host bookkeeping of one optimiser step built from parts: which total the parts were promised, how many rows came.  Pure
+    host object (no device, no library): every argument error of accumulate / apply / step is raised here, before anything is
+    enqueued.  spans_ranks: the parts of this rank are only a share of `total` (the other ranks hold the rest; nobody exchanges
+    counts, which would be a host wait), so the rows of this rank may stay below it."""
 
-    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, n_future=3, store_rest_state=False):
+    def __init__(self, spans_ranks=False):
+        self.spans_ranks = bool(spans_ranks)
+        self.total, self.rows, self.parts = None, 0, 0
+
+    @property
+    def open(self):
+        return self.parts > 0
+
+    def add(self, rows, total=None):
+        """Admit a part of `rows` graphs.  Returns (total, accumulate): accumulate is False for the first part of a step (it
+        overwrites), True after it."""
+        rows = int(rows)
+        if rows < 1:
+            raise ValueError(f"TrainStep.accumulate: a part of {rows} rows")
+        if not self.open:
+            total = rows if total is None else int(total)
+        else:
+            if total is None:
+                raise ValueError("TrainStep.accumulate: total is required from the second part of a step on")
+            if int(total) != self.total:
+                raise ValueError(f"TrainStep.accumulate: total {int(total)} differs from the {self.total} of this step's earlier parts")
+            total = self.total
+        if self.rows + rows > total:
+            raise ValueError(f"TrainStep.accumulate: {self.rows + rows} rows given, the step's total is {total}")
+        self.total, self.rows, self.parts = total, self.rows + rows, self.parts + 1
+        return total, self.parts > 1
+
+    def close(self):
+        """apply(): the rows must add up to the total (on one rank; at most the total when the step spans ranks)."""
+        if not self.open:
+            raise ValueError("TrainStep.apply: no part was accumulated")
+        if self.rows != self.total and not (self.spans_ranks and self.rows < self.total):
+            raise ValueError(f"TrainStep.apply: the parts hold {self.rows} rows, the step's total is {self.total}")
+        self.total, self.rows, self.parts = None, 0, 0
+
+    def forbid_open(self, what):
+        if self.open:
+            raise RuntimeError(f"TrainStep.{what} inside an open step: {self.parts} part(s) accumulated, apply() not called")
+
+
+class TrainStep:
+    """ts = TrainStep(model, lr=1e-3, n_future=3); loss = ts.step(data, max_edges=k); ...; ts.check(); ts.sync_to_module().
+
+    group: a torch.distributed process group (True = the default group) makes the object data-parallel.  Every rank constructs it
+    from the same weights and feeds its own shard; `total` of accumulate() is then the GLOBAL row count of the step (global_rows
+    is its default, and what step() / step_parts() use).  apply() sums the gradients and the loss vector over the ranks
+    (all_reduce SUM) and takes the MAX of the overflow word, so a graph that overflowed on one rank skips the step on every rank:
+    weights, m and v stay identical everywhere, and check() raises on every rank.  No count is exchanged behind the caller's
+    back.  With the nccl (RCCL) backend the three collectives are enqueued on the current stream and apply() still does not wait
+    for the GPU; with gloo torch stages the tensors through the host, so apply() waits (a rehearsal backend)."""
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, n_future=3, store_rest_state=False,
+                 group=None, global_rows=None):
         params = model.ordered_parameters()
         dev = _require_gpu(params[0].device)                     # no CPU fallback, as every other op
         self.model, self.device = model, dev
@@ -79,11 +140,24 @@ class TrainStep:
         self.w = [p.detach().to(dev, torch.float32).clone().contiguous() for p in params]
         self.exp_avg = [torch.zeros_like(w) for w in self.w]
         self.exp_avg_sq = [torch.zeros_like(w) for w in self.w]
-        self.grad = [torch.zeros_like(w) for w in self.w]
+        # the 22 gradients are views into ONE buffer (a data-parallel step moves it in one collective); every view starts on a
+        # 512-byte boundary, as a tensor of its own would
+        offs, n = [], 0
+        for w in self.w:
+            offs.append(n)
+            n += (w.numel() + 127) // 128 * 128
+        self._grad_flat = torch.zeros(n, device=dev)
+        self.grad = [self._grad_flat[o:o + w.numel()].view_as(w) for o, w in zip(offs, self.w)]
         self._status = torch.zeros(4, dtype=torch.int32, device=dev)   # [0] overflow flag, [1] applied steps
-        self._loss = torch.zeros(self.n_future + 1, device=dev)
+        # second buffer of a data-parallel step: the loss vector, then the copy of _status[0] that travels
+        self._small = torch.zeros(self.n_future + 2, dtype=torch.int32, device=dev)
+        self._loss = self._small[:self.n_future + 1].view(torch.float32)
+        self._flag = self._small[self.n_future + 1:]
         self._step = 0                                                  # host counter of enqueued optimiser steps
         self.last_pred = None
+        self.group = group
+        self.global_rows = None if global_rows is None else int(global_rows)
+        self._parts = StepParts(spans_ranks=group is not None)
         self._w_arr, self._g_arr = _vp_array(self.w), _vp_array(self.grad)
         self._m_arr, self._v_arr = _vp_array(self.exp_avg), _vp_array(self.exp_avg_sq)
         self._upload()
@@ -92,7 +166,8 @@ class TrainStep:
         eng = self.engine
         eng.check(eng.lib.ag_ctx_load_weights_device(eng.ctx, current_stream(self.device), self._w_arr))
 
-    def _run(self, data, max_edges, want_grad):
+    def _run(self, data, max_edges, want_grad, total=None, accumulate=False):
+        """total None: ag_train_step on the batch; else ag_train_step_part with B_total = total."""
         model, dev, eng = self.model, self.device, self.engine
         kw = {k: v for k, v in data.items() if k.endswith("_physics_param")}
         with torch.no_grad():
@@ -112,13 +187,76 @@ class TrainStep:
             if max_edges is None:
                 max_edges = int(edges.n_edges.max().item())                 # the one wait of the call
             pred = torch.empty((nf, B, n_p, 3), device=dev, dtype=torch.float32)
-        eng.check(eng.lib.ag_train_step(
-            eng.ctx, current_stream(dev), ptr(state), ptr(attrs), ptr(action), ptr(phys), ptr(group), group.shape[2],
-            ptr(edges.recv), ptr(edges.send), ptr(edges.row_ptr), ptr(edges.n_edges), edges.edge_cap, B, N, n_p, self._w_arr,
-            nf, ptr(fut), ptr(eef), ptr(act_f), int(self.store_rest_state), max(1, int(max_edges)), int(want_grad), self._g_arr,
-            ptr(self._loss), ptr(pred), ptr(self._status)))
-        self.last_pred = pred
-        return self._loss[nf].clone()
+        args = (eng.ctx, current_stream(dev), ptr(state), ptr(attrs), ptr(action), ptr(phys), ptr(group), group.shape[2],
+                ptr(edges.recv), ptr(edges.send), ptr(edges.row_ptr), ptr(edges.n_edges), edges.edge_cap, B, N, n_p, self._w_arr,
+                nf, ptr(fut), ptr(eef), ptr(act_f), int(self.store_rest_state), max(1, int(max_edges)), int(want_grad), self._g_arr,
+                ptr(self._loss), ptr(pred), ptr(self._status))
+        if total is None:
+            eng.check(eng.lib.ag_train_step(*args))
+            self.last_pred = pred
+            return self._loss[nf].clone()
+        before = self._loss[:nf].clone() if accumulate else None
+        eng.check(eng.lib.ag_train_step_part(*args, int(total), int(accumulate)))
+        self.last_pred = self.last_pred + [pred] if accumulate else [pred]
+        if not accumulate:
+            return self._loss[nf].clone()
+        return (self._loss[:nf].double() - before.double()).sum().float()      # what this part added to the running loss vector
+
+    def _adam(self):
+        self._step += 1
+        h, eng = self.hyper, self.engine
+        eng.check(eng.lib.ag_adam_step(eng.ctx, current_stream(self.device), self._w_arr, self._g_arr, self._m_arr, self._v_arr,
+                                       self._step, h["lr"], h["betas"][0], h["betas"][1], h["eps"], h["weight_decay"],
+                                       ptr(self._status)))
+
+    def accumulate(self, data, max_edges=None, total=None):
+        """Enqueue one PART of an optimiser step: `data` as for step(), `total` the row count of the whole step (over every part,
+        and over every rank when the object has a group).  The first part of a step overwrites the gradients and the loss vector,
+        later parts add to them.  `total` may be left out on the first part only (it is then this part's rows, or global_rows) and
+        must be the same on every part; a ValueError is raised before anything is enqueued.  max_edges bounds THIS part's graphs.
+        Returns this part's share of loss_sum as a 0-d device tensor (for a later part: what it added to the running fp32 loss
+        vector); .last_pred is a list with one (n_future, B_part, n_p, 3) tensor per part."""
+        if total is None and not self._parts.open:
+            total = self.global_rows
+        total, acc = self._parts.add(data["state"].shape[0], total)
+        return self._run(data, max_edges, True, total=total, accumulate=acc)
+
+    def _all_reduce(self):
+        import torch.distributed as dist
+        g = None if self.group is True else self.group
+        dist.all_reduce(self._grad_flat, op=dist.ReduceOp.SUM, group=g)
+        dist.all_reduce(self._loss, op=dist.ReduceOp.SUM, group=g)
+        self._flag.copy_(self._status[:1])
+        dist.all_reduce(self._flag, op=dist.ReduceOp.MAX, group=g)
+        self._status[:1].copy_(self._flag)
+
+    def apply(self):
+        """Close the step that accumulate() opened: the rows given must add up to `total` (a host comparison; with a group, at
+        most `total`), then the all-reduce over the group if there is one, ag_adam_step and the step counter, as in step().
+        Returns the full loss_sum as a 0-d device tensor."""
+        self._parts.close()
+        if self.group is not None:
+            self._all_reduce()
+        self._adam()
+        return self._loss[self.n_future].clone()
+
+    def step_parts(self, parts, max_edges=None):
+        """One optimiser step over the dicts in `parts`: accumulate() each with total = the sum of their rows (global_rows with a
+        group), then apply().  max_edges: one bound for all, or a list with one bound per part.  That is the way to train on a
+        batch of mixed graph sizes without padding every graph to the largest: sort the graphs by edge count, split them into a
+        few buckets, and pass each bucket's own bound - the edge-side GEMMs of a bucket then run over its bound, not the batch's.
+        Returns loss_sum (0-d device tensor)."""
+        parts = list(parts)
+        bounds = list(max_edges) if isinstance(max_edges, (list, tuple)) else [max_edges] * len(parts)
+        if len(bounds) != len(parts) or not parts:
+            raise ValueError(f"TrainStep.step_parts: {len(parts)} parts, {len(bounds)} max_edges bounds")
+        self._parts.forbid_open("step_parts")
+        total = self.global_rows if self.group is not None else sum(int(d["state"].shape[0]) for d in parts)
+        if total is None:
+            raise ValueError("TrainStep.step_parts: a data-parallel object needs global_rows")
+        for d, k in zip(parts, bounds):
+            self.accumulate(d, max_edges=k, total=total)
+        return self.apply()
 
     def step(self, data, max_edges=None):
         """One training iteration on `data` (the dict train.py passes to model(**data): state, attrs, p_instance, action,
@@ -126,13 +264,13 @@ class TrainStep:
         Returns loss_sum as a 0-d DEVICE tensor.  max_edges: the caller's bound on the largest edge count of the batch (a data
         loader knows it: it built the edges); with it the call only enqueues.  None reads edges.n_edges.max() back once, which is
         then the step's only wait.  A batch with a graph beyond max_edges (or the EdgeList's capacity) is skipped on the device -
-        weights, m and v stay as they were - and check() reports it."""
+        weights, m and v stay as they were - and check() reports it.  Raises inside a step that accumulate() opened.  With a
+        group: this rank's shard of a step of global_rows rows (= step_parts([data]))."""
+        self._parts.forbid_open("step")
+        if self.group is not None:
+            return self.step_parts([data], max_edges=max_edges)
         loss = self._run(data, max_edges, True)
-        self._step += 1
-        h, eng = self.hyper, self.engine
-        eng.check(eng.lib.ag_adam_step(eng.ctx, current_stream(self.device), self._w_arr, self._g_arr, self._m_arr, self._v_arr,
-                                       self._step, h["lr"], h["betas"][0], h["betas"][1], h["eps"], h["weight_decay"],
-                                       ptr(self._status)))
+        self._adam()
         return loss
 
     def evaluate(self, data, max_edges=None):
@@ -140,6 +278,7 @@ class TrainStep:
         predictions are in .last_pred (n_future, B, n_p, 3).  A batch with a graph beyond max_edges raises the same sticky flag as in
         step(): its loss is then that of the guarded (empty) graph, and every following step() is skipped until check() has
         reported it."""
+        self._parts.forbid_open("evaluate")        # it would overwrite the running loss vector
         return self._run(data, max_edges, False)
 
     def check(self):

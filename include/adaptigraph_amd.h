@@ -30,7 +30,7 @@
  *       ag_ctx_load_weights, ag_ctx_set_precision     always (host repack + copies)
  *       ag_forward, ag_rollout                        once, at the end: they return the overflow verdict (AG_ERR_MAX_NR)
  *       ag_backward, ag_backward_inputs               at the start (edge counts) and at the end
- *       ag_ctx_load_weights_device, ag_adam_step, ag_train_step, ag_ppm_grad_step, ag_ppm_adam_step   NEVER: they only enqueue on the caller's stream; an overflowed
+ *       ag_ctx_load_weights_device, ag_adam_step, ag_train_step, ag_train_step_part, ag_ppm_grad_step, ag_ppm_adam_step   NEVER: they only enqueue on the caller's stream; an overflowed
  *           graph is reported in device memory (d_status), which the caller reads when it chooses to
  *       ag_rollout_work                               for its plan (and a base rollout, if none is kept): it returns host numbers
  *       ag_ctx_rollout_counts (after a device-planned call without prefix sharing), ag_ctx_share_counts   wait for the device
@@ -505,6 +505,25 @@ int ag_mppi_clip(ag_ctx* ctx, void* stream, const float* d_in, const float* d_lo
 int ag_ctx_set_profiling(ag_ctx* ctx, int32_t family_mask);
 int ag_ctx_kernel_stats(ag_ctx* ctx, const char* kernel, double* out_total_ms, int64_t* out_launches);
 int ag_ctx_reset_stats(ag_ctx* ctx);
+
+/* ag_train_step on one PART of an optimiser step (a micro-batch of this rank, or this rank's share of a data-parallel batch):
+ * every argument of ag_train_step in the same order, then
+ *   B_total     rows of the whole step over all parts and ranks (>= B, else AG_ERR_INVALID).  The MSE mean and its gradient
+ *               divide by B_total * n_p * 3 instead of B * n_p * 3 (n_p is the same in every part), so d_loss and d_grad_w are
+ *               this part's share of the full batch's: the shares of the parts sum to the one-call values.
+ *   accumulate  0: d_grad_w[22] and d_loss[0..n_future] are overwritten (the first part of a step); != 0: they hold the earlier
+ *               parts' sums and are added to.  The old fp32 value joins the fixed-order fp64 sum of each weight-gradient
+ *               reduction (and of each step's MSE) before its one rounding: no second rounding, no float atomics, no extra pass.
+ *               d_loss[n_future] is again the fp32 sum of d_loss[0..n_future-1] in step order.  d_pred is this part's own.
+ * d_status[0] stays the sticky atomic max: an overflowed graph in any part makes the following ag_adam_step skip.
+ * ag_train_step is this call with B_total = B and accumulate = 0 (one implementation, the same bits).  Enqueue only. */
+int ag_train_step_part(ag_ctx* ctx, void* stream, const float* d_state, const float* d_attrs, const float* d_action,
+                       const float* d_phys, const float* d_group, int32_t n_inst, const int32_t* d_recv, const int32_t* d_send,
+                       const int32_t* d_row_ptr, const int32_t* d_n_edges, int32_t edge_cap, int32_t B, int32_t N, int32_t n_p,
+                       const float* const* d_w, int32_t n_future, const float* d_state_future, const float* d_eef_future,
+                       const float* d_action_future, int32_t store_rest_state, int32_t edge_rows, int32_t want_grad,
+                       float* const* d_grad_w, float* d_loss, float* d_pred, int32_t* d_status, int32_t B_total,
+                       int32_t accumulate);
 
 #ifdef __cplusplus
 }

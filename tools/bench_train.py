@@ -15,6 +15,11 @@ That the fused step really does not wait is what tests/test_gpu_train_step.py::t
 
   python tools/bench_train.py [--rounds 5] [--iters 5] [--warmup 3] [--out FILE]
   python tools/bench_train.py --only engine --rounds 1 --iters 3    (e.g. under rocprofv3 --kernel-trace --stats)
+  python tools/bench_train.py --parts 1,2,4 --out FILE
+      the parts leg INSTEAD of the three variants: TrainStep.step on the batch (the one-call step, the base every other figure
+      is compared with) alternated in the same process with the same batch as K equal parts through accumulate ... apply, for
+      every K given; and a mixed-size batch (half the graphs built with topk 10, half with topk 5) as one call with the common
+      max_edges against two buckets with their own.  --parts 4 --no-mixed --only-parts under rocprofv3 gives the 4-part kernel table.
 """
 import argparse
 import json
@@ -36,7 +41,7 @@ CFG = dict(verbose=False, nf_particle=150, nf_relation=150, nf_effect=150, nf_ph
            rel_distance_dim=3, rel_density_dim=0)
 
 
-def make_batch(dev, B=128, n_p=100, n_his=4, seed=0):
+def make_batch(dev, B=128, n_p=100, n_his=4, seed=0, topk=10):
     """A rope batch shaped like DynDataset's (fps radius ~0.2, adjacency radius 0.5, rope.yaml)."""
     rng = np.random.default_rng(seed)
     N = n_p + 1
@@ -56,7 +61,7 @@ def make_batch(dev, B=128, n_p=100, n_his=4, seed=0):
     mask = torch.ones(B, N, dtype=torch.bool, device=dev)
     tool = torch.zeros(B, N, dtype=torch.bool, device=dev)
     tool[:, n_p:] = True
-    edges = ag.construct_edges_index(tt(state[:, -1]), 0.5, mask, tool, topk=10, edge_cap=1000)
+    edges = ag.construct_edges_index(tt(state[:, -1]), 0.5, mask, tool, topk=topk, edge_cap=1000)
     ne = edges.n_edges.cpu().numpy()
     assert ne.max() <= 1000, ne.max()
     future = state[:, -1:, :n_p] + rng.normal(0, 0.02, (B, 3, n_p, 3))
@@ -96,6 +101,103 @@ def fused_variant(dev, data, W):
     def it():
         return ts.step(batch, max_edges=max_edges)
     return it
+
+
+BATCH_KEYS = ("state", "attrs", "action", "p_instance", "phys_physics_param", "state_future", "eef_future", "action_future")
+
+
+def slice_batch(data, lo, hi):
+    """Graphs [lo, hi) of a make_batch dict as a TrainStep data dict, and their largest edge count."""
+    from adaptigraph_amd.graph import EdgeList
+    e = data["edges"]
+    d = {k: data[k][lo:hi].contiguous() for k in BATCH_KEYS}
+    d["edges"] = EdgeList(e.recv[lo:hi].contiguous(), e.send[lo:hi].contiguous(), e.row_ptr[lo:hi].contiguous(),
+                          e.n_edges[lo:hi].contiguous(), e.N)
+    return d, int(data["ne"][lo:hi].max())
+
+
+def concat_batches(a, b):
+    """Two make_batch dicts (same N and edge capacity) as one batch, a's graphs first."""
+    from adaptigraph_amd.graph import EdgeList
+    d = {k: torch.cat([a[k], b[k]]) for k in BATCH_KEYS}
+    ea, eb = a["edges"], b["edges"]
+    d["edges"] = EdgeList(*[torch.cat([getattr(ea, k), getattr(eb, k)]) for k in ("recv", "send", "row_ptr", "n_edges")], ea.N)
+    d["ne"], d["n_p"] = np.concatenate([a["ne"], b["ne"]]), a["n_p"]
+    return d
+
+
+def parts_variants(dev, data, W, ks, mixed):
+    """name -> (callable of one iteration, description).  Every leg has a TrainStep of its own from the same weights."""
+    def new_ts():
+        model = ag.DynamicsPredictor(CFG, {"material_index": {"rope": 0}, "rope": {"physics_params": [{"name": "s", "use": True}]}},
+                                     {"n_his": 4, "materials": ["rope"]}, dev)
+        model.load_state_dict({k: torch.from_numpy(v) for k, v in W.items()})
+        return ag.TrainStep(model.to(dev), lr=0.001, n_future=3)
+    B = data["attrs"].shape[0]
+    out = {}
+    whole, bound = slice_batch(data, 0, B)
+    ts0 = new_ts()
+    out["step"] = (lambda: ts0.step(whole, max_edges=bound), f"TrainStep.step, 1 x {B}, max_edges {bound}")
+    for k in ks:
+        cuts = [slice_batch(data, i * B // k, (i + 1) * B // k) for i in range(k)]
+        ts = new_ts()
+        out[f"parts_{k}"] = (lambda ts=ts, cuts=cuts: ts.step_parts([c[0] for c in cuts], max_edges=[c[1] for c in cuts]),
+                             f"accumulate x {k} + apply, {k} x {B // k}, max_edges {[c[1] for c in cuts]}")
+    if mixed:
+        a, b = make_batch(dev, B=B // 2, seed=1, topk=10), make_batch(dev, B=B - B // 2, seed=2, topk=5)
+        mix = concat_batches(a, b)
+        whole_m, bound_m = slice_batch(mix, 0, B)
+        buckets = [slice_batch(mix, 0, B // 2), slice_batch(mix, B // 2, B)]
+        ts1, ts2 = new_ts(), new_ts()
+        out["mixed_common"] = (lambda: ts1.step(whole_m, max_edges=bound_m),
+                               f"mixed batch (topk 10 | topk 5) as one call, max_edges {bound_m}, mean edges {float(mix['ne'].mean()):.1f}")
+        out["mixed_buckets"] = (lambda: ts2.step_parts([c[0] for c in buckets], max_edges=[c[1] for c in buckets]),
+                                f"the same batch as two buckets, max_edges {[c[1] for c in buckets]}")
+    return out
+
+
+def run_parts(a, dev, data, W):
+    ks = [int(x) for x in a.parts.split(",")]
+    legs = parts_variants(dev, data, W, ks, not a.no_mixed)
+    if a.only_parts:
+        legs = {k: v for k, v in legs.items() if k.startswith("parts_")}
+    for fn, _ in legs.values():
+        for _ in range(a.warmup):
+            fn()
+    torch.cuda.synchronize()
+    times, losses = {k: [] for k in legs}, {}
+    for _ in range(a.rounds):
+        for k, (fn, _) in legs.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(a.iters):
+                loss = fn()
+            torch.cuda.synchronize()
+            times[k].append((time.perf_counter() - t0) * 1e3 / a.iters)
+            losses[k] = float(loss)
+    res = {"tool": "bench_train --parts", "device": torch.cuda.get_device_name(dev), "rounds": a.rounds, "iters_per_round": a.iters,
+           "config": dict(B=int(data["attrs"].shape[0]), N=int(data["attrs"].shape[1]), n_p=data["n_p"], n_future=3, pstep=3,
+                          optimizer="Adam lr 1e-3", edges_mean=float(data["ne"].mean()), edges_max=int(data["ne"].max())),
+           "note": "every leg in one process, alternated round by round; ms per optimiser step, median over the rounds; "
+                   "'step' is the one-call TrainStep.step (ag_train_step + ag_adam_step), the base of every ratio"}
+    for k, (_, what) in legs.items():
+        r = times[k]
+        res[k] = {"what": what, "ms_per_iter_median": float(np.median(r)), "ms_per_iter_rounds": [round(x, 3) for x in r],
+                  "ms_min": min(r), "ms_max": max(r), "last_loss": losses[k]}
+    if "step" in res:
+        base = res["step"]
+        for k in legs:
+            if k.startswith("parts_"):
+                res[k]["over_step"] = res[k]["ms_per_iter_median"] / base["ms_per_iter_median"]
+        if "parts_1" in res:
+            res["parts_1"]["inside_step_spread"] = bool(base["ms_min"] <= res["parts_1"]["ms_per_iter_median"] <= base["ms_max"])
+    if "mixed_common" in res and "mixed_buckets" in res:
+        res["mixed_buckets_over_common"] = res["mixed_buckets"]["ms_per_iter_median"] / res["mixed_common"]["ms_per_iter_median"]
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
 
 
 WAITS = {"ag_forward": 1, "ag_backward": 2, "ag_ctx_load_weights": 1, "ag_train_step": 0, "ag_adam_step": 0,
@@ -156,10 +258,15 @@ def main():
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--only", choices=["engine", "fused", "torch"], default=None)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--parts", default=None, help="K[,K...]: the parts leg (see the module docstring)")
+    ap.add_argument("--no-mixed", action="store_true", help="with --parts: leave the mixed-size batch out")
+    ap.add_argument("--only-parts", action="store_true", help="with --parts: the K-part legs alone (for a kernel trace)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     data = make_batch(dev, B=a.batch)
     W = TR.make_weights(0)
+    if a.parts:
+        return run_parts(a, dev, data, W)
     count_calls()
     makers = {"engine": engine_variant, "fused": fused_variant, "torch": torch_variant}
     variants = {k: mk(dev, data, W) for k, mk in makers.items() if a.only in (None, k)}

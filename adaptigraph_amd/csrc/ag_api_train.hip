@@ -1,0 +1,399 @@
+// C-ABI, training side (see include/adaptigraph_amd.h): the backward pass, device-side weight loading and Adam, the chained
+// training step and the physics-parameter fit.  Host orchestration only; context and shared helpers: ag_host.h.
+#include "ag_host.h"
+
+using namespace ag;
+
+namespace {
+
+// Launch chunk and workspace of train_backward_chunk (ag_backward_inputs, ag_train_step_part, ag_ppm_grad_step): the context's
+// chunk if set, else as many candidates as fit a 4-GiB workspace.  want_slab: the split-K slab of the weight gradients.
+struct BackwardWork {
+    int Bb = 1; size_t wf = 0, wi = 0; bool want_slab = false;
+    float* wsf = nullptr; float* slab = nullptr; int* wsi = nullptr;
+    BackwardWork() = default;                                // no backward asked for: carves nothing
+    BackwardWork(const ag_ctx* c, int B, int N, int Ep, int n_his, int pstep, bool want_slab_) : want_slab(want_slab_) {
+        const size_t per_cand = train_work_floats(1, N, Ep, n_his, pstep) * 4 + train_work_ints(1, N, Ep) * 4;
+        Bb = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, (size_t(4) << 30) / per_cand));
+        if (c->chunk > 0) Bb = std::min(Bb, (int)c->chunk);
+        else if (c->opt.chunk > 0) Bb = std::min(Bb, c->opt.chunk);
+        wf = train_work_floats(Bb, N, Ep, n_his, pstep); wi = train_work_ints(Bb, N, Ep);
+    }
+    void carve(Slab& s) { wsf = s.take<float>(wf); slab = want_slab ? s.take<float>(train_slab_floats()) : nullptr; wsi = s.take<int>(wi); }
+};
+
+// the three weight images from 22 plain device tensors, by kernels on `st`; no host copy, no wait (first call: allocations)
+int load_weights_device(ag_ctx* c, hipStream_t st, const float* const* d_w) {
+    const bool his4 = c->dims.n_his == 4;
+    if (his4 && !c->d_wb3) {
+        HIPCHK(c, dev_alloc(c, reinterpret_cast<void**>(&c->d_wb3), (size_t)B3_PHASES * B3_PHASE_BYTES));
+        HIPCHK(c, hipMemset(c->d_wb3, 0, (size_t)B3_PHASES * B3_PHASE_BYTES));
+    }
+    if (his4 && !c->d_wlat) {
+        HIPCHK(c, dev_alloc(c, reinterpret_cast<void**>(&c->d_wlat), lat_weights_floats() * 4));
+        HIPCHK(c, hipMemset(c->d_wlat, 0, lat_weights_floats() * 4));
+    }
+    HIPCHK(c, launch_pack_weights(c->dims.rel_dim, d_w, c->d_w, his4 ? reinterpret_cast<uint16_t*>(c->d_wb3) : nullptr,
+                                  his4 ? c->d_wlat : nullptr, st));
+    c->have_w = true;
+    ++c->weights_version;
+    return enqueue_self_rows(c, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+int ag_backward(ag_ctx* c, void* stream, const float* d_state, const float* d_attrs, const float* d_action,
+                const float* d_phys, const float* d_group, int32_t n_inst, const int32_t* d_recv, const int32_t* d_send,
+                const int32_t* d_row_ptr, const int32_t* d_n_edges, int32_t edge_cap, int32_t B, int32_t N, int32_t n_p,
+                const float* const* d_w, const float* d_grad_pos, const float* d_grad_motion, float* d_grad_state,
+                float* const* d_grad_w) {
+    return ag_backward_inputs(c, stream, d_state, d_attrs, d_action, d_phys, d_group, n_inst, d_recv, d_send, d_row_ptr, d_n_edges,
+                              edge_cap, B, N, n_p, d_w, d_grad_pos, d_grad_motion, d_grad_state, d_grad_w, nullptr, nullptr);
+}
+
+int ag_backward_inputs(ag_ctx* c, void* stream, const float* d_state, const float* d_attrs, const float* d_action,
+                       const float* d_phys, const float* d_group, int32_t n_inst, const int32_t* d_recv, const int32_t* d_send,
+                       const int32_t* d_row_ptr, const int32_t* d_n_edges, int32_t edge_cap, int32_t B, int32_t N, int32_t n_p,
+                       const float* const* d_w, const float* d_grad_pos, const float* d_grad_motion, float* d_grad_state,
+                       float* const* d_grad_w, float* d_grad_phys, float* d_grad_action) {
+    if (!c) return AG_ERR_INVALID;
+    if (!d_state || !d_attrs || !d_action || !d_phys || !d_group || !d_recv || !d_send || !d_row_ptr || !d_n_edges || !d_w)
+        return fail(c, AG_ERR_INVALID, "ag_backward: null pointer");
+    for (int k = 0; k < 22; ++k)
+        if (!d_w[k]) return fail(c, AG_ERR_INVALID, "ag_backward: null parameter %d", k);
+    if (B < 1 || N < 1 || n_p < 1 || n_p > N || n_inst < 1 || edge_cap < 1)
+        return fail(c, AG_ERR_INVALID, "ag_backward: bad sizes B=%d N=%d n_p=%d n_inst=%d edge_cap=%d", B, N, n_p, n_inst, edge_cap);
+    if (c->dims.nf != NF || c->dims.in_dim != IN_DIM || c->dims.rel_dim != 5 + 3 * c->dims.n_his || c->dims.pstep < 1 || c->dims.pstep > 7)
+        return fail(c, AG_ERR_UNSUPPORTED, "ag_backward: nf %d, in_dim %d, rel_dim %d, pstep %d not served", c->dims.nf, c->dims.in_dim,
+                    c->dims.rel_dim, c->dims.pstep);
+    SlotGuard call;
+    int rc = begin_call(c, stream, call);
+    if (rc) return rc;
+    hipStream_t st = call.st; CallSlot* sl = call.sl;
+    // the edge counts size the workspace (rows per graph = the largest count) and carry the overflow verdict
+    std::vector<int32_t> ne((size_t)B);
+    HIPCHK(c, hipMemcpyAsync(ne.data(), d_n_edges, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    int emax = 0;
+    for (int v : ne) emax = std::max(emax, v);
+    if (emax > edge_cap) return fail(c, AG_ERR_MAX_NR, "Exceeds max dims: a graph had %d edges, edge_cap=%d", emax, edge_cap);
+    TrainArgs t{};
+    t.state = d_state; t.attrs = d_attrs; t.action = d_action; t.phys = d_phys; t.group = d_group; t.n_inst = n_inst;
+    t.recv = d_recv; t.send = d_send; t.row_ptr = d_row_ptr; t.n_edges = d_n_edges; t.edge_cap = edge_cap;
+    t.B = B; t.N = N; t.n_p = n_p; t.n_his = c->dims.n_his; t.pstep = c->dims.pstep; t.clamp = c->dims.motion_clamp;
+    t.Ep = std::max(1, emax);
+    t.dpos = d_grad_pos; t.dmot = d_grad_motion; t.dstate = d_grad_state;
+    t.dphys = d_grad_phys; t.daction = d_grad_action;
+    for (int k = 0; k < 22 && d_grad_w; ++k) t.want_w = t.want_w || d_grad_w[k] != nullptr;   // else: data gradients only
+    BackwardWork bw(c, B, N, t.Ep, t.n_his, t.pstep, true);
+    int n22[22]; float* acc[22];
+    weight_tensor_sizes(c->dims.rel_dim, n22);
+    rc = carve_slab(c, *sl, [&](Slab& s) { bw.carve(s); for (int k = 0; k < 22; ++k) acc[k] = s.take<float>((size_t)n22[k]); });
+    if (rc) return rc;
+    for (int k = 0; k < 22; ++k) {
+        HIPCHK(c, hipMemsetAsync(acc[k], 0, (size_t)n22[k] * 4, st));
+        t.w[k] = d_w[k]; t.g[k] = acc[k];
+    }
+    for (int b0 = 0; b0 < B; b0 += bw.Bb)
+        HIPCHK(c, train_backward_chunk(t, b0, std::min(bw.Bb, B - b0), bw.wsf, bw.wsi, bw.slab, st));
+    for (int k = 0; k < 22 && d_grad_w; ++k)
+        if (d_grad_w[k]) HIPCHK(c, hipMemcpyAsync(d_grad_w[k], acc[k], (size_t)n22[k] * 4, hipMemcpyDeviceToDevice, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    return AG_OK;
+}
+
+int ag_ctx_load_weights_device(ag_ctx* c, void* stream, const float* const* d_w) {
+    if (!c) return AG_ERR_INVALID;
+    if (!d_w) return fail(c, AG_ERR_INVALID, "ag_ctx_load_weights_device: null pointer");
+    for (int k = 0; k < 22; ++k)
+        if (!d_w[k]) return fail(c, AG_ERR_INVALID, "ag_ctx_load_weights_device: weight tensor %d is null", k);
+    SlotGuard call;
+    if (int rc = begin_call(c, stream, call)) return rc;
+    return load_weights_device(c, call.st, d_w);
+}
+
+int ag_adam_step(ag_ctx* c, void* stream, float* const* d_w, const float* const* d_grad, float* const* d_exp_avg,
+                 float* const* d_exp_avg_sq, int32_t step, double lr, double beta1, double beta2, double eps, double weight_decay,
+                 int32_t* d_status) {
+    if (!c) return AG_ERR_INVALID;
+    if (!d_w || !d_grad || !d_exp_avg || !d_exp_avg_sq || !d_status) return fail(c, AG_ERR_INVALID, "ag_adam_step: null pointer");
+    for (int k = 0; k < 22; ++k)
+        if (!d_w[k] || !d_grad[k] || !d_exp_avg[k] || !d_exp_avg_sq[k]) return fail(c, AG_ERR_INVALID, "ag_adam_step: null tensor %d", k);
+    if (step < 1 || !(lr >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !(weight_decay >= 0.0))
+        return fail(c, AG_ERR_INVALID, "ag_adam_step: step %d, lr %g, betas (%g, %g), eps %g, weight_decay %g", step, lr, beta1, beta2, eps,
+                    weight_decay);
+    SlotGuard call;
+    if (int rc = begin_call(c, stream, call)) return rc;
+    hipStream_t st = call.st;
+    AdamArgs a{};
+    weight_tensor_sizes(c->dims.rel_dim, a.n);
+    for (int k = 0; k < 22; ++k) { a.w[k] = d_w[k]; a.g[k] = d_grad[k]; a.m[k] = d_exp_avg[k]; a.v[k] = d_exp_avg_sq[k]; }
+    // torch.optim.Adam forms the bias corrections and the step size as Python floats (doubles); a kernel sees them rounded to fp32
+    const double bc1 = 1.0 - std::pow(beta1, (double)step), bc2 = 1.0 - std::pow(beta2, (double)step);
+    a.wd = (float)weight_decay; a.one_minus_b1 = (float)(1.0 - beta1); a.b2 = (float)beta2; a.one_minus_b2 = (float)(1.0 - beta2);
+    a.bc2_sqrt = (float)std::sqrt(bc2); a.eps = (float)eps; a.neg_step_size = (float)(-(lr / bc1));
+    a.status = d_status;
+    HIPCHK(c, launch_adam(a, st));
+    return load_weights_device(c, st, d_w);
+}
+
+int ag_train_step(ag_ctx* c, void* stream, const float* d_state, const float* d_attrs, const float* d_action, const float* d_phys,
+                  const float* d_group, int32_t n_inst, const int32_t* d_recv, const int32_t* d_send, const int32_t* d_row_ptr,
+                  const int32_t* d_n_edges, int32_t edge_cap, int32_t B, int32_t N, int32_t n_p, const float* const* d_w,
+                  int32_t n_future, const float* d_state_future, const float* d_eef_future, const float* d_action_future,
+                  int32_t store_rest_state, int32_t edge_rows, int32_t want_grad, float* const* d_grad_w, float* d_loss,
+                  float* d_pred, int32_t* d_status) {
+    return ag_train_step_part(c, stream, d_state, d_attrs, d_action, d_phys, d_group, n_inst, d_recv, d_send, d_row_ptr, d_n_edges,
+                              edge_cap, B, N, n_p, d_w, n_future, d_state_future, d_eef_future, d_action_future, store_rest_state,
+                              edge_rows, want_grad, d_grad_w, d_loss, d_pred, d_status, B, 0);
+}
+
+// B_total = B, accumulate = 0 is ag_train_step: the same launches with the same arguments, so the same bits
+int ag_train_step_part(ag_ctx* c, void* stream, const float* d_state, const float* d_attrs, const float* d_action, const float* d_phys,
+                       const float* d_group, int32_t n_inst, const int32_t* d_recv, const int32_t* d_send, const int32_t* d_row_ptr,
+                       const int32_t* d_n_edges, int32_t edge_cap, int32_t B, int32_t N, int32_t n_p, const float* const* d_w,
+                       int32_t n_future, const float* d_state_future, const float* d_eef_future, const float* d_action_future,
+                       int32_t store_rest_state, int32_t edge_rows, int32_t want_grad, float* const* d_grad_w, float* d_loss,
+                       float* d_pred, int32_t* d_status, int32_t B_total, int32_t accumulate) {
+    if (!c) return AG_ERR_INVALID;
+    if (!c->have_w) return fail(c, AG_ERR_NO_WEIGHTS, "ag_train_step before ag_ctx_load_weights / ag_ctx_load_weights_device");
+    if (!d_state || !d_attrs || !d_action || !d_phys || !d_group || !d_recv || !d_send || !d_row_ptr || !d_n_edges || !d_state_future ||
+        !d_loss || !d_status)
+        return fail(c, AG_ERR_INVALID, "ag_train_step: null pointer");
+    if (B < 1 || N < 1 || n_p < 1 || n_p > N || n_inst < 1 || edge_cap < 1 || edge_rows < 1 || n_future < 1)
+        return fail(c, AG_ERR_INVALID, "ag_train_step: bad sizes B=%d N=%d n_p=%d n_inst=%d edge_cap=%d edge_rows=%d n_future=%d", B, N, n_p,
+                    n_inst, edge_cap, edge_rows, n_future);
+    if (B_total < B) return fail(c, AG_ERR_INVALID, "ag_train_step_part: B_total=%d is below B=%d", B_total, B);
+    if (n_future > 1 && (!d_eef_future || !d_action_future)) return fail(c, AG_ERR_INVALID, "ag_train_step: n_future > 1 needs eef_future and action_future");
+    if (want_grad) {
+        if (!d_w || !d_grad_w) return fail(c, AG_ERR_INVALID, "ag_train_step: want_grad needs d_w and d_grad_w");
+        for (int k = 0; k < 22; ++k)
+            if (!d_w[k] || !d_grad_w[k]) return fail(c, AG_ERR_INVALID, "ag_train_step: null parameter or gradient tensor %d", k);
+        if (c->dims.pstep > 7) return fail(c, AG_ERR_UNSUPPORTED, "ag_train_step: pstep %d not served by the backward", c->dims.pstep);
+    }
+    SlotGuard call;
+    int rc = begin_call(c, stream, call);
+    if (rc) return rc;
+    hipStream_t st = call.st; CallSlot* sl = call.sl;
+    const int n_his = c->dims.n_his, rest = store_rest_state ? 1 : 0;
+    const int cap = std::min(edge_cap, edge_rows);            // a graph beyond it is presented empty and reported in d_status[0]
+    // forward workspace and launch chunk exactly as ag_forward's: the same kernels are chosen, the predictions are its bits
+    ForwardFrame f(c, B, N, n_inst, edge_cap, n_p, B);
+    // backward: edge rows per graph = the caller's bound, launch chunk as ag_backward's
+    TrainArgs t{};
+    t.attrs = d_attrs; t.phys = d_phys; t.group = d_group; t.n_inst = n_inst;
+    t.recv = d_recv; t.send = d_send; t.row_ptr = d_row_ptr; t.edge_cap = edge_cap;
+    t.B = B; t.N = N; t.n_p = n_p; t.n_his = n_his; t.pstep = c->dims.pstep; t.clamp = c->dims.motion_clamp;
+    t.Ep = cap; t.want_w = true; t.wide = accumulate != 0;
+    BackwardWork bw;
+    if (want_grad) bw = BackwardWork(c, B, N, t.Ep, n_his, t.pstep, true);
+    const size_t n_state = (size_t)B * n_his * N * 3, n_act = (size_t)B * N * 3, n_pred = (size_t)B * n_p * 3;
+    float* S = nullptr; float* A = nullptr; float* P = nullptr; float* motion = nullptr; double* part = nullptr;
+    float* dpos = nullptr; float* D[2] = {nullptr, nullptr};
+    rc = carve_slab(c, *sl, [&](Slab& s) {
+        f.carve(c, s);
+        S = s.take<float>((size_t)(n_future - 1) * n_state);     // model inputs of steps 1.. (step 0: the caller's)
+        A = s.take<float>((size_t)(n_future - 1) * n_act);
+        P = d_pred ? d_pred : s.take<float>((size_t)n_future * n_pred);
+        motion = s.take<float>(n_pred);
+        part = s.take<double>(train_glue_doubles());
+        if (want_grad) {
+            dpos = s.take<float>(n_pred);
+            if (n_future > 1) { D[0] = s.take<float>(n_state); D[1] = s.take<float>(n_state); }
+            bw.carve(s);
+        }
+    });
+    if (rc) return rc;
+    HIPCHK(c, launch_edge_guard(d_n_edges, B, cap, f.n_eff, d_status, st));
+    auto state_of = [&](int fi) { return fi == 0 ? d_state : S + (size_t)(fi - 1) * n_state; };
+    auto action_of = [&](int fi) { return fi == 0 ? d_action : A + (size_t)(fi - 1) * n_act; };
+    // ---- train.py:94-119: n_future chained forwards, MSE of each prediction, the next model input from it
+    for (int fi = 0; fi < n_future; ++fi) {
+        float* pred = P + (size_t)fi * n_pred;
+        rc = enqueue_forward(c, f, state_of(fi), d_attrs, action_of(fi), d_phys, d_group, d_recv, d_send, d_row_ptr, f.n_eff, B, pred,
+                             motion, st);
+        if (rc) return rc;
+        HIPCHK(c, launch_step_loss(pred, d_state_future, B, n_p, n_future, fi, B_total, accumulate ? 1 : 0, part, d_loss, st));
+        if (fi + 1 < n_future)
+            HIPCHK(c, launch_next_state(state_of(fi), pred, d_eef_future, d_action_future, B, N, n_p, n_his, n_future, fi, rest,
+                                        S + (size_t)fi * n_state, A + (size_t)fi * n_act, st));
+    }
+    if (!want_grad) return AG_OK;
+    // ---- train.py:122 loss_sum.backward(): last step first; the weight gradients accumulate in the caller's tensors in that order
+    int n22[22];
+    weight_tensor_sizes(c->dims.rel_dim, n22);
+    for (int k = 0; k < 22; ++k) {
+        if (!accumulate) HIPCHK(c, hipMemsetAsync(d_grad_w[k], 0, (size_t)n22[k] * 4, st));   // else: the earlier parts' sums stay
+        t.w[k] = d_w[k]; t.g[k] = d_grad_w[k];
+    }
+    t.n_edges = f.n_eff; t.dpos = dpos;
+    for (int fi = n_future - 1; fi >= 0; --fi) {
+        const float* dnext = fi + 1 < n_future ? D[1] : nullptr;     // total dLoss/dstate of step fi + 1
+        HIPCHK(c, launch_pred_grad(P + (size_t)fi * n_pred, d_state_future, dnext, B, N, n_p, n_his, n_future, fi, B_total, dpos, st));
+        t.state = state_of(fi); t.action = action_of(fi);
+        t.dstate = fi > 0 ? D[0] : nullptr;                          // step 0's input is data
+        for (int b0 = 0; b0 < B; b0 += bw.Bb) HIPCHK(c, train_backward_chunk(t, b0, std::min(bw.Bb, B - b0), bw.wsf, bw.wsi, bw.slab, st));
+        if (fi > 0) {
+            if (dnext) HIPCHK(c, launch_dstate_carry(D[0], dnext, B, N, n_his, rest, st));
+            std::swap(D[0], D[1]);
+        }
+    }
+    return AG_OK;
+}
+
+int ag_ppm_grad_step(ag_ctx* c, void* stream, const ag_rollout_params* p, const float* d_state0, const uint8_t* d_obj_mask,
+                     const float* d_eef_xz, const float* d_eef_delta, const int32_t* h_repeat, const int32_t* d_repeat,
+                     const float* d_phys, const float* d_obs, const uint8_t* d_obs_mask, int32_t N_t, const float* d_row_weight,
+                     const float* const* d_w, int32_t edge_rows, int32_t want_grad, float* d_state_seqs, float* d_err,
+                     float* d_grad_phys, int32_t* d_status) {
+    if (!c) return AG_ERR_INVALID;
+    if (!c->have_w) return fail(c, AG_ERR_NO_WEIGHTS, "ag_ppm_grad_step before ag_ctx_load_weights / ag_ctx_load_weights_device");
+    if (!p || !d_state0 || !d_obj_mask || !d_eef_xz || !d_eef_delta || !h_repeat || !d_repeat || !d_phys || !d_obs || !d_obs_mask ||
+        !d_state_seqs || !d_err || !d_status)
+        return fail(c, AG_ERR_INVALID, "ag_ppm_grad_step: null pointer");
+    const int B = p->B, N_o = p->N_o, M = p->M, N = N_o + M;
+    if (B < 1 || N_o < 1 || M < 0 || p->H != 1 || p->y_mode != 1 || N_t < 1 || edge_rows < 1 || p->max_nR < 1)
+        return fail(c, AG_ERR_INVALID, "ag_ppm_grad_step: bad sizes B=%d N_o=%d M=%d H=%d y_mode=%d N_t=%d edge_rows=%d max_nR=%d", B, N_o, M,
+                    p->H, p->y_mode, N_t, edge_rows, p->max_nR);
+    if ((size_t)N_o + (size_t)N_t > chamfer_max_points())
+        return fail(c, AG_ERR_UNSUPPORTED, "ag_ppm_grad_step: N_o+N_t=%d exceeds the chamfer LDS tile (%zu points)", N_o + N_t, chamfer_max_points());
+    if (int rc0 = check_topk(c, N, p->topk)) return rc0;
+    if (want_grad) {
+        if (!d_w || !d_grad_phys || !d_row_weight) return fail(c, AG_ERR_INVALID, "ag_ppm_grad_step: want_grad needs d_w, d_row_weight and d_grad_phys");
+        for (int k = 0; k < 22; ++k)
+            if (!d_w[k]) return fail(c, AG_ERR_INVALID, "ag_ppm_grad_step: null parameter tensor %d", k);
+        if (c->dims.pstep > 7) return fail(c, AG_ERR_UNSUPPORTED, "ag_ppm_grad_step: pstep %d not served by the backward", c->dims.pstep);
+    }
+    SlotGuard call;
+    int rc = begin_call(c, stream, call);
+    if (rc) return rc;
+    hipStream_t st = call.st; CallSlot* sl = call.sl;
+    const int n_his = c->dims.n_his;
+    // the step count and the live prefix of every step come from the host-resident repeat counts: no read-back
+    int S = 0;
+    for (int b = 0; b < B; ++b) S = std::max(S, (int)h_repeat[b]);
+    std::vector<int> live((size_t)S + 2, 0);                  // live[s] = rows [0, live[s]) hold every row with repeat >= s
+    for (int b = 0; b < B; ++b)
+        for (int s = 1; s <= std::min(S, (int)h_repeat[b]); ++s) live[s] = b + 1;
+    const int cap = std::min(p->max_nR, edge_rows);           // a graph beyond it is presented empty and reported in d_status[0]
+    ForwardFrame f(c, B, N, 1, cap, N_o, 0);                 // (guarded edge counts: per step, with the edge lists below)
+    const int slices = pick_slices(c, B, N), ell = edge_ell_stride(N, p->topk);
+    TrainArgs t{};
+    t.n_inst = 1; t.edge_cap = cap; t.N = N; t.n_p = N_o; t.n_his = n_his; t.pstep = c->dims.pstep; t.clamp = c->dims.motion_clamp;
+    t.Ep = cap; t.want_w = false;
+    BackwardWork bw;
+    if (want_grad) bw = BackwardWork(c, B, N, t.Ep, n_his, t.pstep, false);
+    // workspace: [forward | builder scratch | model inputs | per-step inputs and edge lists | chamfer and backward]
+    const size_t rows = (size_t)B * N, n_state = (size_t)B * n_his * N * 3, n_pred = (size_t)B * N_o * 3;
+    const size_t nS = want_grad ? (size_t)std::max(S, 1) : 2, nE = want_grad ? (size_t)std::max(S, 1) : 1;
+    EdgeArgs ea{};
+    PpmBufs pb{};
+    pb.B = B; pb.N_o = N_o; pb.M = M; pb.n_his = n_his;
+    pb.state0 = d_state0; pb.obj_mask = d_obj_mask; pb.eef_xz = d_eef_xz; pb.eef_delta = d_eef_delta; pb.phys = d_phys;
+    pb.repeat = d_repeat; pb.grip = p->gripper_offset; pb.grip_on = p->gripper_enable;
+    float* pred = nullptr; float* motion = nullptr; float* states = nullptr;
+    std::vector<int*> e_recv(nE), e_send(nE), e_rptr(nE), e_n(nE), e_eff(nE);
+    int* nn = nullptr; float* cntf = nullptr; float* gseq = nullptr; float* dpos = nullptr; float* D[2] = {nullptr, nullptr};
+    float* gphys = nullptr;
+    rc = carve_slab(c, *sl, [&](Slab& sb) {
+        f.carve(c, sb);
+        ea.ell = sb.take<int>(rows * (size_t)std::max(1, ell)); ea.deg = sb.take<int>(rows);
+        ea.slice_tot = sb.take<int>((size_t)B * slices); ea.cta_flag = sb.take<int>(B);
+        pb.attrs = sb.take<float>(rows * 2); pb.action = sb.take<float>(rows * 3); pb.group = sb.take<float>(rows);
+        pb.physN = sb.take<float>(rows); pb.mask = sb.take<uint8_t>(rows); pb.tool = sb.take<uint8_t>(rows);
+        pb.ymean = sb.take<float>(B); pb.cnt = sb.take<int>(B);
+        pred = sb.take<float>(n_pred); motion = sb.take<float>(n_pred);
+        states = sb.take<float>(nS * n_state);
+        for (size_t k = 0; k < nE; ++k) {
+            e_recv[k] = sb.take<int>((size_t)B * cap); e_send[k] = sb.take<int>((size_t)B * cap);
+            e_rptr[k] = sb.take<int>((size_t)B * (N + 1)); e_n[k] = sb.take<int>(B); e_eff[k] = sb.take<int>(B);
+        }
+        if (want_grad) {
+            nn = sb.take<int>((size_t)B * (N_o + N_t)); cntf = sb.take<float>((size_t)B * 2); gseq = sb.take<float>(n_pred);
+            dpos = sb.take<float>(n_pred); D[0] = sb.take<float>(n_state); D[1] = sb.take<float>(n_state);
+            gphys = sb.take<float>(rows); bw.carve(sb);
+        }
+    });
+    if (rc) return rc;
+    auto state_of = [&](int s) { return states + (want_grad ? (size_t)(s - 1) : (size_t)((s - 1) & 1)) * n_state; };
+    auto eslot = [&](int s) { return want_grad ? (size_t)(s - 1) : (size_t)0; };
+    ea.mask = pb.mask; ea.tool = pb.tool; ea.thr = p->adj_thresh; ea.N = N; ea.topk = p->topk; ea.cta = p->connect_tools_all ? 1 : 0;
+    ea.edge_cap = cap; ea.max_nR = cap; ea.slices = slices; ea.pos_bstride = (long)n_his * N * 3;
+    ea.block_min_rows = c->opt.edge_block_min;
+
+    // ---- forward_dynamics.py:225-372: the masked rollout, every step's model input and edge lists kept for the backward
+    HIPCHK(c, hipMemsetAsync(d_state_seqs, 0, n_pred * 4, st));
+    HIPCHK(c, launch_ppm_mean_y(pb, d_state0, B, st));
+    HIPCHK(c, launch_ppm_init(pb, state_of(1), st));
+    for (int s = 1; s <= S; ++s) {
+        const int L = live[s], Ln = live[s + 1];
+        const size_t k = eslot(s);
+        float* cur = state_of(s);
+        ea.pos = cur + (size_t)(n_his - 1) * N * 3; ea.B = L;
+        ea.recv = e_recv[k]; ea.send = e_send[k]; ea.row_ptr = e_rptr[k]; ea.n_edges = e_n[k];
+        HIPCHK(c, launch_edge_build(ea, st, prof_mark, c));
+        HIPCHK(c, launch_edge_guard(e_n[k], L, cap, e_eff[k], d_status, st));
+        rc = enqueue_forward(c, f, cur, pb.attrs, pb.action, pb.physN, pb.group, e_recv[k], e_send[k], e_rptr[k], e_eff[k], L, pred,
+                             motion, st);
+        if (rc) return rc;
+        if (Ln > 0) HIPCHK(c, launch_ppm_mean_y(pb, pred, Ln, st));
+        HIPCHK(c, launch_ppm_advance(pb, cur, pred, s, L, Ln, Ln > 0 ? state_of(s + 1) : cur, d_state_seqs, st));
+    }
+    // ---- the masked chamfer to the observed clouds (physics_param_optimizer.py:219-226)
+    { Scoped pr(c, FAM_COST);
+      HIPCHK(c, launch_chamfer(d_state_seqs, d_obs, d_obj_mask, d_obs_mask, B, N_o, N_t, B, d_err, st)); }
+    if (!want_grad) return AG_OK;
+    HIPCHK(c, hipMemsetAsync(d_grad_phys, 0, (size_t)B * N_o * 4, st));
+    { Scoped pr(c, FAM_COST);
+      HIPCHK(c, launch_chamfer_backward(d_state_seqs, d_obs, d_obj_mask, d_obs_mask, B, N_o, N_t, B, d_row_weight, nn, cntf, gseq, st)); }
+    // ---- backward through the chain, last step first; edges are constants
+    // (pb.cnt still holds the valid counts: a row's mask never changes)
+    for (int k = 0; k < 22; ++k) { t.w[k] = d_w[k]; t.g[k] = nullptr; }
+    t.attrs = pb.attrs; t.action = pb.action; t.phys = pb.physN; t.group = pb.group; t.dpos = dpos; t.dphys = gphys;
+    for (int s = S; s >= 1; --s) {
+        const int L = live[s], Ln = live[s + 1];
+        const size_t k = eslot(s);
+        HIPCHK(c, launch_ppm_pred_grad(pb, gseq, Ln > 0 ? D[1] : nullptr, s, L, Ln, dpos, st));
+        t.state = state_of(s); t.recv = e_recv[k]; t.send = e_send[k]; t.row_ptr = e_rptr[k]; t.n_edges = e_eff[k]; t.B = L;
+        t.dstate = s > 1 ? D[0] : nullptr;                      // step 1's input is data
+        // no split-K slab: want_w = false makes every linear_dw return before it touches one (wsf stands in for the pointer; a
+        // caller that turns want_w on must carve train_slab_floats() as ag_train_step does)
+        for (int b0 = 0; b0 < L; b0 += bw.Bb) HIPCHK(c, train_backward_chunk(t, b0, std::min(bw.Bb, L - b0), bw.wsf, bw.wsi, bw.wsf, st));
+        HIPCHK(c, launch_ppm_accum(gphys, L, N, N_o, d_grad_phys, st));
+        if (s > 1) {
+            if (Ln > 0) HIPCHK(c, launch_dstate_carry(D[0], D[1], Ln, N, n_his, 0, st));
+            std::swap(D[0], D[1]);
+        }
+    }
+    return AG_OK;
+}
+
+int ag_ppm_adam_step(ag_ctx* c, void* stream, const float* d_err, const float* d_grad_phys, int32_t n_starts, int32_t n_rows,
+                     int32_t N_o, int32_t start_major, int32_t apply_update, double lr, double bias_correction1,
+                     double bias_correction2, double lo, double hi, float* d_x, double* d_exp_avg, double* d_exp_avg_sq,
+                     int32_t hist_cap, float* d_hist_x, double* d_hist_err, double* d_best, double* d_grad_start, float* d_phys,
+                     int32_t* d_status) {
+    if (!c) return AG_ERR_INVALID;
+    if (!d_err || !d_x || !d_hist_x || !d_hist_err || !d_best || !d_grad_start || !d_status)
+        return fail(c, AG_ERR_INVALID, "ag_ppm_adam_step: null pointer");
+    if (n_starts < 1 || n_rows < 1 || N_o < 1 || hist_cap < 0)
+        return fail(c, AG_ERR_INVALID, "ag_ppm_adam_step: bad sizes n_starts=%d n_rows=%d N_o=%d hist_cap=%d", n_starts, n_rows, N_o, hist_cap);
+    if (apply_update && (!d_grad_phys || !d_exp_avg || !d_exp_avg_sq || !d_phys || !(lr >= 0.0) || !(bias_correction1 > 0.0) ||
+                         !(bias_correction2 > 0.0) || !(lo <= hi)))
+        return fail(c, AG_ERR_INVALID, "ag_ppm_adam_step: update needs gradient, moments and d_phys; lr %g, bias corrections (%g, %g), bounds [%g, %g]",
+                    lr, bias_correction1, bias_correction2, lo, hi);
+    // no call slot: one kernel on the caller's stream over the caller's own buffers - nothing of a slot or of the context is
+    // touched, so there is no end of call another stream would ever have to wait for (as the cost and MPPI entry points)
+    HIPCHK(c, hipSetDevice(c->device));
+    PpmAdamArgs a{};
+    a.err = d_err; a.grad = d_grad_phys; a.K = n_starts; a.n = n_rows; a.N_o = N_o; a.start_major = start_major ? 1 : 0;
+    a.hist_cap = hist_cap; a.apply = apply_update ? 1 : 0; a.x = d_x; a.m = d_exp_avg; a.v = d_exp_avg_sq; a.hist_x = d_hist_x;
+    a.hist_e = d_hist_err; a.best = d_best; a.gk = d_grad_start; a.phys = d_phys; a.lr = lr; a.bc1 = bias_correction1;
+    a.bc2 = bias_correction2; a.lo = lo; a.hi = hi; a.status = d_status;
+    HIPCHK(c, launch_ppm_adam(a, static_cast<hipStream_t>(stream)));
+    return AG_OK;
+}
+
+}  // extern "C"

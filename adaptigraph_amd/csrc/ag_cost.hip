@@ -23,12 +23,17 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
     __syncthreads();
     return r;
 }
+// torch.min / max / maximum return NaN when either operand is NaN; fminf / fmaxf return the other one.  The particle reductions
+// below follow torch (as k_reward's tree and limit4 of ag_mppi.hip do): a diverged rollout must score NaN, not as if its bad
+// particles did not exist.  On numbers these give fminf / fmaxf's bits.
+__device__ __forceinline__ float nan_min(float a, float b) { return a != a ? a : b != b ? b : fminf(a, b); }
+__device__ __forceinline__ float nan_max(float a, float b) { return a != a ? a : b != b ? b : fmaxf(a, b); }
 __device__ __forceinline__ float block_min(float v, float* red) {
     const int tid = threadIdx.x;
     red[tid] = v;
     __syncthreads();
     for (int o = CT / 2; o > 0; o >>= 1) {
-        if (tid < o) red[tid] = fminf(red[tid], red[tid + o]);
+        if (tid < o) red[tid] = nan_min(red[tid], red[tid + o]);
         __syncthreads();
     }
     const float r = red[0];
@@ -40,7 +45,7 @@ __device__ __forceinline__ float block_max(float v, float* red) {
     red[tid] = v;
     __syncthreads();
     for (int o = CT / 2; o > 0; o >>= 1) {
-        if (tid < o) red[tid] = fmaxf(red[tid], red[tid + o]);
+        if (tid < o) red[tid] = nan_max(red[tid], red[tid + o]);
         __syncthreads();
     }
     const float r = red[0];
@@ -60,7 +65,8 @@ constexpr int CH_PT = 4;
 // Squared distance from CH_PT owned points (registers) to every point of the other cloud (SoA in LDS, length padded to
 // even with points parked at BIG).  The sweep is VALU-bound, so it runs on the packed fp32 pipe: two points of the other
 // cloud per step (v_pk_add/mul/fma_f32) and one v_min3_f32 folds both distances - 7 instructions per 2 evaluations.
-// A parked point gives dx*dx = +inf, which min() ignores; no select in the loop.
+// A parked point gives dx*dx = +inf, which min() ignores; no select in the loop.  fminf also ignores NaN, which torch.min does
+// not: k_chamfer sends a row with a non-finite coordinate round this sweep (chamfer_nearest_nan).
 __device__ __forceinline__ void chamfer_sweep(const float* os, int opad, const float (&qx)[CH_PT], const float (&qy)[CH_PT],
                                               const float (&qz)[CH_PT], float (&m)[CH_PT]) {
     const f2* ox = reinterpret_cast<const f2*>(os);
@@ -76,6 +82,18 @@ __device__ __forceinline__ void chamfer_sweep(const float* os, int opad, const f
         }
     }
 }
+// A row with a non-finite coordinate in a valid point leaves the packed sweep (whose min drops NaN and whose parking trick
+// needs finite points): one lane per owned point, plain loop over the valid points of the other cloud, min as torch.min has it.
+// Only flagged rows pay for it; what it returns for a clean row would be the sweep's value, not its bits, so it is never used there.
+__device__ __forceinline__ float chamfer_nearest_nan(const float* q, const float* o, const uint8_t* om, int on) {
+    float best = __builtin_inff();
+    for (int i = 0; i < on; ++i) {
+        if (om && om[i] == 0) continue;
+        const float dx = o[3 * i] - q[0], dy = o[3 * i + 1] - q[1], dz = o[3 * i + 2] - q[2];
+        best = nan_min(best, __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx)));
+    }
+    return sqrtf(best);
+}
 __global__ __launch_bounds__(CT) void k_chamfer(ChamferDev a) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     __shared__ float red[CT];
@@ -88,18 +106,31 @@ __global__ __launch_bounds__(CT) void k_chamfer(ChamferDev a) {
     const uint8_t* xm = a.xm ? a.xm + (long)r * a.N : nullptr;
     const uint8_t* ym = a.ym ? a.ym + (long)(a.By == 1 ? 0 : r) * a.M : nullptr;
     const float BIG = 3.0e38f;
+    int odd = 0;                    // some valid point of either cloud has a NaN or infinite coordinate
     for (int i = tid; i < Np; i += CT) {
         const bool v = i < a.N && (xm ? xm[i] != 0 : true);   // masked-out points (and the pad) are parked at "infinity"
-        xs[i] = v ? xr[3 * i] : BIG; xs[Np + i] = v ? xr[3 * i + 1] : BIG; xs[2 * Np + i] = v ? xr[3 * i + 2] : BIG;
+        float px = BIG, py = BIG, pz = BIG;
+        if (v) { px = xr[3 * i]; py = xr[3 * i + 1]; pz = xr[3 * i + 2]; }
+        xs[i] = px; xs[Np + i] = py; xs[2 * Np + i] = pz;
+        odd |= !(__builtin_isfinite(px) && __builtin_isfinite(py) && __builtin_isfinite(pz));
     }
     for (int j = tid; j < Mp; j += CT) {
         const bool v = j < a.M && (ym ? ym[j] != 0 : true);
-        ys[j] = v ? yr[3 * j] : BIG; ys[Mp + j] = v ? yr[3 * j + 1] : BIG; ys[2 * Mp + j] = v ? yr[3 * j + 2] : BIG;
+        float px = BIG, py = BIG, pz = BIG;
+        if (v) { px = yr[3 * j]; py = yr[3 * j + 1]; pz = yr[3 * j + 2]; }
+        ys[j] = px; ys[Mp + j] = py; ys[2 * Mp + j] = pz;
+        odd |= !(__builtin_isfinite(px) && __builtin_isfinite(py) && __builtin_isfinite(pz));
     }
-    __syncthreads();
+    odd = __syncthreads_or(odd);    // (the barrier the LDS fill needs anyway)
     float sum_y = 0.f, cnt_y = 0.f, sum_x = 0.f, cnt_x = 0.f;
+    if (odd) {
+        for (int j = tid; j < a.M; j += CT)
+            if (!ym || ym[j] != 0) { sum_y += chamfer_nearest_nan(yr + 3 * j, xr, xm, a.N); cnt_y += 1.f; }
+        for (int i = tid; i < a.N; i += CT)
+            if (!xm || xm[i] != 0) { sum_x += chamfer_nearest_nan(xr + 3 * i, yr, ym, a.M); cnt_x += 1.f; }
+    } else {
     // register tiling: a lane owns CH_PT points of one cloud, so every LDS read of two points of the other cloud feeds
-    // 2*CH_PT distance evaluations
+    // 2*CH_PT distance evaluations.  Whether an owned point counts comes from its index and its mask, never from its value.
     for (int j0 = tid * CH_PT; j0 < a.M; j0 += CT * CH_PT) {     // for every y point the nearest x
         float qx[CH_PT], qy[CH_PT], qz[CH_PT], m[CH_PT];
 #pragma unroll
@@ -110,7 +141,7 @@ __global__ __launch_bounds__(CT) void k_chamfer(ChamferDev a) {
         chamfer_sweep(xs, Np, qx, qy, qz, m);
 #pragma unroll
         for (int k = 0; k < CH_PT; ++k)
-            if (j0 + k < a.M && qx[k] < BIG) { sum_y += sqrtf(m[k]); cnt_y += 1.f; }
+            if (j0 + k < a.M && (!ym || ym[j0 + k] != 0)) { sum_y += sqrtf(m[k]); cnt_y += 1.f; }
     }
     for (int i0 = tid * CH_PT; i0 < a.N; i0 += CT * CH_PT) {     // for every x point the nearest y
         float qx[CH_PT], qy[CH_PT], qz[CH_PT], m[CH_PT];
@@ -122,7 +153,8 @@ __global__ __launch_bounds__(CT) void k_chamfer(ChamferDev a) {
         chamfer_sweep(ys, Mp, qx, qy, qz, m);
 #pragma unroll
         for (int k = 0; k < CH_PT; ++k)
-            if (i0 + k < a.N && qx[k] < BIG) { sum_x += sqrtf(m[k]); cnt_x += 1.f; }
+            if (i0 + k < a.N && (!xm || xm[i0 + k] != 0)) { sum_x += sqrtf(m[k]); cnt_x += 1.f; }
+    }
     }
     const float sy = block_sum(sum_y, red), cy = block_sum(cnt_y, red);
     const float sx = block_sum(sum_x, red), cx = block_sum(cnt_x, red);
@@ -212,10 +244,10 @@ __global__ __launch_bounds__(CT) void k_state_stats(StatsDev a) {
     float acc = 0.f, xmin = 3.0e38f, xmax = -3.0e38f, zmin = 3.0e38f, zmax = -3.0e38f;
     for (int i = tid; i < a.N; i += CT) {
         const float x = s[3 * i], z = s[3 * i + 2];
-        xmin = fminf(xmin, x); xmax = fmaxf(xmax, x); zmin = fminf(zmin, z); zmax = fmaxf(zmax, z);
-        if (a.has_box) {
-            const float xd = fmaxf(a.bx0 - x, 0.f) + fmaxf(x - a.bx1, 0.f);
-            const float zd = fmaxf(a.bz0 - z, 0.f) + fmaxf(z - a.bz1, 0.f);
+        xmin = nan_min(xmin, x); xmax = nan_max(xmax, x); zmin = nan_min(zmin, z); zmax = nan_max(zmax, z);
+        if (a.has_box) {                                     // torch.maximum: a NaN coordinate makes the row's box_loss NaN
+            const float xd = nan_max(a.bx0 - x, 0.f) + nan_max(x - a.bx1, 0.f);
+            const float zd = nan_max(a.bz0 - z, 0.f) + nan_max(z - a.bz1, 0.f);
             acc += sqrtf(xd * xd + zd * zd);
         }
     }
@@ -261,14 +293,14 @@ __global__ __launch_bounds__(CT) void k_penalty(PenDev a) {
         for (int k = 0; k < npt; ++k) {
             const float ex = px[k] - sx, ez = pz[k] - sz;
             const float d = sqrtf(ex * ex + ez * ez);
-            dmin = fminf(dmin, d); dmax = fmaxf(dmax, d);
+            dmin = nan_min(dmin, d); dmax = nan_max(dmax, d);
         }
     }
     const float mn = block_min(dmin, red), mx = block_max(dmax, red);
     if (tid == 0) {
         const float size = (a.kind == 1 ? 0.005f : 0.02f) * a.ratio;
-        a.out[(long)bh * 2 + 0] = expf(-fmaxf(mn - size, 0.f) * 100.f);
-        a.out[(long)bh * 2 + 1] = fminf(mx, 0.4f * a.ratio);
+        a.out[(long)bh * 2 + 0] = expf(-nan_max(mn - size, 0.f) * 100.f);
+        a.out[(long)bh * 2 + 1] = nan_min(mx, 0.4f * a.ratio);
     }
 }
 
@@ -307,10 +339,10 @@ __global__ __launch_bounds__(RW) void k_reward(RewardDev a) {
         float ps = 0.f, bs = 0.f;
         for (int h = 0; h < a.H; ++h) {
             const float* st = a.stats + ((long)b * a.H + h) * 5;
-            const float v0 = fmaxf(st[1] - a.bx0, 0.f), v1 = fmaxf(a.bx1 - st[2], 0.f);
-            const float v2 = fmaxf(st[3] - a.bz0, 0.f), v3 = fmaxf(a.bz1 - st[4], 0.f);
+            const float v0 = nan_max(st[1] - a.bx0, 0.f), v1 = nan_max(a.bx1 - st[2], 0.f);
+            const float v2 = nan_max(st[3] - a.bz0, 0.f), v3 = nan_max(a.bz1 - st[4], 0.f);
             const float e0 = expf(-v0 * 100.0f), e1 = expf(-v1 * 100.0f), e2 = expf(-v2 * 100.0f), e3 = expf(-v3 * 100.0f);
-            bs += fmaxf(fmaxf(e0, e1), fmaxf(e2, e3));
+            bs += nan_max(nan_max(e0, e1), nan_max(e2, e3));
             ps += a.pen[(long)b * a.H + h];
         }
         a.out[b] = -ew * a.error[(long)b * a.H + a.H - 1] - 5.0f * (ps * inv_h) - 5.0f * (bs * inv_h);
@@ -331,11 +363,11 @@ __global__ __launch_bounds__(RW) void k_cloth_combine(const float* __restrict__ 
     if (dmax_in) mx = dmax_in[0];
     else {
         float m = -3.4e38f;
-        for (long i = tid; i < n; i += RW) m = fmaxf(m, raw[2 * i + 1]);
+        for (long i = tid; i < n; i += RW) m = nan_max(m, raw[2 * i + 1]);
         red[tid] = m;
         __syncthreads();
-        for (int o = RW / 2; o > 0; o >>= 1) { if (tid < o) red[tid] = fmaxf(red[tid], red[tid + o]); __syncthreads(); }
-        mx = red[0];
+        for (int o = RW / 2; o > 0; o >>= 1) { if (tid < o) red[tid] = nan_max(red[tid], red[tid + o]); __syncthreads(); }
+        mx = red[0];                                         // (a NaN maximum makes the whole batch NaN, as losses.py:62 does)
     }
     for (long i = tid; i < n; i += RW) out[i] = 1.0f - raw[2 * i] - (raw[2 * i + 1] / mx) * 0.2f;
 }

@@ -9,7 +9,8 @@
 // look-ahead step, three passes over the B rewards (max, sum of exponentials, weighted point sums) with fixed-order
 // LDS trees, so the result does not depend on B's sharding history; k_mppi_sample is one thread per (sample, step).
 // Both are tiny and latency-bound (B <= tens of thousands, 16 B per action); no roofline applies.
-// fp32 throughout, each product/sum spelled in the reference's order (-ffp-contract=off: no FMA contraction).
+// The sampler is fp32 throughout, each product/sum spelled in the reference's order (-ffp-contract=off: no FMA contraction); the
+// update keeps the reference's fp32 terms per candidate and reduces them in double (see k_mppi_update).
 #include "ag_common.h"
 
 namespace ag {
@@ -97,36 +98,48 @@ __device__ float tree_max(float v, float* red) {
     __syncthreads();
     return r;
 }
-__device__ float tree_sum(float v, float* red) {
+// fixed-order tree over doubles (MT of them: 8 KB of LDS)
+__device__ double tree_sum(double v, double* red) {
     red[threadIdx.x] = v;
     __syncthreads();
     for (int o = MT / 2; o > 0; o >>= 1) {
         if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
         __syncthreads();
     }
-    const float r = red[0];
+    const double r = red[0];
     __syncthreads();
     return r;
 }
+// The weighted means are accumulated in double, and the push vector start - end = reach * (cos theta, sin theta) is accumulated
+// itself instead of being recovered as the difference of two fp32 point sums: length = |start - end| / push_length magnifies
+// whatever that difference loses tenfold (one ulp of a sum of magnitude 3 is 2.4e-6 of length).  Per candidate the reference's
+// fp32 terms are kept (reward * weight, expf, reach = length * push_length, cosf / sinf); what is rounded to fp32 once, at the
+// end, is the start point, the angle and the length.  limit4 stays in fp32: the wrap at +-pi has the reference's bits.
 __global__ __launch_bounds__(MT) void k_mppi_update(UpdateDev d) {
-    __shared__ float red[MT];
+    __shared__ double redd[MT];
+    float* red = reinterpret_cast<float*>(redd);
     const int h = blockIdx.x, tid = threadIdx.x;
     float m = -3.4e38f;
     for (int b = tid; b < d.B; b += MT) m = fmaxf(m, d.reward[b] * d.rw);
     m = tree_max(m, red);
-    float z = 0.0f;
-    for (int b = tid; b < d.B; b += MT) z += expf(d.reward[b] * d.rw - m);
-    z = tree_sum(z, red);
-    float sx = 0.f, sy = 0.f, sxe = 0.f, sye = 0.f;
+    double z = 0.0;
+    for (int b = tid; b < d.B; b += MT) z += (double)expf(d.reward[b] * d.rw - m);
+    z = tree_sum(z, redd);
+    double sx = 0.0, sy = 0.0, sdx = 0.0, sdy = 0.0;
     for (int b = tid; b < d.B; b += MT) {
-        const float w = expf(d.reward[b] * d.rw - m) / z;
+        const double w = (double)expf(d.reward[b] * d.rw - m) / z;
         const float* a = d.acts + ((long)b * d.H + h) * 4;
-        float xe, ye;
-        end_point(a, d.pl, xe, ye);
-        sx += w * a[0]; sy += w * a[1]; sxe += w * xe; sye += w * ye;
+        const float reach = a[3] * d.pl;                      // lengths * push_length, then * cos / sin   (:87-88)
+        sx += w * (double)a[0]; sy += w * (double)a[1];
+        sdx += w * ((double)reach * (double)cosf(a[2])); sdy += w * ((double)reach * (double)sinf(a[2]));
     }
-    sx = tree_sum(sx, red); sy = tree_sum(sy, red); sxe = tree_sum(sxe, red); sye = tree_sum(sye, red);
-    if (tid == 0) encode_limit(sx, sy, sxe, sye, d.pl, d.lo, d.hi, d.out + h * 4);
+    sx = tree_sum(sx, redd); sy = tree_sum(sy, redd); sdx = tree_sum(sdx, redd); sdy = tree_sum(sdy, redd);
+    if (tid == 0) {
+        float v[4] = {(float)sx, (float)sy, (float)atan2(sdy, sdx), (float)(sqrt(sdx * sdx + sdy * sdy) / (double)d.pl)};
+        limit4(v, d.lo, d.hi);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) d.out[h * 4 + k] = v[k];
+    }
 }
 
 // ---- limits alone (clip_actions, :35-39) on n actions ---------------------------------------------------------------

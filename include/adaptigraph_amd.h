@@ -430,11 +430,15 @@ int ag_rollout_actions(ag_ctx* ctx, void* stream, const ag_rollout_params* p, co
 int ag_rollout_work(ag_ctx* ctx, void* stream, const ag_rollout_params* p, const float* d_state0, const float* d_action,
                     float push_length, const float* h_tool_offsets, int32_t max_repeat, const float* d_phys_vec, int32_t* h_work);
 
-/* ---- Per-candidate cost functions: SURVEY §8(f) rank 1 (reference src/planning/losses.py, src/planning/plan.py:27-59) ---- */
+/* ---- Per-candidate cost functions: SURVEY §8(f) rank 1 (reference src/planning/losses.py, src/planning/plan.py:27-59) ----
+ * Non-finite inputs: every ag_cost_* entry does what torch.min / max / maximum do in the reference - a NaN that a reduction reads
+ * comes out as NaN (never as "that particle was not there"), an infinity as the infinity the formula gives.  What a mask excludes
+ * is never read.  The chamfer backward is specified for finite inputs only. */
 
 /* chamfer(x, y) (losses.py:4-10): d_x (R,N,3); d_y (By,M,3) with By == 1 (one target for all rows, plan.py:146) or
  * By == R; optional uint8 masks d_xmask (R,N), d_ymask (By,M) keep only masked-in points (mean_chamfer, losses.py:12-24).
- * d_out (R,).  N + M must fit the LDS tile (<= ~13k points). */
+ * d_out (R,).  N + M must fit the LDS tile (<= ~13k points).  A row with a NaN coordinate in a masked-in point of either cloud
+ * is NaN (By == 1: a NaN in y makes every row NaN); an infinite coordinate gives +inf; the other rows keep their bits. */
 int ag_cost_chamfer(ag_ctx* ctx, void* stream, const float* d_x, const float* d_y, const uint8_t* d_xmask,
                     const uint8_t* d_ymask, int32_t R, int32_t N, int32_t M, int32_t By, float* d_out);
 
@@ -447,20 +451,22 @@ int ag_cost_chamfer_backward(ag_ctx* ctx, void* stream, const float* d_x, const 
                              float* d_grad_x);
 
 /* Particle statistics of d_state (R,N,3) -> d_out (R,5) = [box_loss, xmin, xmax, zmin, zmax]: box_loss (losses.py:26-35)
- * against h_box4 = {xmin, xmax, zmin, zmax} (NULL: entry 0 is 0), and the x/z bounds running_cost needs (plan.py:41-44). */
+ * against h_box4 = {xmin, xmax, zmin, zmax} (NULL: entry 0 is 0), and the x/z bounds running_cost needs (plan.py:41-44).
+ * A NaN x (z) coordinate makes the row's box_loss and its two x (z) bounds NaN. */
 int ag_cost_state_stats(ag_ctx* ctx, void* stream, const float* d_state, int32_t R, int32_t N, const float* h_box4,
                         float* d_out);
 
 /* Collision penalties (losses.py:37-92): kind 0 rope, 1 cloth, 2 granular.  d_state_pred (B,H,N,3), d_action (B,H,4)
  * raw [x,z,theta,len], d_state_init (N,3).  d_out (B,H,2) = [exp(-max(dmin - size,0)*100), min(dmax, 0.4*ratio)];
- * rope/granular: entry 0 is the penalty; cloth: 1 - e0 - 0.2 * e1 / max_batch(e1) (the caller owns the global max). */
+ * rope/granular: entry 0 is the penalty; cloth: 1 - e0 - 0.2 * e1 / max_batch(e1) (the caller owns the global max).
+ * A NaN in the cloud a step reads, or in its action, makes both entries of that (b,h) NaN. */
 int ag_cost_penalty(ag_ctx* ctx, void* stream, const float* d_state_pred, const float* d_action,
                     const float* d_state_init, int32_t B, int32_t H, int32_t N, int32_t kind, float sim_real_ratio,
                     float* d_out);
 
 /* cloth_penalty's tail (losses.py:62-63) on the (B,H,2) output of ag_cost_penalty(kind 1): d_out[i] = 1 - e0 - 0.2 * e1 / max(e1),
  * n = B*H entries.  d_dmax: NULL = the maximum over this batch is formed here; else a device float holding it (a sharded batch
- * all-reduces it first).  One launch. */
+ * all-reduces it first).  One launch.  The maximum formed here is NaN if any e1 is (torch.max): then every d_out is. */
 int ag_cost_cloth_combine(ag_ctx* ctx, void* stream, const float* d_raw, const float* d_dmax, int64_t n, float* d_out);
 
 /* What is left of running_cost (src/planning/plan.py:35-53) once the particle reductions are done, in one launch:
@@ -468,7 +474,8 @@ int ag_cost_cloth_combine(ag_ctx* ctx, void* stream, const float* d_raw, const f
  *   h_bbox4 = {x_lo, x_hi, z_lo, z_hi} (doubles, rounded to fp32 as torch rounds a Python scalar); reward[b] =
  *   -error_weight * error[b,H-1] - 5 * mean_h penalty[b,h] - 5 * mean_h box_penalty[b,h].
  * d_error, d_penalty (B,H); d_stats (B*H,5) as ag_cost_state_stats writes it; d_error_max: NULL = batch maximum formed here,
- * else a device float holding it (sharded batches all-reduce it first); d_reward (B,). */
+ * else a device float holding it (sharded batches all-reduce it first); d_reward (B,).  One NaN error makes the maximum formed
+ * here, hence every reward, NaN; NaN bounds make that candidate's box penalty, hence its reward, NaN. */
 int ag_cost_reward(ag_ctx* ctx, void* stream, const float* d_error, const float* d_penalty, const float* d_stats,
                    const float* d_error_max, const double* h_bbox4, int32_t B, int32_t H, float* d_reward);
 

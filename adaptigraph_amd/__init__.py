@@ -47,10 +47,11 @@ from .mppi import angle_normalize, clip_actions, sample_action_seq, optimize_act
 from .planner import Planner
 from .rollout import rollout_eval, rollout_eval_step, surface_bounds
 from .train_step import TrainStep
+from .dataset import DeviceDynDataset, BatchDraws
 
 __all__ = ["hw_queues", "Engine", "default_engine", "dynamics", "dynamics_masked", "dynamics_mixed", "rollout_work", "EdgeList", "construct_edges_from_states_batch", "construct_edges_from_states",
            "construct_edges_index", "construct_edges_with_backoff", "pad_torch", "truncate_graph", "DynamicsPredictor", "decode_action", "chamfer",
            "mean_chamfer", "box_loss", "rope_penalty", "cloth_penalty", "granular_penalty", "running_cost", "dynamics_error", "dynamics_error_sweep", "angle_normalize",
            "clip_actions", "sample_action_seq", "optimize_action_mppi", "mpc_iteration", "Planner", "rollout_eval", "rollout_eval_step", "surface_bounds",
            "dynamics_masked_diff", "chamfer_diff", "dynamics_error_grad", "optimize_grad", "TrainStep", "PhysParamFit",
-           "optimize_grad_device", "dynamics_error_grad_device"]
+           "optimize_grad_device", "dynamics_error_grad_device", "DeviceDynDataset", "BatchDraws"]

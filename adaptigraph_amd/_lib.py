@@ -21,7 +21,7 @@ AG_ERR_UNSUPPORTED = -4
 AG_ERR_NO_WEIGHTS = -5
 
 KERNEL_FAMILIES = ["edge_count", "edge_emit", "prep", "node_enc", "edge_enc", "mp", "node_prop", "node_final",
-                   "roll_init", "roll_update", "cost"]
+                   "roll_init", "roll_update", "cost", "fps", "assemble"]
 
 # exactly the symbols include/adaptigraph_amd.h declares (tests/test_abi.py checks both directions)
 EXPORTS = ["ag_abi_version", "ag_ctx_create", "ag_ctx_destroy", "ag_last_error", "ag_ctx_load_weights",
@@ -31,7 +31,8 @@ EXPORTS = ["ag_abi_version", "ag_ctx_create", "ag_ctx_destroy", "ag_last_error",
            "ag_edges_apply_tool_rule", "ag_mppi_sample", "ag_mppi_update", "ag_mppi_clip",
            "ag_ctx_set_option", "ag_ctx_get_option", "ag_ctx_rollout_counts", "ag_rollout_actions", "ag_ctx_share_counts", "ag_ctx_launch_counts", "ag_cost_reward", "ag_cost_cloth_combine",
            "ag_ctx_alloc_counts", "ag_rollout_work", "ag_backward", "ag_backward_inputs", "ag_cost_chamfer_backward",
-           "ag_ctx_load_weights_device", "ag_adam_step", "ag_train_step", "ag_ppm_grad_step", "ag_ppm_adam_step", "ag_train_step_part"]
+           "ag_ctx_load_weights_device", "ag_adam_step", "ag_train_step", "ag_ppm_grad_step", "ag_ppm_adam_step", "ag_train_step_part",
+           "ag_fps_batch", "ag_dataset_assemble", "ag_build_edges_graphs"]
 
 OPTIONS = ["streams", "chunk", "latency", "ragged", "ell_graph", "self_dedupe", "repeat_sort", "edge_wgs", "edge_block_min",
            "enc_persist", "stagger_us", "device_decode", "zigzag", "share_first", "share_prefix", "stream_min_rows", "pipeline_fork"]
@@ -47,6 +48,16 @@ class AgRolloutParams(C.Structure):
                 ("connect_tools_all", C.c_int32), ("max_nR", C.c_int32), ("y_mode", C.c_int32),
                 ("adj_thresh", C.c_float), ("gripper_offset", C.c_float), ("gripper_enable", C.c_int32),
                 ("physics_param", C.c_float)]
+
+
+class AgDatasetBatch(C.Structure):
+    """ag_dataset_batch (include/adaptigraph_amd.h), field for field."""
+    _fields_ = ([(n, C.c_void_p) for n in ("d_obj_pos", "d_eef_pos", "d_sample", "d_fps_idx", "d_n_obj", "d_phys", "d_phys_noise",
+                                           "d_state_noise", "d_rot", "d_adj_thresh")] +
+                [(n, C.c_int32) for n in ("B", "n_his", "n_future", "max_nobj", "n_eef", "phys_dim", "n_mat", "mat_col")] +
+                [(n, C.c_void_p) for n in ("d_state", "d_action", "d_eef_future", "d_action_future", "d_state_future", "d_attrs",
+                                           "d_p_instance", "d_obj_mask", "d_state_mask", "d_eef_mask", "d_material_index",
+                                           "d_physics_param", "d_thr2", "d_cull")])
 
 
 _lib = None
@@ -108,6 +119,9 @@ def load():
     lib.ag_mppi_sample.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp]
     lib.ag_mppi_update.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, vp]
     lib.ag_mppi_clip.argtypes = [vp, vp, vp, vp, vp, C.c_int64, vp]
+    lib.ag_fps_batch.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp]
+    lib.ag_dataset_assemble.argtypes = [vp, vp, C.POINTER(AgDatasetBatch)]
+    lib.ag_build_edges_graphs.argtypes = [vp, vp, vp, C.c_int64, vp, vp, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp]
     lib.ag_ctx_set_profiling.argtypes = [vp, i32]
     lib.ag_ctx_kernel_stats.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     lib.ag_ctx_reset_stats.argtypes = [vp]

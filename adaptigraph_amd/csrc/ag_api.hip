@@ -9,7 +9,7 @@ using namespace ag;
 namespace {
 
 const char* kFamilyNames[FAM_COUNT] = {"edge_count", "edge_emit", "prep", "node_enc", "edge_enc",
-                                       "mp", "node_prop", "node_final", "roll_init", "roll_update", "cost"};
+                                       "mp", "node_prop", "node_final", "roll_init", "roll_update", "cost", "fps", "assemble"};
 
 struct OptName { const char* name; const char* env; int Options::* field; bool env_negates; int lo, hi; };
 const OptName kOptions[] = {
@@ -355,7 +355,8 @@ int build_edges(ag_ctx* c, void* stream, EdgeArgs& a) {
         a.slice_tot = s.take<int>((size_t)a.B * a.slices); a.cta_flag = s.take<int>(a.B);
     });
     if (rc) return rc;
-    a.pos_bstride = (long)a.N * 3; a.overflow = nullptr; a.max_nR = a.edge_cap; a.zero_on_overflow = 0;
+    if (!a.pos_bstride) a.pos_bstride = (long)a.N * 3;      // (ag_build_edges_graphs reads the graphs out of a larger tensor)
+    a.overflow = nullptr; a.max_nR = a.edge_cap; a.zero_on_overflow = 0;
     a.block_min_rows = c->opt.edge_block_min;
     HIPCHK(c, launch_edge_build(a, call.st, prof_mark, c));
     return AG_OK;
@@ -533,6 +534,23 @@ int ag_build_edges_single(ag_ctx* c, void* stream, const float* d_pos, const uin
     a.pos = d_pos; a.mask = d_mask; a.tool = d_tool; a.thr_vec = nullptr; a.thr = cull_radius;
     a.thr2_override = thr2; a.use_thr2 = 1;
     a.B = 1; a.N = N; a.topk = topk; a.cta = cta ? 2 : 0; a.edge_cap = edge_cap;
+    a.recv = d_recv; a.send = d_send; a.row_ptr = d_row_ptr; a.n_edges = d_n_edges;
+    return build_edges(c, stream, a);
+}
+
+int ag_build_edges_graphs(ag_ctx* c, void* stream, const float* d_pos, int64_t pos_bstride, const uint8_t* d_mask,
+                          const uint8_t* d_tool, int32_t B, int32_t N, const float* d_thr2, const float* d_cull, int32_t topk,
+                          int32_t cta, int32_t edge_cap, int32_t* d_recv, int32_t* d_send, int32_t* d_row_ptr, int32_t* d_n_edges) {
+    if (!c) return AG_ERR_INVALID;
+    if (!d_pos || !d_mask || !d_tool || !d_thr2 || !d_cull || !d_recv || !d_send || !d_row_ptr || !d_n_edges || B < 1 || edge_cap < 1)
+        return fail(c, AG_ERR_INVALID, "ag_build_edges_graphs: null pointer or empty batch");
+    int rc = check_topk(c, N, topk);
+    if (rc) return rc;
+    if (pos_bstride != 0 && pos_bstride < (int64_t)N * 3)
+        return fail(c, AG_ERR_INVALID, "ag_build_edges_graphs: pos_bstride %lld is below N*3 = %d", (long long)pos_bstride, N * 3);
+    EdgeArgs a{};
+    a.pos = d_pos; a.pos_bstride = (long)pos_bstride; a.mask = d_mask; a.tool = d_tool; a.thr_vec = d_cull; a.thr2_vec = d_thr2;
+    a.B = B; a.N = N; a.topk = topk; a.cta = cta ? 2 : 0; a.edge_cap = edge_cap;
     a.recv = d_recv; a.send = d_send; a.row_ptr = d_row_ptr; a.n_edges = d_n_edges;
     return build_edges(c, stream, a);
 }

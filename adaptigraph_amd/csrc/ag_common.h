@@ -62,7 +62,7 @@ struct WeightLayout {
 
 // ---- kernel families (profiling ids) ------------------------------------------------------------------
 enum Family { FAM_EDGE_COUNT = 0, FAM_EDGE_EMIT, FAM_PREP, FAM_NODE_ENC, FAM_EDGE_ENC, FAM_MP, FAM_NODE_PROP,
-              FAM_NODE_FINAL, FAM_ROLL_INIT, FAM_ROLL_UPDATE, FAM_COST, FAM_COUNT };
+              FAM_NODE_FINAL, FAM_ROLL_INIT, FAM_ROLL_UPDATE, FAM_COST, FAM_FPS, FAM_ASSEMBLE, FAM_COUNT };
 
 // ---- per-context tuning / A-B switches.  Defaults come from the environment ONCE, at ag_ctx_create (the AG_* name in
 // brackets); ag_ctx_set_option changes them per context afterwards.  None of them changes a result (bit-identical paths),
@@ -112,6 +112,8 @@ struct EdgeArgs {
     const float* thr_vec;       // (B,) or null
     float thr;                  // also the chunk-culling radius: must satisfy thr*thr >= the squared threshold in use
     float thr2_override; int use_thr2;   // single-graph builder (graph.py:86,101)
+    const float* thr2_vec;      // (B,) or null: B single-graph builds in one launch (ag_build_edges_graphs) - graph b's squared
+                                // threshold; thr_vec then holds its culling radius (thr_vec[b]^2 >= thr2_vec[b])
     int B, N, topk, cta, edge_cap, slices;   // cta: 0 off, 1 batch rule (graph.py:276-286), 2 single-graph rule (:119-122)
     int* ell;                   // (B,N,min(topk,N)) scratch: kept senders per row (unused when topk >= N)
     int* deg;                   // (B,N) scratch
@@ -145,6 +147,16 @@ struct EdgeArgs {
     const int* share_start; const int* share_cand; int share_b0;
 };
 hipError_t launch_edge_build(const EdgeArgs& a, hipStream_t st, void (*mark)(void*, int, int), void* mark_ctx);
+// both farthest-point stages of B samples (ag_dataset.hip); pt_off / npts are read at [b * stride]
+struct FpsArgs {
+    const float* pos; const long long* pt_off; const long long* npts; int stride;
+    const int* fps_start; const float* fps_radius; const int* rad_start;
+    int B, max_nobj, max_pts;
+    int* fps_idx; int* n_obj;
+};
+hipError_t launch_fps_batch(const FpsArgs& a, hipStream_t st);
+size_t fps_max_points();
+int fps_max_nobj();
 // list of non-self-loop edges per candidate (self-loop dedupe, see GraphBufs)
 // one tool-attachment rule of the single-graph builder applied to a CSR edge list (ag_rules.hip)
 struct RuleArgs {

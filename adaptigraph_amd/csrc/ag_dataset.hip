@@ -1,0 +1,279 @@
+// Training-batch construction: the sampling and assembly half of DynDataset.__getitem__ (reference
+// src/dynamics/dataset/dataset.py:117-300) for B samples per launch.  gfx950 only.
+//
+//   k_fps_batch         both farthest-point stages (dataset/graph.py:8-36) of B samples, one workgroup per sample
+//   k_dataset_assemble  every dense tensor of the batch, zero padding included, straight from the flat episode buffers
+//
+// Indices and un-augmented tensors must equal the reference bit for bit, so the fp32 arithmetic is spelled out:
+//   stage 1 (dgl.geometry.farthest_point_sampler, restated from its CPU implementation - dgl is not available to check
+//   against): running minimum of ((dx*dx + dy*dy) + dz*dz), separate mul/add, initialised to 1e10; the next point is the
+//   strict-greater argmax, i.e. the LOWEST index among equal distances; the first point is given.
+//   stage 2 (fps_rad_idx, src/dynamics/utils.py:10-24) on the stage-1 points in their order: the same sum, then a correctly
+//   rounded sqrt (np.linalg.norm); while max > radius (fp32 against fp32): append the argmax (lowest index), take the minimum.
+// The argmax is one max-reduction over a packed 64-bit key: distance bits above (non-negative floats order as integers),
+// inverted index below - the largest key is the largest distance at the lowest index, no second pass.  The running minima
+// live in registers (PPT points per thread), the cloud in LDS as SoA; one barrier per selected point.
+// No atomics: every output has one writer.
+#include "../../include/adaptigraph_amd.h"
+#include "ag_common.h"
+
+namespace ag {
+
+constexpr int FW = 256;                 // threads per workgroup: 4 wavefronts, so the cross-wave step reads 4 keys
+constexpr int FWAVES = FW / 64;
+constexpr int FPS_PPT_MAX = 32;         // points per thread of the largest instantiation
+constexpr int FPS_MAX_POINTS = FW * FPS_PPT_MAX;   // 8192 points: 96 KB of the CU's 160 KB of LDS for the cloud
+constexpr int FPS_PPT2 = 4;
+constexpr int FPS_MAX_NOBJ = FW * FPS_PPT2;        // 1024 stage-1 points (16 KB), stage 2 keeps 4 per thread
+
+size_t fps_max_points() { return FPS_MAX_POINTS; }
+int fps_max_nobj() { return FPS_MAX_NOBJ; }
+
+__device__ __forceinline__ float fps_d2(float xi, float yi, float zi, float xj, float yj, float zj) {
+    const float dx = __fsub_rn(xi, xj), dy = __fsub_rn(yi, yj), dz = __fsub_rn(zi, zj);
+    return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+}
+__device__ __forceinline__ unsigned long long fps_key(float d, int i) {
+    return ((unsigned long long)__float_as_uint(d) << 32) | (0xffffffffu - (unsigned)i);
+}
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned lo = __shfl_xor((unsigned)(v & 0xffffffffull), o);
+        const unsigned hi = __shfl_xor((unsigned)(v >> 32), o);
+        const unsigned long long w = ((unsigned long long)hi << 32) | lo;
+        v = w > v ? w : v;
+    }
+    return v;
+}
+// max of `mine` over the workgroup, in every thread.  `it` counts the reductions of the launch: consecutive ones use
+// alternate halves of wkey, so one barrier per reduction is enough (a thread can only overwrite a half after every thread
+// has passed the barrier of the reduction in between, i.e. has read it).
+__device__ __forceinline__ unsigned long long block_max_u64(unsigned long long mine, unsigned long long* wkey, int& it) {
+    mine = wave_max_u64(mine);
+    unsigned long long* w = wkey + (it & 1) * FWAVES;
+    if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = mine;
+    __syncthreads();
+    unsigned long long g = w[0];
+#pragma unroll
+    for (int k = 1; k < FWAVES; ++k) g = w[k] > g ? w[k] : g;
+    ++it;
+    return g;
+}
+
+struct FpsDev {
+    const float* pos; const long long* pt_off; const long long* npts; int stride;
+    const int* fps_start; const float* fps_radius; const int* rad_start;
+    int max_nobj, max_pts, pad;          // pad: floats per LDS coordinate array
+    int* fps_idx; int* n_obj;
+};
+inline size_t fps_lds_bytes(int pad, int max_nobj) { return 64 + (size_t)pad * 12 + (size_t)max_nobj * 16; }
+
+template <int PPT>
+__global__ __launch_bounds__(FW) void k_fps_batch(FpsDev a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned long long* wkey = reinterpret_cast<unsigned long long*>(smem);          // [2][FWAVES]
+    float* x = reinterpret_cast<float*>(smem + 64);
+    float* y = x + a.pad;
+    float* z = y + a.pad;
+    float* sx = z + a.pad;               // stage-1 points in selection order
+    float* sy = sx + a.max_nobj;
+    float* sz = sy + a.max_nobj;
+    int* sidx = reinterpret_cast<int*>(sz + a.max_nobj);
+    const int b = blockIdx.x, tid = threadIdx.x;
+    int* out = a.fps_idx + (long)b * a.max_nobj;
+    const long long nraw = a.npts[(long)b * a.stride];
+    // (the host refuses clouds above max_pts before it enqueues; the clamp keeps a wrong count inside the LDS arrays)
+    const int n = (int)(nraw < 0 ? 0 : nraw > (long long)a.max_pts ? (long long)a.max_pts : nraw);
+    if (n == 0) {
+        for (int t = tid; t < a.max_nobj; t += FW) out[t] = -1;
+        if (tid == 0) a.n_obj[b] = 0;
+        return;
+    }
+    const float* p = a.pos + a.pt_off[(long)b * a.stride] * 3;
+    for (int i = tid; i < n; i += FW) { x[i] = p[3 * (long)i]; y[i] = p[3 * (long)i + 1]; z[i] = p[3 * (long)i + 2]; }
+    __syncthreads();
+    int it = 0;
+    // ---- stage 1
+    const int n1 = min(a.max_nobj, n);
+    float md[PPT];
+#pragma unroll
+    for (int u = 0; u < PPT; ++u) md[u] = 1e10f;
+    int cur = min(max(a.fps_start[b], 0), n - 1);
+    if (tid == 0) { sidx[0] = cur; sx[0] = x[cur]; sy[0] = y[cur]; sz[0] = z[cur]; }
+    for (int k = 1; k < n1; ++k) {
+        const float cx = x[cur], cy = y[cur], cz = z[cur];                            // same address in every lane: broadcast
+        unsigned long long best = 0;
+#pragma unroll
+        for (int u = 0; u < PPT; ++u) {
+            const int i = u * FW + tid;
+            if (i < n) {
+                const float d = fps_d2(x[i], y[i], z[i], cx, cy, cz);
+                md[u] = md[u] > d ? d : md[u];
+                const unsigned long long key = fps_key(md[u], i);
+                best = key > best ? key : best;
+            }
+        }
+        const unsigned long long g = block_max_u64(best, wkey, it);
+        cur = (int)(0xffffffffu - (unsigned)(g & 0xffffffffull));
+        if (tid == 0) { sidx[k] = cur; sx[k] = x[cur]; sy[k] = y[cur]; sz[k] = z[cur]; }
+    }
+    __syncthreads();
+    // ---- stage 2 on the n1 selected points
+    const float radius = a.fps_radius[b];
+    float m2[FPS_PPT2];
+#pragma unroll
+    for (int u = 0; u < FPS_PPT2; ++u) m2[u] = __builtin_huge_valf();
+    cur = min(max(a.rad_start[b], 0), n1 - 1);
+    int count = 0;
+    while (true) {
+        if (tid == 0) out[count] = sidx[cur];
+        ++count;
+        const float cx = sx[cur], cy = sy[cur], cz = sz[cur];
+        unsigned long long best = 0;
+#pragma unroll
+        for (int u = 0; u < FPS_PPT2; ++u) {
+            const int i = u * FW + tid;
+            if (i < n1) {
+                const float d = __fsqrt_rn(fps_d2(sx[i], sy[i], sz[i], cx, cy, cz));
+                m2[u] = m2[u] > d ? d : m2[u];
+                const unsigned long long key = fps_key(m2[u], i);
+                best = key > best ? key : best;
+            }
+        }
+        const unsigned long long g = block_max_u64(best, wkey, it);                   // the same value in every thread
+        if (!(__uint_as_float((unsigned)(g >> 32)) > radius) || count >= n1) break;
+        cur = (int)(0xffffffffu - (unsigned)(g & 0xffffffffull));
+    }
+    for (int t = count + tid; t < a.max_nobj; t += FW) out[t] = -1;
+    if (tid == 0) a.n_obj[b] = count;
+}
+
+template <int PPT>
+static hipError_t launch_fps(const FpsDev& a, int B, size_t lds, hipStream_t st) {
+    if (lds > 64 * 1024) {               // above 64 KB of dynamic LDS: a per-device opt-in of the function
+        // (host threads may race on this mask: harmless, the attribute call is idempotent - at worst it is repeated)
+        static unsigned long long attr_devices = 0;
+        int dev_id = 0;
+        if (hipGetDevice(&dev_id) != hipSuccess) dev_id = 0;
+        if (dev_id >= 64 || !(attr_devices >> dev_id & 1ull)) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_fps_batch<PPT>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
+            if (e != hipSuccess) return e;
+            if (dev_id < 64) attr_devices |= 1ull << dev_id;
+        }
+    }
+    hipLaunchKernelGGL(k_fps_batch<PPT>, dim3(B), dim3(FW), lds, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_fps_batch(const FpsArgs& h, hipStream_t st) {
+    FpsDev a;
+    a.pos = h.pos; a.pt_off = h.pt_off; a.npts = h.npts; a.stride = h.stride;
+    a.fps_start = h.fps_start; a.fps_radius = h.fps_radius; a.rad_start = h.rad_start;
+    a.max_nobj = h.max_nobj; a.max_pts = h.max_pts; a.fps_idx = h.fps_idx; a.n_obj = h.n_obj;
+    const int ppt = h.max_pts <= 4 * FW ? 4 : h.max_pts <= 16 * FW ? 16 : FPS_PPT_MAX;
+    a.pad = ppt * FW;
+    const size_t lds = fps_lds_bytes(a.pad, a.max_nobj);   // at most 64 + 96 KB + 16 KB
+    if (ppt == 4) return launch_fps<4>(a, h.B, lds, st);
+    if (ppt == 16) return launch_fps<16>(a, h.B, lds, st);
+    return launch_fps<FPS_PPT_MAX>(a, h.B, lds, st);
+}
+
+// ---------------------------------------------------------------------------------------------- assembly
+// One workgroup per sample, one thread per particle row: the row's history, action, futures, attributes and masks.
+// Augmentation (dataset.py:274-285): the noise is added in double and rounded once (numpy's float32 += float64), then the
+// row vector is multiplied by the fp32 rotation matrix of the angle - x' = x*c + y*s, y' = x*(-s) + y*c, z' = z - as
+// separate fp32 products and one sum (the reference's matmul may contract them: tests allow for that on rotated fixtures).
+struct AsmRot { float c, s; bool on; };
+__device__ __forceinline__ void rot_store(float* dst, float vx, float vy, float vz, const AsmRot& r) {
+    if (r.on) {
+        const float nx = __fadd_rn(__fmul_rn(vx, r.c), __fmul_rn(vy, r.s));
+        const float ny = __fadd_rn(__fmul_rn(vx, -r.s), __fmul_rn(vy, r.c));
+        vx = nx; vy = ny;
+    }
+    dst[0] = vx; dst[1] = vy; dst[2] = vz;
+}
+
+__global__ __launch_bounds__(FW) void k_dataset_assemble(ag_dataset_batch a) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int nh = a.n_his, nf = a.n_future, No = a.max_nobj, Ne = a.n_eef, N = No + Ne;
+    const int64_t* m = a.d_sample + (long)b * (5 + nh + nf);
+    const long long n_e = m[1], obj_off = m[2], eef_off = m[3], ep = m[4];
+    const int64_t* fr = m + 5;
+    const int n_obj = min(max(a.d_n_obj[b], 0), No);
+    AsmRot r{1.f, 0.f, a.d_rot != nullptr};
+    if (r.on) { const double ang = a.d_rot[b]; r.c = (float)cos(ang); r.s = (float)sin(ang); }
+    for (int i = tid; i < N; i += FW) {
+        const bool is_obj = i < No, live = i < n_obj, is_eef = !is_obj;
+        long long src = 0;
+        if (live) { src = a.d_fps_idx[(long)b * No + i]; src = src < 0 ? 0 : src >= n_e ? n_e - 1 : src; }
+        // position of this row in pair frame t (zero for the padding rows)
+        auto at = [&](int t, float& vx, float& vy, float& vz) {
+            vx = vy = vz = 0.f;
+            const float* p = nullptr;
+            if (live) p = a.d_obj_pos + (obj_off + fr[t] * n_e + src) * 3;
+            else if (is_eef) p = a.d_eef_pos + (eef_off + fr[t] * Ne + (i - No)) * 3;
+            if (p) { vx = p[0]; vy = p[1]; vz = p[2]; }
+        };
+        for (int t = 0; t < nh; ++t) {                                               // dataset.py:192-202
+            float vx, vy, vz;
+            at(t, vx, vy, vz);
+            const long o = (((long)b * nh + t) * N + i) * 3;
+            if (a.d_state_noise) {                                                   // :275, padding and tool rows included
+                vx = (float)((double)vx + a.d_state_noise[o]);
+                vy = (float)((double)vy + a.d_state_noise[o + 1]);
+                vz = (float)((double)vz + a.d_state_noise[o + 2]);
+            }
+            rot_store(a.d_state + o, vx, vy, vz, r);
+        }
+        {                                                                            // :176-179
+            float ax = 0.f, ay = 0.f, az = 0.f;
+            if (is_eef) {
+                float x0, y0, z0, x1, y1, z1;
+                at(nh - 1, x0, y0, z0); at(nh, x1, y1, z1);
+                ax = __fsub_rn(x1, x0); ay = __fsub_rn(y1, y0); az = __fsub_rn(z1, z0);
+            }
+            rot_store(a.d_action + ((long)b * N + i) * 3, ax, ay, az, r);
+        }
+        for (int f = 0; f < nf - 1; ++f) {                                           // :220-225
+            float x0 = 0.f, y0 = 0.f, z0 = 0.f, x1 = 0.f, y1 = 0.f, z1 = 0.f;
+            if (is_eef) { at(nh + f, x0, y0, z0); at(nh + f + 1, x1, y1, z1); }
+            const long o = (((long)b * (nf - 1) + f) * N + i) * 3;
+            rot_store(a.d_eef_future + o, x0, y0, z0, r);
+            rot_store(a.d_action_future + o, __fsub_rn(x1, x0), __fsub_rn(y1, y0), __fsub_rn(z1, z0), r);
+        }
+        a.d_attrs[((long)b * N + i) * 2] = live ? 1.f : 0.f;                         // :249-251
+        a.d_attrs[((long)b * N + i) * 2 + 1] = is_eef ? 1.f : 0.f;
+        a.d_state_mask[(long)b * N + i] = (live || is_eef) ? 1 : 0;                  // :234-239
+        a.d_eef_mask[(long)b * N + i] = is_eef ? 1 : 0;
+        if (is_obj) {
+            for (int f = 0; f < nf; ++f) {                                           // :213-216
+                float vx, vy, vz;
+                at(nh + f, vx, vy, vz);
+                rot_store(a.d_state_future + (((long)b * nf + f) * No + i) * 3, vx, vy, vz, r);
+            }
+            a.d_p_instance[(long)b * No + i] = live ? 1.f : 0.f;                     // :257-258
+            a.d_obj_mask[(long)b * No + i] = live ? 1 : 0;                           // :241-242
+            for (int k = 0; k < a.n_mat; ++k)                                        // :269-271
+                a.d_material_index[((long)b * No + i) * a.n_mat + k] = (live && k == a.mat_col) ? 1 : 0;
+        }
+    }
+    // physics parameter: the stored value plus the noise, in double, rounded once (:265-266 on a copy, :299)
+    for (int k = tid; k < a.phys_dim; k += FW)
+        a.d_physics_param[(long)b * a.phys_dim + k] =
+            (float)(a.d_phys[ep * a.phys_dim + k] + (a.d_phys_noise ? a.d_phys_noise[(long)b * a.phys_dim + k] : 0.0));
+    // squared edge threshold of the single-graph builder (graph.py:86,101) and a culling radius whose square covers it
+    if (tid == 0 && a.d_adj_thresh) {
+        const double adj = a.d_adj_thresh[b];
+        a.d_thr2[b] = (float)(adj * adj);
+        a.d_cull[b] = nextafterf((float)fabs(adj), __builtin_huge_valf());
+    }
+}
+
+hipError_t launch_dataset_assemble(const ag_dataset_batch& a, hipStream_t st) {
+    hipLaunchKernelGGL(k_dataset_assemble, dim3(a.B), dim3(FW), 0, st, a);
+    return hipGetLastError();
+}
+
+}  // namespace ag

@@ -46,6 +46,7 @@ struct EdgeDev {
     const float* pos; long pos_bstride;  // floats between candidates
     const uint8_t* mask; const uint8_t* tool; const float* thr_vec; float thr;
     float thr2_override; int use_thr2;   // single-graph builder: threshold squared in double, then rounded (graph.py:86,101)
+    const float* thr2_vec;               // one such threshold per graph (EdgeArgs::thr2_vec), or null
     int B, N, k, topk_active, cta, edge_cap, slices, rows_per_slice;
     int* ell;                            // (B, N, k) kept non-merged senders per row (top-k active only)
     int ell_full, ell_stride; long ell_bstride;   // see EdgeArgs
@@ -468,7 +469,10 @@ constexpr int BLOCK_MIN_ROWS = 256;   // below: the per-row path (16 wavefronts 
 __device__ __forceinline__ float thr_of(const EdgeDev& a, int b) { return a.thr_vec ? a.thr_vec[b] : a.thr; }
 // squared threshold of the adjacency test: fp32*fp32 for the batch builder (graph.py:250), a caller-supplied value
 // for the single-graph builder, whose Python squares in double before the fp32 subtraction (graph.py:86,101)
-__device__ __forceinline__ float thr2_of(const EdgeDev& a, float thr) { return a.use_thr2 ? a.thr2_override : __fmul_rn(thr, thr); }
+// (one per graph when B of them are built in one launch)
+__device__ __forceinline__ float thr2_of(const EdgeDev& a, int b, float thr) {
+    return a.thr2_vec ? a.thr2_vec[b] : a.use_thr2 ? a.thr2_override : __fmul_rn(thr, thr);
+}
 
 // number of final senders of row i when top-k is not active (full sweep with culling); nontool_raw as above
 __device__ int row_radius_count(const EdgeDev& a, const EdgeLds& l, int i, float thr, float thr2, int flag, int* nontool_raw) {
@@ -498,7 +502,7 @@ __global__ __launch_bounds__(EW) void k_edge_count(EdgeDev a) {
     const EdgeLds l = carve(smem, a.N);
     load_candidate(a, l, b, true);
     const float thr = thr_of(a, b);
-    const float thr2 = thr2_of(a, thr);
+    const float thr2 = thr2_of(a, b, thr);
     const int lane = lane_id(), wave = threadIdx.x >> 6;
     const int r0 = sl * a.rows_per_slice;
     const int r1 = min(a.N, r0 + a.rows_per_slice);
@@ -686,7 +690,7 @@ __global__ __launch_bounds__(EW) void k_edge_emit(EdgeDev a) {
         }
     } else {
         const float thr = thr_of(a, b);
-        const float thr2 = thr2_of(a, thr);
+        const float thr2 = thr2_of(a, b, thr);
         for (int i = r0 + wave; i < r1; i += EWAVES) {
             const float xi = l.x[i], yi = l.y[i], zi = l.z[i];
             const int fi = l.fl[i];
@@ -844,7 +848,7 @@ __global__ __launch_bounds__(EW) void k_ell_index(EdgeDev a) {
 hipError_t launch_edge_build(const EdgeArgs& h, hipStream_t st, void (*mark)(void*, int, int), void* mark_ctx) {
     EdgeDev a;
     a.pos = h.pos; a.pos_bstride = h.pos_bstride; a.mask = h.mask; a.tool = h.tool; a.thr_vec = h.thr_vec; a.thr = h.thr;
-    a.thr2_override = h.thr2_override; a.use_thr2 = h.use_thr2;
+    a.thr2_override = h.thr2_override; a.use_thr2 = h.use_thr2; a.thr2_vec = h.thr2_vec;
     a.B = h.B; a.N = h.N; a.k = min(h.N, h.topk); a.topk_active = a.k < h.N; a.cta = h.cta; a.edge_cap = h.edge_cap;
     a.slices = h.slices; a.rows_per_slice = (h.N + h.slices - 1) / h.slices;
     a.ell = h.ell; a.deg = h.deg; a.slice_tot = h.slice_tot; a.cta_flag = h.cta_flag;

@@ -532,6 +532,76 @@ int ag_train_step_part(ag_ctx* ctx, void* stream, const float* d_state, const fl
                        float* const* d_grad_w, float* d_loss, float* d_pred, int32_t* d_status, int32_t B_total,
                        int32_t accumulate);
 
+/* ---- training batches on the device: the sampling, assembly and graph half of DynDataset.__getitem__
+ * (src/dynamics/dataset/dataset.py:117-383).  Episode positions live in two flat fp32 buffers (object points, end-effector
+ * points), episode after episode, frame after frame, without padding.  All three calls only enqueue. */
+
+/* Both farthest-point stages of dataset/graph.py:8-36 (fps) for B samples in one launch, one workgroup per sample.
+ *   d_pos        flat object positions; sample b's cloud is the d_npts[b*stride] points from point d_pt_off[b*stride] on
+ *                (int64 arrays read with an element stride, so that both may be columns of one per-sample table)
+ *   d_fps_start  first point of stage 1, in [0, N_e); d_fps_radius fp32 radius of stage 2 (>= 0); d_rad_start first point of
+ *                stage 2, in [0, min(max_nobj, N_e))   (out-of-range starts are clamped into range)
+ *   max_pts      the caller's bound on d_npts (a larger count is truncated to it)
+ * Stage 1 is dgl.geometry.farthest_point_sampler restated from its CPU implementation (dgl itself was not available to
+ * check against): min(max_nobj, N_e) points; running minimum of the fp32 squared distance ((dx*dx + dy*dy) + dz*dz), no
+ * contraction, initialised to 1e10; the next point is the strict-greater argmax, so the lowest index wins ties.  Stage 2
+ * is fps_rad_idx (src/dynamics/utils.py:10-24) on the stage-1 points in stage-1 order: distance = correctly rounded sqrt of
+ * the same sum; while the maximum exceeds the radius (fp32 against fp32) append the argmax (lowest index) and take the
+ * minimum.  Outputs: d_fps_idx (B, max_nobj) int32 = stage1[stage2] in selection order, -1 behind the d_n_obj[b] entries.
+ * Limits: 1 <= max_nobj <= 1024, 1 <= max_pts <= 8192 (the cloud is LDS-resident), else AG_ERR_UNSUPPORTED. */
+int ag_fps_batch(ag_ctx* ctx, void* stream, const float* d_pos, const int64_t* d_pt_off, const int64_t* d_npts, int32_t stride,
+                 const int32_t* d_fps_start, const float* d_fps_radius, const int32_t* d_rad_start, int32_t B, int32_t max_nobj,
+                 int32_t max_pts, int32_t* d_fps_idx, int32_t* d_n_obj);
+
+/* One training batch (dataset.py:171-300), N = max_nobj + n_eef rows per sample.  T = n_his + n_future pair frames per sample: a
+ * rest frame (store_rest_state with a short pair) is just frame index 0 in front. */
+typedef struct ag_dataset_batch {
+    const float* d_obj_pos;        /* flat object positions                                                              */
+    const float* d_eef_pos;        /* flat end-effector positions, n_eef points per frame                                */
+    const int64_t* d_sample;       /* (B, 5 + T): [unused, N_e, first object point of the episode, first end-effector point
+                                      of the episode, episode index, frame index x T]; frame t of the episode starts at point
+                                      first + frame * N_e (n_eef)                                                        */
+    const int32_t* d_fps_idx;      /* (B, max_nobj), d_n_obj (B,): ag_fps_batch's outputs                                */
+    const int32_t* d_n_obj;
+    const double* d_phys;          /* (n_episodes, phys_dim) stored physics parameter                                    */
+    const double* d_phys_noise;    /* (B, phys_dim) or NULL                                                              */
+    const double* d_state_noise;   /* (B, n_his, N, 3) or NULL: added to EVERY row of state (padding and tool rows too, as
+                                      the reference does), in double, one rounding = numpy's float32 += float64          */
+    const double* d_rot;           /* (B,) angle or NULL: then state, action, eef_future, action_future and state_future are
+                                      multiplied by the fp32 matrix of dataset.py:277-285: x' = x*c + y*s, y' = x*(-s) + y*c
+                                      (c, s = cos, sin in double, rounded to fp32; separate products, one sum), z' = z    */
+    const double* d_adj_thresh;    /* (B,) or NULL: edge radius -> d_thr2 = fp32(adj*adj in double) (graph.py:86,101) and
+                                      d_cull = nextafter(fp32(|adj|), inf), the inputs of ag_build_edges_graphs          */
+    int32_t B, n_his, n_future, max_nobj, n_eef, phys_dim, n_mat, mat_col;
+    float* d_state;                /* (B, n_his, N, 3)                                                                    */
+    float* d_action;               /* (B, N, 3) fp32 difference of the end-effector rows, frames n_his and n_his - 1      */
+    float* d_eef_future;           /* (B, n_future - 1, N, 3)                                                             */
+    float* d_action_future;        /* (B, n_future - 1, N, 3)                                                             */
+    float* d_state_future;         /* (B, n_future, max_nobj, 3)                                                          */
+    float* d_attrs;                /* (B, N, 2)                                                                           */
+    float* d_p_instance;           /* (B, max_nobj, 1)                                                                    */
+    uint8_t* d_obj_mask;           /* (B, max_nobj)                                                                       */
+    uint8_t* d_state_mask;         /* (B, N) valid particle; d_eef_mask (B, N) tool particle: the edge builder's masks    */
+    uint8_t* d_eef_mask;
+    int64_t* d_material_index;     /* (B, max_nobj, n_mat): column mat_col is 1 on the sampled rows                       */
+    float* d_physics_param;        /* (B, phys_dim) = fp32(stored + noise): the noise goes to a copy, the stored value
+                                      never changes (the reference adds in place, dataset.py:261-266)                    */
+    float* d_thr2; float* d_cull;  /* (B,) each; written only with d_adj_thresh                                           */
+} ag_dataset_batch;
+/* One launch writes every output above, zero padding included; nothing else is allocated or staged. */
+int ag_dataset_assemble(ag_ctx* ctx, void* stream, const ag_dataset_batch* batch);
+
+/* B independent graphs under ag_build_edges_single's rule (construct_edges_from_states, graph.py:68-231, default arguments:
+ * threshold squared in double then rounded, connect_tools_all unconditional, no tool<->tool edge) in one launch pair.
+ *   d_pos        graph b's (N,3) positions start at d_pos + b * pos_bstride floats (0: N*3) - e.g. the last history frame of
+ *                a (B, n_his, N, 3) state
+ *   d_thr2       (B,) squared threshold per graph; d_cull_radius (B,) with cull^2 >= thr2 per graph (the caller's duty)
+ * Outputs as ag_build_edges: d_n_edges[b] is the TRUE count even above edge_cap (then nothing is written for graph b). */
+int ag_build_edges_graphs(ag_ctx* ctx, void* stream, const float* d_pos, int64_t pos_bstride, const uint8_t* d_mask,
+                          const uint8_t* d_tool_mask, int32_t B, int32_t N, const float* d_thr2, const float* d_cull_radius,
+                          int32_t topk, int32_t connect_tools_all, int32_t edge_cap, int32_t* d_recv, int32_t* d_send,
+                          int32_t* d_row_ptr, int32_t* d_n_edges);
+
 #ifdef __cplusplus
 }
 #endif

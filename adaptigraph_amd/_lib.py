@@ -32,7 +32,7 @@ EXPORTS = ["ag_abi_version", "ag_ctx_create", "ag_ctx_destroy", "ag_last_error",
            "ag_ctx_set_option", "ag_ctx_get_option", "ag_ctx_rollout_counts", "ag_rollout_actions", "ag_ctx_share_counts", "ag_ctx_launch_counts", "ag_cost_reward", "ag_cost_cloth_combine",
            "ag_ctx_alloc_counts", "ag_rollout_work", "ag_backward", "ag_backward_inputs", "ag_cost_chamfer_backward",
            "ag_ctx_load_weights_device", "ag_adam_step", "ag_train_step", "ag_ppm_grad_step", "ag_ppm_adam_step", "ag_train_step_part",
-           "ag_fps_batch", "ag_dataset_assemble", "ag_build_edges_graphs"]
+           "ag_fps_batch", "ag_dataset_assemble", "ag_build_edges_graphs", "ag_eval_step"]
 
 OPTIONS = ["streams", "chunk", "latency", "ragged", "ell_graph", "self_dedupe", "repeat_sort", "edge_wgs", "edge_block_min",
            "enc_persist", "stagger_us", "device_decode", "zigzag", "share_first", "share_prefix", "stream_min_rows", "pipeline_fork"]
@@ -58,6 +58,18 @@ class AgDatasetBatch(C.Structure):
                 [(n, C.c_void_p) for n in ("d_state", "d_action", "d_eef_future", "d_action_future", "d_state_future", "d_attrs",
                                            "d_p_instance", "d_obj_mask", "d_state_mask", "d_eef_mask", "d_material_index",
                                            "d_physics_param", "d_thr2", "d_cull")])
+
+
+class AgEvalStepArgs(C.Structure):
+    """ag_eval_step_args (include/adaptigraph_amd.h), field for field."""
+    _fields_ = ([(n, C.c_void_p) for n in ("d_state", "d_action", "d_attrs", "d_phys", "d_group", "d_recv", "d_send", "d_row_ptr",
+                                           "d_n_edges", "d_obj_pos", "d_eef_pos", "d_fps_idx", "d_n_obj", "d_frames", "d_state_mask",
+                                           "d_eef_mask", "d_thr2", "d_cull")] +
+                [(n, C.c_int64) for n in ("obj_points", "eef_points")] +
+                [(n, C.c_int32) for n in ("B", "max_nobj", "n_eef", "n_inst", "edge_cap", "edge_rows", "topk", "connect_tools_all",
+                                          "store_rest_state", "pred_given", "step", "err_stride")] +
+                [(n, C.c_void_p) for n in ("d_pred", "d_err", "d_state_next", "d_action_next", "d_recv_next", "d_send_next",
+                                           "d_row_ptr_next", "d_n_edges_next", "d_status")])
 
 
 _lib = None
@@ -122,6 +134,7 @@ def load():
     lib.ag_fps_batch.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp]
     lib.ag_dataset_assemble.argtypes = [vp, vp, C.POINTER(AgDatasetBatch)]
     lib.ag_build_edges_graphs.argtypes = [vp, vp, vp, C.c_int64, vp, vp, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp]
+    lib.ag_eval_step.argtypes = [vp, vp, C.POINTER(AgEvalStepArgs)]
     lib.ag_ctx_set_profiling.argtypes = [vp, i32]
     lib.ag_ctx_kernel_stats.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     lib.ag_ctx_reset_stats.argtypes = [vp]

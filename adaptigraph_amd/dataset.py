@@ -252,6 +252,26 @@ class DeviceDynDataset:
         mv = (lambda t: None if t is None else t.to(dev))
         return BatchDraws(mv(fps_start), mv(fps_radius), mv(rad_start), mv(phys_noise), mv(state_noise), mv(rot), mv(adj), mv(knn))
 
+    def eval_draws(self, idx, fps_start=None, rad_start=None):
+        """The BatchDraws of the eval rollout's construct_graph (rollout/graph.py:353-356): fps radius, adj threshold and kNN at
+        the MIDPOINT of their ranges, zero physics noise, no state noise, no rotation.  fps_start / rad_start: the two
+        farthest-point start indices, (B,) or one integer, default 0 (the reference draws them from numpy's global stream)."""
+        sp, dev = self.spec, self.device
+        B = len(np.asarray(idx).reshape(-1))
+        fr = sp.fps_radius_range
+        rad = fr if isinstance(fr, float) else (fr[0] + fr[1]) / 2
+        adj = (sp.adj_radius_range[0] + sp.adj_radius_range[1]) / 2
+        knn = (sp.knn_range[0] + sp.knn_range[1]) / 2
+
+        def start(v):
+            v = np.zeros(B, np.int32) if v is None else np.broadcast_to(np.asarray(v, np.int32), (B,)).copy()
+            return torch.from_numpy(v).to(dev)
+
+        full = (lambda v, dt: torch.full((B,), v, dtype=dt, device=dev))
+        return BatchDraws(start(fps_start), full(float(np.float32(rad)), torch.float32), start(rad_start),
+                          torch.zeros((B, self.phys_dim), dtype=torch.float64, device=dev), None, None,
+                          full(adj, torch.float64), full(knn, torch.float64))
+
     # ------------------------------------------------------------------------------------------ one batch
     def _sample_table(self, idx):
         """(B, 5 + T) int64, ag_dataset_batch::d_sample: [first point of the sampled cloud, N_e, first object point of the episode,
@@ -270,11 +290,12 @@ class DeviceDynDataset:
         return fps_batch(self._obj, tab[:, 0], tab[:, 1], dr.fps_start, dr.fps_radius, dr.rad_start, self.spec.max_nobj,
                          int(self._n_e.max()), engine=self.engine)
 
-    def batch(self, idx, draws=None, generator=None, dense=False):
+    def batch(self, idx, draws=None, generator=None, dense=False, with_fps=False):
         """The collated batch of the samples `idx` (a sequence of pair indices): state, action, eef_future, action_future,
         state_future, attrs, p_rigid, p_instance, obj_mask, material_index, <material>_physics_param as the reference's DataLoader
         collates them, plus edges (an EdgeList over the B graphs, every graph within max_nR) and max_edges (= max_nR).
         dense=True adds Rr / Rs, zero-padded to max_nR.  draws: a BatchDraws (default: self.draws(idx, generator)).
+        with_fps=True adds fps_idx (B, max_nobj) int32 (-1 behind the first n_obj[b] entries) and n_obj (B,) int32.
         Waits once, on the current stream, for the B edge counts (configs with a tool rule or a kNN range build their graphs
         sample by sample and wait more often)."""
         sp, dev, eng = self.spec, self.device, self.engine
@@ -318,10 +339,13 @@ class DeviceDynDataset:
         else:
             edges, trail = self._edges_per_sample(idx, out["state"], state_mask, eef_mask, fps_idx, n_obj, dr)
         self.last_trail = trail
+        self._last_build = dict(state_mask=state_mask, eef_mask=eef_mask, thr2=thr2, cull=cull)   # rollout_eval_batch reads them
         out["edges"] = edges
         out["max_edges"] = sp.max_nR
         if dense:
             out["Rr"], out["Rs"] = edges.to_dense(sp.max_nR)
+        if with_fps:
+            out["fps_idx"], out["n_obj"] = fps_idx, n_obj
         return out
 
     # ------------------------------------------------------------------------------------------ edges
@@ -345,6 +369,14 @@ class DeviceDynDataset:
         el = self._build_graphs(last, nh * N * 3, mask, tool, thr2, cull, sp.topk)
         counts = el.n_edges.cpu().numpy()                                                    # the one wait
         trail = [[(1.0, sp.topk, int(c))] for c in counts]
+        self._backoff(el, counts, state, mask, tool, thr2, cull, trail)
+        return el, trail
+
+    def _backoff(self, el, counts, state, mask, tool, thr2, cull, trail, waits=None):
+        """The graphs of `el` whose count exceeds max_nR, rebuilt in place as a sub-batch at top-k - 1, top-k - 2, ... from
+        state[:, -1] until they fit; every attempt is appended to the graph's trail.  waits: a one-element list that counts the
+        read-backs (one per attempt)."""
+        sp, N = self.spec, self.N
         over = np.nonzero(counts > sp.max_nR)[0]
         k = sp.topk
         while len(over):
@@ -356,6 +388,8 @@ class DeviceDynDataset:
             se = self._build_graphs(pos.data_ptr(), N * 3, mask[sub].contiguous(), tool[sub].contiguous(), thr2[sub].contiguous(),
                                     cull[sub].contiguous(), k)
             c = se.n_edges.cpu().numpy()
+            if waits is not None:
+                waits[0] += 1
             for j, b in enumerate(over):
                 trail[b].append((1.0, k, int(c[j])))
             fit = c <= sp.max_nR
@@ -364,7 +398,6 @@ class DeviceDynDataset:
                 dst = sub[src]
                 el.recv[dst], el.send[dst], el.row_ptr[dst], el.n_edges[dst] = se.recv[src], se.send[src], se.row_ptr[src], se.n_edges[src]
             over = over[~fit]
-        return el, trail
 
     def _edges_per_sample(self, idx, state, mask, tool, fps_idx, n_obj, dr):
         """Configs with a tool rule or a kNN range: sample by sample through construct_edges_with_backoff, stitched into one

@@ -602,6 +602,63 @@ int ag_build_edges_graphs(ag_ctx* ctx, void* stream, const float* d_pos, int64_t
                           int32_t topk, int32_t connect_tools_all, int32_t edge_cap, int32_t* d_recv, int32_t* d_send,
                           int32_t* d_row_ptr, int32_t* d_n_edges);
 
+/* ---- open-loop eval rollout (src/dynamics/rollout/rollout.py:103-260, rollout_from_start_graph's loop) for B rollouts at once.
+ * One call is one step of all B: the forward on the current graphs, the ground-truth error of its prediction, the next model
+ * input, and the next graphs at top-k `topk` into the OTHER half of the caller's double-buffered edge arrays.  Enqueue only: the
+ * caller reads d_n_edges_next back (its one wait per step), rebuilds the graphs above max_nR at a smaller top-k
+ * (ag_build_edges_graphs on d_state_next's last frames) and swaps the halves.  N = max_nobj + n_eef rows per graph. */
+typedef struct ag_eval_step_args {
+    /* the step's model input, as ag_forward takes it */
+    const float* d_state;          /* (B, n_his, N, 3)                                                                   */
+    const float* d_action;         /* (B, N, 3)                                                                          */
+    const float* d_attrs;          /* (B, N, 2)                                                                          */
+    const float* d_phys;           /* (B, N)                                                                             */
+    const float* d_group;          /* (B, N, n_inst)                                                                     */
+    const int32_t* d_recv;         /* (B, edge_cap); d_send alike; d_row_ptr (B, N + 1); d_n_edges (B,)                  */
+    const int32_t* d_send;
+    const int32_t* d_row_ptr;
+    const int32_t* d_n_edges;
+    /* ground truth and tool trajectory: the flat episode buffers of ag_dataset_batch and the sampling of the start graphs */
+    const float* d_obj_pos;        /* obj_points points                                                                  */
+    const float* d_eef_pos;        /* eef_points points                                                                  */
+    const int32_t* d_fps_idx;      /* (B, max_nobj), d_n_obj (B,): ag_fps_batch's outputs for the start graphs           */
+    const int32_t* d_n_obj;
+    const int64_t* d_frames;       /* (B, 3) for THIS step: [first object point of the frame the prediction is compared
+                                      with, first tool point of the next pair's start frame or -1 (the rollout ended), first
+                                      tool point of the next pair's end frame]                                           */
+    /* the edge builder's per-graph inputs (ag_build_edges_graphs) */
+    const uint8_t* d_state_mask;   /* (B, N) valid particle; d_eef_mask (B, N) tool particle                             */
+    const uint8_t* d_eef_mask;
+    const float* d_thr2;           /* (B,) squared threshold; d_cull (B,) culling radius, cull^2 >= thr2                 */
+    const float* d_cull;
+    int64_t obj_points, eef_points;   /* sizes of the two flat buffers in points: indices formed from d_frames are clamped */
+    int32_t B, max_nobj, n_eef, n_inst, edge_cap;
+    int32_t edge_rows;             /* every graph is promised to have at most this many edges (the back-off has run); a
+                                      graph beyond min(edge_cap, edge_rows) is presented empty and its count is raised into
+                                      d_status[0] (sticky atomic max, as ag_train_step)                                  */
+    int32_t topk, connect_tools_all, store_rest_state;
+    int32_t pred_given;            /* != 0: no forward, d_pred is an INPUT (the advance and the builder alone)           */
+    int32_t step, err_stride;      /* the error of graph b goes to d_err[step * err_stride + b]                          */
+    /* outputs */
+    float* d_pred;                 /* (B, max_nobj, 3): ag_forward's d_pred_pos, bit for bit                             */
+    float* d_err;                  /* fp32(mean over n < d_n_obj[b] of |pred[b,n] - obj_pos[frames[b,0] + fps_idx[b,n]]|):
+                                      differences, squares, sqrt and the sum in fp64 in a fixed order (no atomics), one
+                                      rounding; a NaN prediction gives NaN; d_n_obj[b] == 0 gives NaN                    */
+    float* d_state_next;           /* (B, n_his, N, 3), not d_state: history shifted by one (store_rest_state: frame 0 stays,
+                                      frame 1 leaves), last frame = all max_nobj predicted rows, then the n_eef tool rows of
+                                      the next start frame.  d_action_next (B, N, 3): zero on the object rows, the fp32
+                                      difference end - start on the tool rows.  A graph that ended writes neither.       */
+    float* d_action_next;
+    int32_t* d_recv_next;          /* the next graphs, as ag_build_edges_graphs writes them; d_n_edges_next[b] is the TRUE */
+    int32_t* d_send_next;          /* count even above edge_cap, and 0 for a graph that ended                            */
+    int32_t* d_row_ptr_next;
+    int32_t* d_n_edges_next;
+    int32_t* d_status;             /* [0]: see edge_rows                                                                 */
+} ag_eval_step_args;
+/* Limits: N <= 4096 (the LDS-resident edge builder), max_nobj <= 1024, topk as ag_build_edges; else AG_ERR_UNSUPPORTED before
+ * anything is enqueued.  The predictions are ag_forward's for the same B (same launch chunk, same kernels). */
+int ag_eval_step(ag_ctx* ctx, void* stream, const ag_eval_step_args* args);
+
 #ifdef __cplusplus
 }
 #endif

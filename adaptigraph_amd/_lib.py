@@ -21,7 +21,7 @@ AG_ERR_UNSUPPORTED = -4
 AG_ERR_NO_WEIGHTS = -5
 
 KERNEL_FAMILIES = ["edge_count", "edge_emit", "prep", "node_enc", "edge_enc", "mp", "node_prop", "node_final",
-                   "roll_init", "roll_update", "cost", "fps", "assemble"]
+                   "roll_init", "roll_update", "cost", "fps", "assemble", "rule"]
 
 # exactly the symbols include/adaptigraph_amd.h declares (tests/test_abi.py checks both directions)
 EXPORTS = ["ag_abi_version", "ag_ctx_create", "ag_ctx_destroy", "ag_last_error", "ag_ctx_load_weights",
@@ -32,7 +32,8 @@ EXPORTS = ["ag_abi_version", "ag_ctx_create", "ag_ctx_destroy", "ag_last_error",
            "ag_ctx_set_option", "ag_ctx_get_option", "ag_ctx_rollout_counts", "ag_rollout_actions", "ag_ctx_share_counts", "ag_ctx_launch_counts", "ag_cost_reward", "ag_cost_cloth_combine",
            "ag_ctx_alloc_counts", "ag_rollout_work", "ag_backward", "ag_backward_inputs", "ag_cost_chamfer_backward",
            "ag_ctx_load_weights_device", "ag_adam_step", "ag_train_step", "ag_ppm_grad_step", "ag_ppm_adam_step", "ag_train_step_part",
-           "ag_fps_batch", "ag_dataset_assemble", "ag_build_edges_graphs", "ag_eval_step"]
+           "ag_fps_batch", "ag_dataset_assemble", "ag_build_edges_graphs", "ag_eval_step",
+           "ag_edges_nonfixed_rule_graphs"]
 
 OPTIONS = ["streams", "chunk", "latency", "ragged", "ell_graph", "self_dedupe", "repeat_sort", "edge_wgs", "edge_block_min",
            "enc_persist", "stagger_us", "device_decode", "zigzag", "share_first", "share_prefix", "stream_min_rows", "pipeline_fork"]
@@ -70,6 +71,16 @@ class AgEvalStepArgs(C.Structure):
                                           "store_rest_state", "pred_given", "step", "err_stride")] +
                 [(n, C.c_void_p) for n in ("d_pred", "d_err", "d_state_next", "d_action_next", "d_recv_next", "d_send_next",
                                            "d_row_ptr_next", "d_n_edges_next", "d_status")])
+
+
+class AgRuleGraphsArgs(C.Structure):
+    """ag_rule_graphs_args (include/adaptigraph_amd.h), field for field."""
+    _fields_ = ([("d_pos", C.c_void_p), ("pos_bstride", C.c_int64)] +
+                [(n, C.c_void_p) for n in ("d_mask", "d_tool_mask", "d_send_in", "d_row_ptr_in", "d_n_edges_in", "d_kNN", "d_bounds_pos",
+                                           "d_bounds_first", "d_bounds_idx", "d_bounds_n")] +
+                [("bounds_points", C.c_int64), ("ratio", C.c_double)] +
+                [(n, C.c_int32) for n in ("B", "N", "n_tools", "base_cap", "idx_stride", "pad_rows", "edge_cap")] +
+                [(n, C.c_void_p) for n in ("d_recv", "d_send", "d_row_ptr", "d_n_edges_out", "d_thr")])
 
 
 _lib = None
@@ -135,6 +146,7 @@ def load():
     lib.ag_dataset_assemble.argtypes = [vp, vp, C.POINTER(AgDatasetBatch)]
     lib.ag_build_edges_graphs.argtypes = [vp, vp, vp, C.c_int64, vp, vp, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp]
     lib.ag_eval_step.argtypes = [vp, vp, C.POINTER(AgEvalStepArgs)]
+    lib.ag_edges_nonfixed_rule_graphs.argtypes = [vp, vp, C.POINTER(AgRuleGraphsArgs)]
     lib.ag_ctx_set_profiling.argtypes = [vp, i32]
     lib.ag_ctx_kernel_stats.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     lib.ag_ctx_reset_stats.argtypes = [vp]

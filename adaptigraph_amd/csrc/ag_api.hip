@@ -9,7 +9,7 @@ using namespace ag;
 namespace {
 
 const char* kFamilyNames[FAM_COUNT] = {"edge_count", "edge_emit", "prep", "node_enc", "edge_enc",
-                                       "mp", "node_prop", "node_final", "roll_init", "roll_update", "cost", "fps", "assemble"};
+                                       "mp", "node_prop", "node_final", "roll_init", "roll_update", "cost", "fps", "assemble", "rule"};
 
 struct OptName { const char* name; const char* env; int Options::* field; bool env_negates; int lo, hi; };
 const OptName kOptions[] = {
@@ -582,6 +582,41 @@ int ag_edges_apply_tool_rule(ag_ctx* c, void* stream, const float* d_pos, const 
     if (rc) return rc;
     a.recv = d_recv; a.send = d_send; a.row_ptr = d_row_ptr; a.n_out = d_n_out;
     HIPCHK(c, launch_tool_rule(a, st));
+    return AG_OK;
+}
+
+int ag_edges_nonfixed_rule_graphs(ag_ctx* c, void* stream, const ag_rule_graphs_args* p) {
+    if (!c) return AG_ERR_INVALID;
+    if (!p || !p->d_pos || !p->d_mask || !p->d_tool_mask || !p->d_send_in || !p->d_row_ptr_in || !p->d_n_edges_in || !p->d_kNN ||
+        !p->d_bounds_pos || !p->d_bounds_first || !p->d_bounds_n || !p->d_recv || !p->d_send || !p->d_row_ptr || !p->d_n_edges_out)
+        return fail(c, AG_ERR_INVALID, "ag_edges_nonfixed_rule_graphs: null pointer");
+    if (p->B < 1 || p->N < 1 || p->n_tools < 0 || p->n_tools > p->N || p->base_cap < 1 || p->edge_cap < 1 || p->bounds_points < 1 ||
+        p->pad_rows < 0 || (p->d_bounds_idx && p->idx_stride < 1))
+        return fail(c, AG_ERR_INVALID, "ag_edges_nonfixed_rule_graphs: bad sizes B=%d N=%d n_tools=%d base_cap=%d edge_cap=%d "
+                    "bounds_points=%lld pad_rows=%d idx_stride=%d", p->B, p->N, p->n_tools, p->base_cap, p->edge_cap,
+                    (long long)p->bounds_points, p->pad_rows, p->idx_stride);
+    if (p->pos_bstride != 0 && p->pos_bstride < (int64_t)p->N * 3)
+        return fail(c, AG_ERR_INVALID, "ag_edges_nonfixed_rule_graphs: pos_bstride %lld is below N*3 = %d", (long long)p->pos_bstride,
+                    p->N * 3);
+    if (p->N > 4096) return fail(c, AG_ERR_UNSUPPORTED, "ag_edges_nonfixed_rule_graphs: N=%d exceeds 4096", p->N);
+    if (p->n_tools > RULE_GRAPHS_MAX_TOOLS || (int64_t)p->N * p->n_tools > RULE_GRAPHS_MAX_PAIRS)
+        return fail(c, AG_ERR_UNSUPPORTED, "ag_edges_nonfixed_rule_graphs: N=%d x n_tools=%d exceeds the LDS-resident pair tables "
+                    "(at most %d tools and N * n_tools <= %d pairs)", p->N, p->n_tools, RULE_GRAPHS_MAX_TOOLS, RULE_GRAPHS_MAX_PAIRS);
+    if (p->d_send_in == p->d_send || p->d_row_ptr_in == p->d_row_ptr || p->d_n_edges_in == p->d_n_edges_out)
+        return fail(c, AG_ERR_INVALID, "ag_edges_nonfixed_rule_graphs: input and output arrays must differ");
+    SlotGuard call;
+    int rc = begin_call(c, stream, call);
+    if (rc) return rc;
+    RuleGraphsArgs a{};                                   // every table of a graph lives in its workgroup's LDS: no slab carve
+    a.pos = p->d_pos; a.pos_bstride = p->pos_bstride ? (long)p->pos_bstride : (long)p->N * 3; a.mask = p->d_mask; a.tool = p->d_tool_mask;
+    a.send_in = p->d_send_in; a.row_ptr_in = p->d_row_ptr_in; a.n_edges_in = p->d_n_edges_in; a.base_cap = p->base_cap;
+    a.B = p->B; a.N = p->N; a.n_tools = p->n_tools; a.edge_cap = p->edge_cap; a.kNN = p->d_kNN;
+    a.bnd_pos = p->d_bounds_pos; a.bnd_points = (long)p->bounds_points; a.bnd_first = (const long long*)p->d_bounds_first;
+    a.bnd_idx = p->d_bounds_idx; a.idx_stride = p->idx_stride; a.bnd_n = p->d_bounds_n; a.pad_rows = p->pad_rows;
+    a.ratio = (float)p->ratio;
+    a.recv = p->d_recv; a.send = p->d_send; a.row_ptr = p->d_row_ptr; a.n_out = p->d_n_edges_out; a.thr_out = p->d_thr;
+    { Scoped pr(c, FAM_RULE);
+      HIPCHK(c, launch_rule_graphs(a, call.st)); }
     return AG_OK;
 }
 

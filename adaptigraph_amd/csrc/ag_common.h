@@ -62,7 +62,7 @@ struct WeightLayout {
 
 // ---- kernel families (profiling ids) ------------------------------------------------------------------
 enum Family { FAM_EDGE_COUNT = 0, FAM_EDGE_EMIT, FAM_PREP, FAM_NODE_ENC, FAM_EDGE_ENC, FAM_MP, FAM_NODE_PROP,
-              FAM_NODE_FINAL, FAM_ROLL_INIT, FAM_ROLL_UPDATE, FAM_COST, FAM_FPS, FAM_ASSEMBLE, FAM_COUNT };
+              FAM_NODE_FINAL, FAM_ROLL_INIT, FAM_ROLL_UPDATE, FAM_COST, FAM_FPS, FAM_ASSEMBLE, FAM_RULE, FAM_COUNT };
 
 // ---- per-context tuning / A-B switches.  Defaults come from the environment ONCE, at ag_ctx_create (the AG_* name in
 // brackets); ag_ctx_set_option changes them per context afterwards.  None of them changes a result (bit-identical paths),
@@ -167,6 +167,22 @@ struct RuleArgs {
     int* recv; int* send; int* row_ptr; int* n_out;
 };
 hipError_t launch_tool_rule(const RuleArgs& a, hipStream_t st);
+// the non-fixed rule and its kNN filter for B graphs in one launch, one workgroup per graph (ag_rules_batch.hip); the tool list
+// and the (N, n_tools) pair tables of a graph live in LDS, which sets the two limits
+constexpr int RULE_GRAPHS_MAX_PAIRS = 8192;
+constexpr int RULE_GRAPHS_MAX_TOOLS = 64;
+struct RuleGraphsArgs {
+    const float* pos; long pos_bstride; const uint8_t* mask; const uint8_t* tool;   // as EdgeArgs
+    const int* send_in; const int* row_ptr_in; const int* n_edges_in; int base_cap; // the base graphs, (B, base_cap) / (B, N+1) / (B,)
+    int B, N, n_tools, edge_cap;
+    const double* kNN;                                                              // (B,)
+    // bounds source: graph b's threshold comes from the y of rows first[b] + (idx ? idx[b, r] : r), r < n[b], of a flat point
+    // buffer (indices clamped into it), plus a zero row iff pad_rows > n[b]
+    const float* bnd_pos; long bnd_points; const long long* bnd_first; const int* bnd_idx; int idx_stride; const int* bnd_n;
+    int pad_rows; float ratio;
+    int* recv; int* send; int* row_ptr; int* n_out; float* thr_out;                 // thr_out (B,) may be null
+};
+hipError_t launch_rule_graphs(const RuleGraphsArgs& a, hipStream_t st);
 hipError_t launch_edge_nonself(const int* recv, const int* send, const int* row_ptr, int B, int N, int edge_cap,
                                int* ns_edge, int* n_ns, const int* live, hipStream_t st);
 

@@ -3,7 +3,9 @@ batch at a time on the GPU.
 
 A batch is three launches on flat, unpadded episode buffers that were uploaded once - ag_fps_batch (both farthest-point stages),
 ag_dataset_assemble (every dense tensor, padding and augmentation included), ag_build_edges_graphs (B single-graph edge builds) -
-and ONE read-back of the B edge counts for the max_nR back-off.  The dict that comes out goes unchanged into
+and ONE read-back of the B edge counts for the max_nR back-off.  Configs with the tool-to-non-fixed rule or a kNN range
+(softbody) add one launch, ag_edges_nonfixed_rule_graphs, on the B base graphs; their back-off runs in rounds over the sub-batch
+that is still over max_nR, one read-back per round (graph.BackoffPlan).  The dict that comes out goes unchanged into
 TrainStep.step(data, max_edges=data['max_edges']), evaluate, accumulate and DynamicsPredictor(**data).
 
 Every random number of a batch is an explicit input (BatchDraws): a batch is a pure function of (idx, draws).  The default draws
@@ -29,7 +31,7 @@ import torch
 
 from . import _lib
 from .context import default_engine, ptr, current_stream, _require_gpu
-from .graph import EdgeList, construct_edges_with_backoff
+from .graph import EdgeList, BackoffPlan, RuleConfig, backoff_rounds, construct_edges_with_backoff, rule_attempt, rule_graphs_limit
 from .rollout import surface_bounds
 
 FPS_MAX_POINTS = 8192        # ag_fps_batch keeps a cloud in LDS (96 KB of the CU's 160 KB at this size)
@@ -64,7 +66,8 @@ class DatasetSpec:
 
     @property
     def batched_edges(self):
-        """No tool rule and no kNN range (rope, cloth, granular, bunnybath, multiobj): all B graphs in one launch."""
+        """No tool rule and no kNN range (rope, cloth, granular, bunnybath, multiobj): all B graphs in one launch and nothing
+        after it.  The other configs (softbody) add the batched rule launch and back off in rounds (_edges_rule_batched)."""
         return not self.connect_tool_all_non_fixed and not self.connect_tool_surface and self.min_kNN >= 1.0
 
 
@@ -215,6 +218,8 @@ class DeviceDynDataset:
         self._phys = torch.from_numpy(phys).to(dev)
         self._side = None
         self.last_trail = None
+        self.last_waits = None               # read-backs of the last batch(): 1 + back-off rounds (None: the per-sample path)
+        self._warned_rule_limit = False
 
     def __len__(self):
         return len(self._episode)
@@ -290,14 +295,16 @@ class DeviceDynDataset:
         return fps_batch(self._obj, tab[:, 0], tab[:, 1], dr.fps_start, dr.fps_radius, dr.rad_start, self.spec.max_nobj,
                          int(self._n_e.max()), engine=self.engine)
 
-    def batch(self, idx, draws=None, generator=None, dense=False, with_fps=False):
+    def batch(self, idx, draws=None, generator=None, dense=False, with_fps=False, per_sample_edges=False):
         """The collated batch of the samples `idx` (a sequence of pair indices): state, action, eef_future, action_future,
         state_future, attrs, p_rigid, p_instance, obj_mask, material_index, <material>_physics_param as the reference's DataLoader
         collates them, plus edges (an EdgeList over the B graphs, every graph within max_nR) and max_edges (= max_nR).
         dense=True adds Rr / Rs, zero-padded to max_nR.  draws: a BatchDraws (default: self.draws(idx, generator)).
         with_fps=True adds fps_idx (B, max_nobj) int32 (-1 behind the first n_obj[b] entries) and n_obj (B,) int32.
-        Waits once, on the current stream, for the B edge counts (configs with a tool rule or a kNN range build their graphs
-        sample by sample and wait more often)."""
+        Waits once, on the current stream, for the B edge counts, and once more per back-off round (last_waits).
+        per_sample_edges=True: configs with a tool rule or a kNN range build their graphs sample by sample through
+        construct_edges_with_backoff, with several waits per sample - the A/B partner of the batched rule path, and what a config
+        beyond ag_edges_nonfixed_rule_graphs' size limit falls back to (with one warning)."""
         sp, dev, eng = self.spec, self.device, self.engine
         idx = np.asarray(idx, np.int64).reshape(-1)
         if len(idx) < 1 or idx.min() < 0 or idx.max() >= len(self):
@@ -334,10 +341,22 @@ class DeviceDynDataset:
         out["material_index"] = material_index
         for name, dim in self.materials.items():                                             # dataset.py:377-381
             out[name + "_physics_param"] = phys if name == sp.material else torch.zeros((B, dim), **f32)
+        limit = rule_graphs_limit(N, self.n_eef) if sp.connect_tool_all_non_fixed else None
+        if limit is not None and not sp.batched_edges and not per_sample_edges:
+            if not self._warned_rule_limit:
+                import warnings
+                warnings.warn(f"DeviceDynDataset: {limit}; the graphs of this config are built sample by sample", RuntimeWarning)
+                self._warned_rule_limit = True
+            per_sample_edges = True
         if sp.batched_edges:
-            edges, trail = self._edges_batched(out["state"], state_mask, eef_mask, thr2, cull)
-        else:
+            waits = [1]
+            edges, trail = self._edges_batched(out["state"], state_mask, eef_mask, thr2, cull, waits)
+            self.last_waits = waits[0]
+        elif per_sample_edges:
             edges, trail = self._edges_per_sample(idx, out["state"], state_mask, eef_mask, fps_idx, n_obj, dr)
+            self.last_waits = None
+        else:
+            edges, trail = self._edges_rule_batched(out["state"], state_mask, eef_mask, thr2, cull, tab, fps_idx, n_obj, dr)
         self.last_trail = trail
         self._last_build = dict(state_mask=state_mask, eef_mask=eef_mask, thr2=thr2, cull=cull)   # rollout_eval_batch reads them
         out["edges"] = edges
@@ -349,9 +368,9 @@ class DeviceDynDataset:
         return out
 
     # ------------------------------------------------------------------------------------------ edges
-    def _build_graphs(self, pos, bstride, mask, tool, thr2, cull, topk):
+    def _build_graphs(self, pos, bstride, mask, tool, thr2, cull, topk, cap=None):
         sp, dev, eng = self.spec, self.device, self.engine
-        B, N, cap = mask.shape[0], self.N, max(1, sp.max_nR)
+        B, N, cap = mask.shape[0], self.N, max(1, sp.max_nR if cap is None else cap)
         recv = torch.empty((B, cap), dtype=torch.int32, device=dev)
         send = torch.empty((B, cap), dtype=torch.int32, device=dev)
         row_ptr = torch.empty((B, N + 1), dtype=torch.int32, device=dev)
@@ -361,7 +380,7 @@ class DeviceDynDataset:
                                                 ptr(row_ptr), ptr(n_edges)))
         return EdgeList(recv, send, row_ptr, n_edges, N)
 
-    def _edges_batched(self, state, mask, tool, thr2, cull):
+    def _edges_batched(self, state, mask, tool, thr2, cull, waits=None):
         """All B graphs at top-k, one read-back of the counts; the graphs over max_nR are rebuilt as a sub-batch at top-k - 1,
         top-k - 2, ... until they fit (dataset.py:317-349 with kNN at its minimum)."""
         sp, N, nh = self.spec, self.N, self.spec.n_his
@@ -369,8 +388,41 @@ class DeviceDynDataset:
         el = self._build_graphs(last, nh * N * 3, mask, tool, thr2, cull, sp.topk)
         counts = el.n_edges.cpu().numpy()                                                    # the one wait
         trail = [[(1.0, sp.topk, int(c))] for c in counts]
-        self._backoff(el, counts, state, mask, tool, thr2, cull, trail)
+        self._backoff(el, counts, state, mask, tool, thr2, cull, trail, waits)
         return el, trail
+
+    def _edges_rule_batched(self, state, mask, tool, thr2, cull, tab, fps_idx, n_obj, dr):
+        """Configs with the non-fixed rule and / or a kNN range.  All B base graphs at top-k into buffers of the structural bound
+        (the rule removes edges as well as adding them, so max_nR is no capacity for its input), ONE rule launch into max_nR-wide
+        buffers, one read-back of the counts (with the kNN draws).  Then graph.BackoffPlan's rounds over the sub-batch that is
+        still over max_nR: a graph whose kNN went down reruns the rule on its unchanged base graph, graphs whose top-k went down
+        share one base launch per top-k; one read-back per round (dataset.py:317-349).  The bounds of the rule's threshold are
+        the un-augmented rows of frame n_his - 1, padding zeros included (dataset.py:186-209); min_x / min_z are never passed
+        on (dataset.py:310-314), so connect_tool_surface cannot fire here."""
+        sp, N, nh = self.spec, self.N, self.spec.n_his
+        B, rule, cap = mask.shape[0], sp.connect_tool_all_non_fixed, max(1, sp.max_nR)
+        k = min(N, sp.topk)
+        base_cap = max(1, N * (k + self.n_eef) if k < N else N * N) if rule else cap
+        last = state.data_ptr() + (nh - 1) * N * 3 * 4                                       # state[:, -1] in place
+        bnd = (self._obj, tab[:, 0].contiguous(), fps_idx, n_obj, sp.max_nobj)
+        base = self._build_graphs(last, nh * N * 3, mask, tool, thr2, cull, sp.topk, cap=base_cap)
+        el = self._ruled(last, nh * N * 3, mask, tool, base, dr.knn_thresh, bnd, cap)
+        host = torch.cat([dr.knn_thresh, el.n_edges.to(torch.float64)]).cpu().numpy()        # the one wait
+        plan = BackoffPlan(host[:B], sp.topk, sp.max_nR, sp.min_kNN, sp.knn_increment, has_rule=rule)
+        plan.record(host[B:].astype(np.int64))
+        self._rule_rounds(plan, el, base, state, mask, tool, thr2, cull, bnd)
+        self.last_waits = plan.rounds
+        return el, [[(float(a), int(kk), int(c)) for a, kk, c in t] for t in plan.trail]
+
+    def _rule_config(self):
+        sp = self.spec
+        return RuleConfig(sp.connect_tool_all_non_fixed, self.n_eef, sp.connect_tool_surface_ratio, sp.connect_tool_all, self.engine)
+
+    def _ruled(self, pos, bstride, mask, tool, base, knn, bnd, cap, out=None):
+        return rule_attempt(self._rule_config(), pos, bstride, mask, tool, base, knn, bnd, cap, out=out)
+
+    def _rule_rounds(self, plan, el, base, state, mask, tool, thr2, cull, bnd):
+        backoff_rounds(self._rule_config(), plan, el, base, state[:, -1], mask, tool, thr2, cull, bnd)
 
     def _backoff(self, el, counts, state, mask, tool, thr2, cull, trail, waits=None):
         """The graphs of `el` whose count exceeds max_nR, rebuilt in place as a sub-batch at top-k - 1, top-k - 2, ... from

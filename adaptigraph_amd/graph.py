@@ -253,6 +253,201 @@ def construct_edges_with_backoff(states, adj_thresh, mask, tool_mask, topk, max_
             k_now = topk
 
 
+def construct_edges_graphs(pos, pos_bstride, mask_u8, tool_u8, thr2, cull, topk, connect_tools_all=False, edge_cap=None, engine=None):
+    """ag_build_edges_graphs: B independent graphs under the single-graph builder's rule in one launch -> EdgeList.  pos: a float32
+    tensor (B, N, 3) or a device address with pos_bstride floats between graphs (0: N * 3); thr2 / cull (B,) float32: the squared
+    threshold fp32(adj * adj in double) and a culling radius with cull^2 >= thr2; edge_cap defaults to the structural bound
+    N * (min(topk, N) + tools).  Enqueue only; n_edges[b] is the TRUE count even above edge_cap."""
+    dev = mask_u8.device
+    eng = engine or default_engine(dev)
+    B, N = mask_u8.shape
+    if edge_cap is None:
+        k = min(N, int(topk))
+        edge_cap = N * (k + int(tool_u8[0].sum().item())) if k < N else N * N
+    edge_cap = max(1, int(edge_cap))
+    recv = torch.empty((B, edge_cap), device=dev, dtype=torch.int32)
+    send = torch.empty((B, edge_cap), device=dev, dtype=torch.int32)
+    row_ptr = torch.empty((B, N + 1), device=dev, dtype=torch.int32)
+    n_edges = torch.empty((B,), device=dev, dtype=torch.int32)
+    eng.check(eng.lib.ag_build_edges_graphs(eng.ctx, current_stream(dev), pos if isinstance(pos, int) else pos.data_ptr(),
+                                            int(pos_bstride), ptr(mask_u8), ptr(tool_u8), B, N, ptr(thr2), ptr(cull), int(topk),
+                                            int(bool(connect_tools_all)), edge_cap, ptr(recv), ptr(send), ptr(row_ptr), ptr(n_edges)))
+    return EdgeList(recv, send, row_ptr, n_edges, N)
+
+
+RULE_GRAPHS_MAX_PAIRS = 8192   # ag_edges_nonfixed_rule_graphs keeps a graph's (N, n_tools) pair tables in LDS
+RULE_GRAPHS_MAX_TOOLS = 64
+
+
+def rule_graphs_limit(N, n_tools):
+    """None when ag_edges_nonfixed_rule_graphs takes graphs of N particles with n_tools tool points, else the limit in words."""
+    if N > 4096:
+        return f"N = {N} exceeds 4096"
+    if n_tools > RULE_GRAPHS_MAX_TOOLS or N * n_tools > RULE_GRAPHS_MAX_PAIRS:
+        return (f"N * n_tools = {N} * {n_tools} exceeds the LDS-resident pair tables (at most {RULE_GRAPHS_MAX_TOOLS} tool points and "
+                f"{RULE_GRAPHS_MAX_PAIRS} pairs)")
+    return None
+
+
+def nonfixed_rule_graphs(pos, pos_bstride, mask_u8, tool_u8, base, n_tools, kNN, bounds_pos, bounds_first, bounds_idx, bounds_n,
+                         pad_rows, ratio, edge_cap, engine=None, out=None, thr_out=None):
+    """ag_edges_nonfixed_rule_graphs: the non-fixed rule (graph.py:125-171) and its kNN filter on the B base graphs `base` (an
+    EdgeList as ag_build_edges_graphs wrote it) -> new EdgeList of capacity edge_cap.  Enqueue only.
+    pos: a float32 tensor (B, N, 3) or a device address, graph b at + b * pos_bstride floats (0: N * 3); mask_u8 / tool_u8 (B, N)
+    uint8; kNN (B,) float64; the bounds source: bounds_pos flat (P, 3) float32, bounds_first (B,) int64, bounds_idx (B, stride) int32
+    or None, bounds_n (B,) int32, pad_rows, ratio (include/adaptigraph_amd.h).  out: an EdgeList to write into; thr_out: (B,)
+    float32 that receives the thresholds.  n_edges[b] = -1 marks a refused graph: raise where the counts are read."""
+    import ctypes as C
+    from . import _lib
+    dev = mask_u8.device
+    eng = engine or default_engine(dev)
+    B, N = mask_u8.shape
+    for t, dt, shape in ((mask_u8, torch.uint8, (B, N)), (tool_u8, torch.uint8, (B, N)), (kNN, torch.float64, (B,)),
+                         (bounds_first, torch.int64, (B,)), (bounds_n, torch.int32, (B,)), (base.n_edges, torch.int32, (B,)),
+                         (base.row_ptr, torch.int32, (B, N + 1))):
+        assert t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev, (t.dtype, tuple(t.shape), shape)
+    assert base.send.dtype == torch.int32 and base.send.shape[0] == B and base.send.is_contiguous()
+    assert bounds_pos.dtype == torch.float32 and bounds_pos.is_contiguous() and bounds_pos.shape[-1] == 3
+    assert bounds_idx is None or (bounds_idx.dtype == torch.int32 and bounds_idx.shape[0] == B and bounds_idx.is_contiguous())
+    edge_cap = max(1, int(edge_cap))
+    if out is None:
+        out = EdgeList(torch.empty((B, edge_cap), device=dev, dtype=torch.int32), torch.empty((B, edge_cap), device=dev, dtype=torch.int32),
+                       torch.empty((B, N + 1), device=dev, dtype=torch.int32), torch.empty((B,), device=dev, dtype=torch.int32), N)
+    assert out.edge_cap == edge_cap and out.recv.shape[0] == B
+    a = _lib.AgRuleGraphsArgs()
+    a.d_pos = pos if isinstance(pos, int) else pos.data_ptr()
+    a.pos_bstride = int(pos_bstride)
+    for name, t in (("d_mask", mask_u8), ("d_tool_mask", tool_u8), ("d_send_in", base.send), ("d_row_ptr_in", base.row_ptr),
+                    ("d_n_edges_in", base.n_edges), ("d_kNN", kNN), ("d_bounds_pos", bounds_pos), ("d_bounds_first", bounds_first),
+                    ("d_bounds_idx", bounds_idx), ("d_bounds_n", bounds_n), ("d_recv", out.recv), ("d_send", out.send),
+                    ("d_row_ptr", out.row_ptr), ("d_n_edges_out", out.n_edges), ("d_thr", thr_out)):
+        setattr(a, name, t.data_ptr() if t is not None else None)
+    a.bounds_points = bounds_pos.numel() // 3
+    a.ratio = float(ratio)
+    a.B, a.N, a.n_tools, a.base_cap, a.edge_cap = B, N, int(n_tools), base.edge_cap, edge_cap
+    a.idx_stride = bounds_idx.shape[1] if bounds_idx is not None else 0
+    a.pad_rows = int(pad_rows)
+    eng.check(eng.lib.ag_edges_nonfixed_rule_graphs(eng.ctx, current_stream(dev), C.byref(a)))
+    return out
+
+
+class BackoffPlan:
+    """The max_nR back-off of construct_edges_with_backoff (dataset.py:317-349, rollout.py:173-222) for B graphs at once, as a
+    pure host state machine: it is told the edge counts of an attempt and says which graphs need another one, and with what.
+
+        plan = BackoffPlan(knn, topk, max_nR, min_kNN, knn_increment)
+        while plan.active:                      # graph indices of this round's attempt
+            counts = <attempt: graph b at plan.kNN[b] and top-k plan.k_now[b]; plan.rebuild[b]: its base graph changes too>
+            plan.record(counts)
+
+    Per graph: while kNN > min_kNN, kNN -= knn_increment (Python doubles) at the ORIGINAL top-k - the base graph is unchanged, only
+    the rule reruns; after that top-k goes down by one per attempt with kNN left where it stopped; below top-k 1 it raises
+    Exception('Exceeds max dims').  trail[b] holds (kNN, topk, n_rel) of every attempt.  has_rule=False (a kNN range without the
+    non-fixed rule): a kNN attempt rebuilds nothing, so it is recorded with the unchanged count and costs no round.
+    rounds: the number of record() calls = read-backs."""
+
+    def __init__(self, knn, topk, max_nR, min_kNN=1.0, knn_increment=0.1, has_rule=True):
+        self.kNN = [float(v) for v in knn]
+        B = len(self.kNN)
+        self.topk, self.max_nR, self.min_kNN, self.knn_increment = int(topk), int(max_nR), float(min_kNN), float(knn_increment)
+        self.has_rule = bool(has_rule)
+        self.k_now = [self.topk] * B
+        self._decrease_topK = [self.topk] * B
+        self.rebuild = [True] * B
+        self.trail = [[] for _ in range(B)]
+        self.active = list(range(B))
+        self.rounds = 0
+
+    def record(self, counts):
+        """counts[j]: the edge count of graph self.active[j] in the attempt just made.  Returns the graphs of it that now fit."""
+        assert len(counts) == len(self.active)
+        nxt, fits = [], []
+        for b, c in zip(self.active, counts):
+            c = int(c)
+            if c < 0:
+                raise RuntimeError("internal: ag_edges_nonfixed_rule_graphs refused a graph (base edge list or tool count inconsistent)")
+            while True:
+                self.trail[b].append((self.kNN[b], self.k_now[b], c))
+                if c <= self.max_nR:
+                    fits.append(b)
+                    break
+                if self.kNN[b] <= self.min_kNN:
+                    self._decrease_topK[b] -= 1
+                    if self._decrease_topK[b] < 1:
+                        raise Exception("Exceeds max dims")                              # (the reference would loop on: utils.py:63-65)
+                    self.k_now[b], self.rebuild[b] = self._decrease_topK[b], True
+                    nxt.append(b)
+                    break
+                self.kNN[b] = self.kNN[b] - self.knn_increment
+                self.k_now[b], self.rebuild[b] = self.topk, False
+                if self.has_rule:
+                    nxt.append(b)
+                    break
+        self.active = nxt
+        self.rounds += 1
+        return fits
+
+
+@dataclass
+class RuleConfig:
+    """What an attempt of the batched back-off needs besides its graphs: is the non-fixed rule on (else only the base graphs are
+    built), the tool points per graph, connect_tool_surface_ratio, connect_tool_all, the engine."""
+    rule: bool
+    n_tools: int
+    ratio: float
+    connect_tools_all: bool = False
+    engine: object = None
+
+
+def rule_attempt(cfg, pos, bstride, mask, tool, base, knn, bnd, cap, out=None):
+    """The non-fixed rule on the base graphs -> EdgeList of capacity cap (the base graphs themselves for a config without the
+    rule).  bnd: the bounds source (flat points, first (B,) int64, gather (B, stride) int32 or None, rows (B,) int32, pad_rows)."""
+    if not cfg.rule:
+        return base
+    pts, first, idx, n, pad_rows = bnd
+    return nonfixed_rule_graphs(pos, bstride, mask, tool, base, cfg.n_tools, knn, pts, first, idx, n, pad_rows, cfg.ratio, cap,
+                                engine=cfg.engine, out=out)
+
+
+def backoff_rounds(cfg, plan, el, base, last, mask, tool, thr2, cull, bnd):
+    """BackoffPlan's rounds after the first attempt: per round the sub-batch plan.active, one group per top-k (the kNN group reruns
+    the rule on its rows of `base`, a lower top-k rebuilds the base graphs from `last`, the (B, N, 3) positions), ONE read-back of
+    the round's counts, and the graphs that now fit are copied into their rows of `el`.  Rows of el / base / last / mask / tool /
+    thr2 / cull / bnd correspond; a graph fits when its count is within plan.max_nR, whatever el's capacity."""
+    N, dev = el.N, mask.device
+    pts, first, idx, n_rows, pad_rows = bnd
+    while plan.active:
+        groups = {}
+        for b in plan.active:
+            groups.setdefault(plan.k_now[b], []).append(b)
+        groups = [groups[kk] for kk in sorted(groups, reverse=True)]                         # graphs that share a top-k share a launch
+        parts = []
+        for g in groups:
+            kk = plan.k_now[g[0]]
+            sub = torch.tensor(g, dtype=torch.int64).to(dev)
+            pos, m, t = last[sub].contiguous(), mask[sub].contiguous(), tool[sub].contiguous()
+            if kk == plan.topk:                                                              # kNN went down: the base graph stands
+                b_el = EdgeList(base.recv[sub], base.send[sub], base.row_ptr[sub], base.n_edges[sub], N)
+            else:
+                b_el = construct_edges_graphs(pos, 0, m, t, thr2[sub].contiguous(), cull[sub].contiguous(), kk, cfg.connect_tools_all,
+                                              edge_cap=base.edge_cap, engine=cfg.engine)
+            knn = torch.tensor([plan.kNN[b] for b in g], dtype=torch.float64).to(dev)
+            sub_bnd = (pts, first[sub], None if idx is None else idx[sub], n_rows[sub], pad_rows)
+            parts.append((sub, rule_attempt(cfg, pos, 0, m, t, b_el, knn, sub_bnd, el.edge_cap)))
+        counts = torch.cat([se.n_edges for _, se in parts]).cpu().numpy()                    # one wait per round
+        plan.active = [b for g in groups for b in g]                                         # the order of `counts`
+        plan.record(counts)
+        off = 0
+        for sub, se in parts:
+            c = counts[off:off + len(sub)]
+            off += len(sub)
+            fit = (c <= plan.max_nR).nonzero()[0]
+            if len(fit):
+                src = torch.from_numpy(fit).to(dev)
+                dst = sub[src]
+                el.recv[dst], el.send[dst], el.row_ptr[dst], el.n_edges[dst] = se.recv[src], se.send[src], se.row_ptr[src], se.n_edges[src]
+
+
 def pad_torch(x, max_dim, dim=0):
     """src/dynamics/utils.py:49-69: zero-pad `dim` to max_dim, raise Exception('Exceeds max dims') when larger."""
     if dim == 0:

@@ -148,7 +148,7 @@ class EvalResult:
     pred: torch.Tensor | None = None   # (L_max, B, max_nobj, 3) with keep_pred; NaN behind each rollout's length
     edges: list | None = None     # with keep_pred: per step an EdgeList over the B graphs prediction i ran on (ended: 0 edges)
     host_waits: int = 0           # read-backs of the step loop: one per step (the counts; after the last step the status word)
-                                  # plus one per back-off attempt.  The start batch's own waits are DeviceDynDataset.batch's.
+                                  # plus one per back-off attempt (rule configs: per back-off round).  The start batch's own waits are DeviceDynDataset.batch's.
 
     def step_error(self):
         """rollout.py:439-444: the (min_step, B) float64 matrix of the steps every rollout reached (what error_short.txt holds)."""
@@ -217,9 +217,11 @@ def rollout_eval_batch(model, ds, idx, rollout_steps=100, draws=None, keep_pred=
     that go on, the sub-batch back-off at top-k - 1, ... for those over max_nR (Exception("Exceeds max dims") at top-k < 1), the
     swap.  A graph beyond max_nR never reaches a forward; the status word ag_eval_step raises if one did is checked at the end.
 
-    Configs with a tool rule or a kNN range (spec.batched_edges false), or per_graph=True, take the same start batch through
-    rollout_eval_step graph by graph, the error from the same kernel at B = 1: correct and slow (several waits per step and
-    graph).  keep_pred: also return every prediction and every step's edge lists.  keep_prev_fps and hetero of the reference's
+    Configs with the non-fixed rule and / or a kNN range advance together as well (_eval_rule_batched: after ag_eval_step the rule
+    launch ag_edges_nonfixed_rule_graphs, fed from d_state_next, then the back-off in rounds; host_waits = steps + extra rounds).
+    Configs with connect_tool_surface (that rule can fire here and has no batched form), configs beyond the rule kernel's size
+    limit, or per_graph=True, take the same start batch through rollout_eval_step graph by graph, the error from the same kernel
+    at B = 1: correct and slow (several waits per step and graph).  keep_pred: also return every prediction and every step's edge lists.  keep_prev_fps and hetero of the reference's
     script are out of scope: every start pair samples its own points, the physics parameter is the episode's."""
     sp, dev = ds.spec, ds.device
     idx = np.asarray(idx, np.int64).reshape(-1)
@@ -260,8 +262,15 @@ def rollout_eval_batch(model, ds, idx, rollout_steps=100, draws=None, keep_pred=
                 tab[i, j, 1] = ds._eef_off[e] + sch[i + 1][0] * ds.n_eef
                 tab[i, j, 2] = ds._eef_off[e] + sch[i + 1][1] * ds.n_eef
     waits = [0]
-    if per_graph or not sp.batched_edges:
+    from .graph import rule_graphs_limit
+    rule_cfg = not sp.batched_edges                  # the non-fixed rule and / or a kNN range
+    # connect_tool_surface can fire in the eval rollout (all six bounds are passed on), and it has no batched form
+    rule_batched = rule_cfg and not sp.connect_tool_surface and not (sp.connect_tool_all_non_fixed and rule_graphs_limit(N, ds.n_eef))
+    if per_graph or (rule_cfg and not rule_batched):
         _eval_per_graph(model, ds, eng, data, aux, dr, order, scheds, tab, errors, pred, kept, trails, keep_pred)
+    elif rule_cfg:
+        _eval_rule_batched(ds, eng, data, aux, (attrs, action, phys, group, edges), lengths[order], tab, errors, pred, kept, trails,
+                           keep_pred, waits)
     else:
         tab_d = torch.from_numpy(tab).to(dev)
         status = torch.zeros(4, dtype=torch.int32, device=dev)
@@ -322,6 +331,77 @@ def rollout_eval_batch(model, ds, idx, rollout_steps=100, draws=None, keep_pred=
     for j, r in enumerate(order):
         out_trails[r] = trails[j]
     return EvalResult(out_err, lengths, scheds, out_trails, out_pred, out_edges, waits[0])
+
+
+def _eval_rule_batched(ds, eng, data, aux, inputs, len_s, tab, errors, pred, kept, trails, keep_pred, waits):
+    """rollout_eval_batch's step loop for configs with the non-fixed rule and / or a kNN range (and without connect_tool_surface).
+    Per step: ag_eval_step unchanged - it writes the BASE next graphs at top-k into the second edge buffer -, then
+    ag_edges_nonfixed_rule_graphs on the graphs that go on, fed from d_state_next (bounds: the predicted rows of its last frame,
+    rollout.py:125-133; kNN: the start graph's draw, the config's midpoint), back into the first edge buffer, which the next
+    step's forward reads; one read-back of their counts, then graph.BackoffPlan's rounds (DeviceDynDataset._rule_rounds) on those
+    over max_nR.  Both edge buffers are max(max_nR, structural bound) wide - the rule can remove edges, so its input may exceed
+    max_nR - and ag_eval_step is told edge_rows = max_nR; a config without the rule keeps the max_nR-wide double buffer."""
+    from .graph import BackoffPlan
+    sp, dev, N, nh = ds.spec, ds.device, ds.N, ds.spec.n_his
+    attrs, action, phys, group, edges = inputs
+    L_max, B = errors.shape
+    rule, cap = sp.connect_tool_all_non_fixed, max(1, sp.max_nR)
+    k = min(N, sp.topk)
+    ecap = max(cap, N * (k + ds.n_eef) if k < N else N * N) if rule else cap
+    i32 = dict(dtype=torch.int32, device=dev)
+    el = [EdgeList(torch.zeros((B, ecap), **i32), torch.zeros((B, ecap), **i32), edges.row_ptr.clone(), edges.n_edges.clone(), N),
+          EdgeList(torch.zeros((B, ecap), **i32), torch.zeros((B, ecap), **i32), torch.zeros_like(edges.row_ptr),
+                   torch.zeros_like(edges.n_edges), N)]
+    el[0].recv[:, :cap], el[0].send[:, :cap] = edges.recv, edges.send
+    knn_host = [t[0][0][0] for t in trails]                                              # the start graphs' own kNN draws
+    knn_dev = torch.tensor(knn_host, dtype=torch.float64).to(dev)
+    first = torch.arange(B, dtype=torch.int64, device=dev) * (nh * N) + (nh - 1) * N     # last frame of d_state_next, in points
+    view = (lambda e, n: EdgeList(e.recv[:n], e.send[:n], e.row_ptr[:n], e.n_edges[:n], N))
+    tab_d = torch.from_numpy(tab).to(dev)
+    status = torch.zeros(4, **i32)
+    state = [data["state"], data["state"].clone()]
+    act = [action, action.clone()]
+    cur = ec = 0                                                                          # state / action half, edge buffer read
+    for s in range(L_max):
+        Bs, Bn = int((len_s > s).sum()), int((len_s > s + 1).sum())
+        nxt, en = 1 - cur, 1 - ec
+        if keep_pred:
+            kept.append(EdgeList(el[ec].recv[:, :cap].clone(), el[ec].send[:, :cap].clone(), el[ec].row_ptr.clone(), el[ec].n_edges.clone(), N))
+            kept[-1].n_edges[Bs:] = 0
+        a = _eval_step_args(ds, Bs, sp.topk, ecap)
+        a.d_state, a.d_action, a.d_attrs, a.d_phys, a.d_group = (t.data_ptr() for t in (state[cur], act[cur], attrs, phys, group))
+        a.d_recv, a.d_send, a.d_row_ptr, a.d_n_edges = (t.data_ptr() for t in (el[ec].recv, el[ec].send, el[ec].row_ptr, el[ec].n_edges))
+        a.d_fps_idx, a.d_n_obj, a.d_frames = data["fps_idx"].data_ptr(), data["n_obj"].data_ptr(), tab_d[s].data_ptr()
+        a.d_state_mask, a.d_eef_mask = aux["state_mask"].data_ptr(), aux["eef_mask"].data_ptr()
+        a.d_thr2, a.d_cull = aux["thr2"].data_ptr(), aux["cull"].data_ptr()
+        a.pred_given, a.step, a.err_stride = 0, s, B
+        a.d_pred, a.d_err = pred[s if keep_pred else 0].data_ptr(), errors.data_ptr()
+        a.d_state_next, a.d_action_next = state[nxt].data_ptr(), act[nxt].data_ptr()
+        a.d_recv_next, a.d_send_next, a.d_row_ptr_next, a.d_n_edges_next = (
+            t.data_ptr() for t in (el[en].recv, el[en].send, el[en].row_ptr, el[en].n_edges))
+        a.d_status = status.data_ptr()
+        eng.check(eng.lib.ag_eval_step(eng.ctx, current_stream(dev), C.byref(a)))
+        if Bn > 0:
+            base = view(el[en], Bn)
+            bnd = (state[nxt].view(-1, 3), first[:Bn], None, data["n_obj"][:Bn], 0)
+            mask, tool = aux["state_mask"][:Bn], aux["eef_mask"][:Bn]
+            # (the forward that read el[ec] is ahead of the rule on the stream: its buffer is free to take the ruled graphs)
+            out = ds._ruled(state[nxt].data_ptr() + (nh - 1) * N * 3 * 4, nh * N * 3, mask, tool, base, knn_dev[:Bn], bnd, ecap,
+                            out=view(el[ec], Bn))
+            counts = out.n_edges.cpu().numpy()                                            # the step's one wait
+            plan = BackoffPlan(knn_host[:Bn], sp.topk, sp.max_nR, sp.min_kNN, sp.knn_increment, has_rule=rule)
+            plan.record(counts)
+            ds._rule_rounds(plan, out, base, state[nxt][:Bn], mask, tool, aux["thr2"][:Bn], aux["cull"][:Bn], bnd)
+            waits[0] += plan.rounds
+            for j in range(Bn):
+                trails[j].append([(float(p), int(kk), int(c)) for p, kk, c in plan.trail[j]])
+            if not rule:
+                ec = en
+        cur = nxt
+    seen = int(status[:1].cpu()[0])                                                      # the last step's wait: the status word
+    waits[0] += 1
+    if seen > 0:
+        raise Exception("Exceeds max dims")
 
 
 def _eval_per_graph(model, ds, eng, data, aux, dr, order, scheds, tab, errors, pred, kept, trails, keep_pred):

@@ -659,6 +659,51 @@ typedef struct ag_eval_step_args {
  * anything is enqueued.  The predictions are ag_forward's for the same B (same launch chunk, same kernels). */
 int ag_eval_step(ag_ctx* ctx, void* stream, const ag_eval_step_args* args);
 
+/* ---- the "tool to all non-fixed particles" rule (graph.py:125-171) and its flat kNN filter for B graphs in one launch.
+ * Semantics are ag_edges_apply_tool_rule's, per graph b, with the subset S = d_mask AND (y > thr[b]) formed on the device:
+ *   the rule applies only if the base list holds at least one edge whose sender is a tool (graph.py:128-135), otherwise the base
+ *   graph is copied through; with 0 < d_kNN[b] < 1 only keepK = (int)(kNN * #pairs) (in double) of the (receiver in S <- tool)
+ *   pairs survive, ranked by (fp32 distance, flat row-major pair index), tool receivers in S counting as pairs at distance 1e10;
+ *   no tool<->tool edge remains.
+ * thr[b] = fadd(fmul(fsub(fmul(max_y, fp32(ratio)), min_y), fp32(0.1)), min_y), four separately rounded fp32 operations
+ * (rollout.py:136 and graph.py:134 on numpy float32 scalars), max_y / min_y over the y of the rows the bounds source names:
+ *   row r < d_bounds_n[b] is point d_bounds_first[b] + (d_bounds_idx ? d_bounds_idx[b * idx_stride + r] : r) of the flat
+ *   (bounds_points, 3) buffer d_bounds_pos (indices are clamped into the buffer; with d_bounds_idx, r < idx_stride); a zero row
+ *   takes part iff pad_rows > d_bounds_n[b].  A NaN among them makes thr NaN (as np.max does) and S empty; so does no row at all.
+ *   Dataset: the episode buffer, first point of frame n_his - 1, ag_fps_batch's d_fps_idx / d_n_obj, pad_rows = max_nobj
+ *   (dataset.py:186-209).  Eval rollout: d_state_next, b * n_his * N + (n_his - 1) * N, no gather, d_n_obj, pad_rows 0
+ *   (rollout.py:125-133).
+ * The base graphs are ag_build_edges_graphs' outputs with capacity base_cap.  A graph whose d_n_edges_in[b] is outside
+ * [0, base_cap], whose CSR is not consistent (rows ascending, senders strictly ascending within [0, N)) or whose tool count is
+ * not n_tools gets d_n_edges_out[b] = -1 and nothing else.  Outputs as ag_build_edges_graphs: sorted by (receiver, sender),
+ * d_n_edges_out[b] the TRUE count even above edge_cap (then nothing else is written for graph b).  A graph's result does not
+ * depend on the others in the launch.  Input and output arrays must not overlap.  Enqueue only.
+ * Limits: N <= 4096, n_tools <= 64, N * n_tools <= 8192 (a graph's pair tables live in LDS); beyond them AG_ERR_UNSUPPORTED
+ * before anything is enqueued. */
+typedef struct ag_rule_graphs_args {
+    const float* d_pos;            /* graph b's (N,3) positions start at d_pos + b * pos_bstride floats (0: N*3)          */
+    int64_t pos_bstride;
+    const uint8_t* d_mask;         /* (B, N) valid particle; d_tool_mask (B, N) tool particle                            */
+    const uint8_t* d_tool_mask;
+    const int32_t* d_send_in;      /* (B, base_cap); d_row_ptr_in (B, N + 1); d_n_edges_in (B,)                          */
+    const int32_t* d_row_ptr_in;
+    const int32_t* d_n_edges_in;
+    const double* d_kNN;           /* (B,)                                                                               */
+    const float* d_bounds_pos;     /* the bounds source, see above                                                       */
+    const int64_t* d_bounds_first; /* (B,)                                                                               */
+    const int32_t* d_bounds_idx;   /* (B, idx_stride) or NULL                                                            */
+    const int32_t* d_bounds_n;     /* (B,)                                                                               */
+    int64_t bounds_points;
+    double ratio;                  /* connect_tool_surface_ratio; rounded to fp32 before use                             */
+    int32_t B, N, n_tools, base_cap, idx_stride, pad_rows, edge_cap;
+    int32_t* d_recv;               /* (B, edge_cap); d_send alike; d_row_ptr (B, N + 1); d_n_edges_out (B,)              */
+    int32_t* d_send;
+    int32_t* d_row_ptr;
+    int32_t* d_n_edges_out;
+    float* d_thr;                  /* (B,) or NULL: the thresholds                                                       */
+} ag_rule_graphs_args;
+int ag_edges_nonfixed_rule_graphs(ag_ctx* ctx, void* stream, const ag_rule_graphs_args* args);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,12 @@ and of 2000 raw points, in one process:
   cpu            tests/dataset_restate.py (numpy) on the same samples and draws, on this machine's CPU: the reference itself is not
                  where the GPU is
 
+A second leg ("softbody") follows config/dynamics/softbody.yaml's dataset entries (n_his 5, rest frame, max_nobj 300, five tool
+points, topk 10, max_nR 3500, tool-to-non-fixed rule, knn_range [0.4, 1.0]): ds.batch on the batched rule path
+(ag_edges_nonfixed_rule_graphs, back-off in rounds) against ds.batch(..., per_sample_edges=True), the graph-by-graph path,
+alternated round by round in one process on the same samples and draws; ms per call, the ratio, the read-backs of a batch and the
+HIP-event time of the kernel families, "rule" among them.
+
 There is no pass / fail threshold.  The claim to confirm or refute: a batch builds in less than one TrainStep iteration, so that
 prefetch hides it ("loop_prefetch_minus_step_ms" is then about zero); if not, "kernels" says which phase dominates.
 
@@ -40,6 +46,13 @@ DATASET = {"n_his": 4, "n_future": 3, "materials": ["rope"],
            "randomness": {"use": True, "state_noise": {"train": 0.05, "valid": 0.0}, "phys_noise": {"train": 0.0, "valid": 0.0}}}
 MATERIAL = {"material_index": {"rope": 0}, "rope": {"physics_params": [{"name": "stiffness", "use": True}]}}
 FAMILIES = ["fps", "assemble", "edge_count", "edge_emit"]
+SOFT_DATASET = {"n_his": 5, "n_future": 3, "store_rest_state": True, "materials": ["softbody"],
+                "datasets": [{"name": "softbody", "max_nobj": 300, "max_nR": 3500, "fps_radius_range": [0.2, 0.24],
+                              "adj_radius_range": [0.48, 0.52], "topk": 10, "connect_tool_all": False, "connect_tool_surface": False,
+                              "connect_tool_surface_ratio": 1.0, "connect_tool_all_non_fixed": True, "knn_range": [0.4, 1.0],
+                              "min_knn": 0.4, "knn_increment": 0.1}],
+                "randomness": {"use": False, "state_noise": {"train": 0.05, "valid": 0.0}, "phys_noise": {"train": 0.0, "valid": 0.0}}}
+SOFT_MATERIAL = {"material_index": {"softbody": 0}, "softbody": {"physics_params": [{"name": "stiffness", "use": True}]}}
 
 
 def make_episodes(points, n_epis=8, T=38, seed=0):
@@ -58,6 +71,69 @@ def make_episodes(points, n_epis=8, T=38, seed=0):
         phys.append({"rope": np.array([rng.uniform(0.2, 0.8)], np.float32)})
         pairs += [[e] + list(range(s, s + 7)) for s in range(T - 6)]
     return np.array(pairs), phys, obj, eef
+
+
+def make_soft_episodes(points=600, n_epis=8, T=38, seed=0):
+    """Blocks of `points` raw particles (2.4 x 0.7 x 2.4 units) that sag a little frame by frame, five tool points in a row that
+    come down on the top face: farthest-point sampling at radius ~0.22 keeps a few hundred of them."""
+    rng = np.random.default_rng(seed)
+    obj, eef, phys, pairs = [], [], [], []
+    for e in range(n_epis):
+        base = rng.uniform(0, 1, (points, 3)) * [2.4, 0.7, 2.4] - [1.2, 0.0, 1.2]
+        drift = rng.normal(0, 0.004, (1, 3))
+        obj.append(np.stack([base + drift * k + rng.normal(0, 0.003, base.shape) for k in range(T)]).astype(np.float32))
+        row = np.array([[0.5, 0.9, 0.0], [-0.5, 0.9, 0.0], [0.0, 0.9, 0.0], [0.25, 0.9, 0.0], [-0.25, 0.9, 0.0]]) + [rng.uniform(-0.5, 0.5), 0, rng.uniform(-0.5, 0.5)]
+        eef.append(np.stack([row - [0.0, 0.008 * k, 0.0] for k in range(T)]).astype(np.float32))
+        phys.append({"softbody": np.array([rng.uniform(0.2, 0.8)], np.float32)})
+        pairs += [[e] + list(range(s, s + 8)) for s in range(T - 7)]
+    return np.array(pairs), phys, obj, eef
+
+
+def run_softbody(a, dev):
+    pairs, phys, obj, eef = make_soft_episodes()
+    ds = ag.DeviceDynDataset(SOFT_DATASET, SOFT_MATERIAL, pairs, phys, obj, eef, dev)
+    B = a.batch
+    g = torch.Generator(device=dev)
+    g.manual_seed(1)
+    idx = np.random.default_rng(1).integers(0, len(ds), B)
+    dr = ds.draws(idx, generator=g)
+    sync = torch.cuda.synchronize
+    variants = {"batched": lambda: ds.batch(idx, draws=dr), "per_sample": lambda: ds.batch(idx, draws=dr, per_sample_edges=True)}
+    data = {k: fn() for k, fn in variants.items()}                                       # warm-up, and the two agree
+    na, nb = data["batched"]["edges"].n_edges.cpu().numpy(), data["per_sample"]["edges"].n_edges.cpu().numpy()
+    same = bool(np.array_equal(na, nb)) and all(
+        torch.equal(data["batched"]["edges"].send[b, :na[b]], data["per_sample"]["edges"].send[b, :na[b]]) for b in range(B))
+    variants["batched"]()
+    res = {"points": 600, "pairs": len(ds), "B": B, "N": ds.N, "n_obj_mean": float(data["batched"]["obj_mask"].sum(1).float().mean()),
+           "edges_mean": float(na.mean()), "edges_max": int(na.max()), "edges_equal": same, "last_waits": ds.last_waits,
+           "attempts_per_graph_mean": float(np.mean([len(t) for t in ds.last_trail])),
+           "attempts_per_graph_max": int(max(len(t) for t in ds.last_trail)),
+           "graphs_backed_off": int(sum(len(t) > 1 for t in ds.last_trail))}
+    times = {k: [] for k in variants}
+    iters = {"batched": a.iters, "per_sample": 1}
+    for _ in range(a.rounds):
+        for k, fn in variants.items():                                                   # alternated within the round
+            sync()
+            t0 = time.perf_counter()
+            for _ in range(iters[k]):
+                fn()
+            sync()
+            times[k].append((time.perf_counter() - t0) * 1e3 / iters[k])
+    for k, v in times.items():
+        res[k] = {"ms_median": float(np.median(v)), "ms_rounds": [round(x, 3) for x in v], "calls_per_round": iters[k]}
+    res["per_sample_over_batched"] = res["per_sample"]["ms_median"] / res["batched"]["ms_median"]
+    fams = FAMILIES + ["rule"]
+    ds.engine.set_profiling(fams)
+    ds.engine.reset_stats()
+    for _ in range(a.iters):
+        variants["batched"]()
+    sync()
+    res["kernels"] = {}
+    for f in fams:
+        ms, n = ds.engine.kernel_stats(f)
+        res["kernels"][f] = {"ms_per_batch": ms / a.iters, "launches_per_batch": n / a.iters}
+    ds.engine.set_profiling([])
+    return res
 
 
 def timed(fn, rounds, iters, sync):
@@ -149,6 +225,7 @@ def main():
     ap.add_argument("--cpu-samples", type=int, default=32)
     ap.add_argument("--fast-factor", type=int, default=40, help="the sub-millisecond rows run iters x this many calls per round")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--softbody", choices=["also", "only", "no"], default="also", help="the softbody leg: with the rope configs, alone, or not")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     res = {"tool": "bench_dataset", "device": torch.cuda.get_device_name(dev), "rounds": a.rounds, "iters_per_round": a.iters,
@@ -157,7 +234,9 @@ def main():
                    "draws rows time iters x fast_factor calls per round; 'kernels' are HIP-event times from a separate pass; every "
                    "loop iteration is a full batch (shuffled with the device generator); cpu_restate is the numpy restatement on this "
                    "machine, not the reference", "fast_factor": a.fast_factor,
-           "configs": [run_config(a, dev, int(p)) for p in a.points.split(",")]}
+           "configs": [] if a.softbody == "only" else [run_config(a, dev, int(p)) for p in a.points.split(",")]}
+    if a.softbody != "no":
+        res["softbody"] = run_softbody(a, dev)
     line = json.dumps(res)
     print(line)
     if a.out:

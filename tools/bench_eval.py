@@ -7,6 +7,11 @@ max_nR 1000) for 64 rollouts of 30 steps on synthetic episodes, three ways in on
                with torch ops on the device - how this work was done before rollout_eval_batch
   per_graph    rollout_eval_batch(..., per_graph=True)
 
+--config softbody runs softbody.yaml's entries instead (n_his 5, rest frame, pstep 4, max_nobj 300, five tool points, topk 10,
+max_nR 3500, tool-to-non-fixed rule, kNN range): the batched variant then advances the rule graphs together
+(ag_edges_nonfixed_rule_graphs per step, back-off in rounds), per_graph is the graph-by-graph path these configs took before; the
+sequential variant is the rope leg's only.
+
 All three include building the start batch.  Reported: ms per variant (median of the rounds), per step and per rollout, the ratio
 to the sequential path, and - from a separate pass - the HIP-event time of each kernel family inside the batched path
 (ag_ctx_kernel_stats) next to one plain forward at B = 64.  No pass / fail threshold.  The expectation to confirm or refute: a
@@ -29,10 +34,10 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import adaptigraph_amd as ag  # noqa: E402
 import train_restate as TR  # noqa: E402
-from bench_dataset import DATASET, MATERIAL, make_episodes  # noqa: E402
+from bench_dataset import DATASET, MATERIAL, SOFT_DATASET, SOFT_MATERIAL, make_episodes, make_soft_episodes  # noqa: E402
 from bench_train import CFG  # noqa: E402
 
-FAMILIES = ["fps", "assemble", "edge_count", "edge_emit", "prep", "node_enc", "edge_enc", "node_prop", "node_final", "roll_update"]
+FAMILIES = ["fps", "assemble", "edge_count", "edge_emit", "rule", "prep", "node_enc", "edge_enc", "node_prop", "node_final", "roll_update"]
 
 
 def sequential(model, ds, idx, steps):
@@ -69,26 +74,37 @@ def main():
     ap.add_argument("--rollouts", type=int, default=64)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--config", choices=["rope", "softbody"], default="rope")
     a = ap.parse_args()
+    soft = a.config == "softbody"
     dev = torch.device("cuda:0")
     T = a.steps + 15
     n_epis, per = 8, a.rollouts // 8
     assert per * n_epis == a.rollouts and per <= 8, "rollouts: a multiple of 8, at most 64"
-    pairs, phys, obj, eef = make_episodes(600, n_epis=n_epis, T=T)
-    ds = ag.DeviceDynDataset(DATASET, MATERIAL, pairs, phys, obj, eef, dev, phase="valid")
-    model = ag.DynamicsPredictor(CFG, MATERIAL, {"n_his": 4, "materials": ["rope"]}, dev)
-    model.load_state_dict({k: torch.from_numpy(v) for k, v in TR.make_weights(0).items()})
+    if soft:
+        pairs, phys, obj, eef = make_soft_episodes(600, n_epis=n_epis, T=T)
+        ds = ag.DeviceDynDataset(SOFT_DATASET, SOFT_MATERIAL, pairs, phys, obj, eef, dev, phase="valid")
+        model = ag.DynamicsPredictor(dict(CFG, pstep=4), SOFT_MATERIAL, {"n_his": 5, "materials": ["softbody"]}, dev)
+        model.load_state_dict({k: torch.from_numpy(v) for k, v in TR.make_weights(0, n_his=5).items()})
+    else:
+        pairs, phys, obj, eef = make_episodes(600, n_epis=n_epis, T=T)
+        ds = ag.DeviceDynDataset(DATASET, MATERIAL, pairs, phys, obj, eef, dev, phase="valid")
+        model = ag.DynamicsPredictor(CFG, MATERIAL, {"n_his": 4, "materials": ["rope"]}, dev)
+        model.load_state_dict({k: torch.from_numpy(v) for k, v in TR.make_weights(0).items()})
     model = model.to(dev)
-    idx = np.array([e * (T - 6) + s for e in range(n_epis) for s in range(per)])
+    idx = np.array([e * (len(pairs) // n_epis) + s for e in range(n_epis) for s in range(per)])
     sync = torch.cuda.synchronize
     variants = {"batched": lambda: ag.rollout_eval_batch(model, ds, idx, rollout_steps=a.steps).errors,
                 "sequential": lambda: sequential(model, ds, idx, a.steps),
                 "per_graph": lambda: ag.rollout_eval_batch(model, ds, idx, rollout_steps=a.steps, per_graph=True).errors}
+    if soft:
+        del variants["sequential"]
+    base = "per_graph" if soft else "sequential"
     out = {k: fn() for k, fn in variants.items()}                                    # warm-up, and the three agree
     sync()
     res0 = ag.rollout_eval_batch(model, ds, idx, rollout_steps=a.steps)
     assert res0.lengths.tolist() == [a.steps] * a.rollouts
-    agree = {k: float((out[k] - out["batched"]).abs().max()) for k in ("sequential", "per_graph")}
+    agree = {k: float((out[k] - out["batched"]).abs().max()) for k in variants if k != "batched"}
     times = {k: [] for k in variants}
     for _ in range(a.rounds):
         for k, fn in variants.items():
@@ -98,7 +114,9 @@ def main():
             sync()
             times[k].append((time.perf_counter() - t0) * 1e3)
     res = {"tool": "bench_eval", "device": torch.cuda.get_device_name(dev), "rounds": a.rounds, "rollouts": a.rollouts, "steps": a.steps,
-           "config": "rope: max_nobj 100 + 1 tool point, topk 10, max_nR 1000, synthetic episodes of 600 points",
+           "config": ("softbody: max_nobj 300 + 5 tool points, topk 10, max_nR 3500, non-fixed rule, kNN range [0.4, 1.0], n_his 5, pstep 4, "
+                      "synthetic episodes of 600 points") if soft else
+                     "rope: max_nobj 100 + 1 tool point, topk 10, max_nR 1000, synthetic episodes of 600 points",
            "n_obj_mean": float(ds.batch(idx, ds.eval_draws(idx), with_fps=True)["n_obj"].float().mean()),
            "edges_start_mean": float(np.mean([tr[0][-1][2] for tr in res0.trails])),
            "backoff_attempts_in_loop": int(sum(len(t) - 1 for tr in res0.trails for t in tr[1:])), "host_waits": res0.host_waits,
@@ -107,9 +125,9 @@ def main():
         med = float(np.median(v))
         res["variants"][k] = {"ms_median": med, "ms_rounds": [round(x, 2) for x in v], "ms_per_step": med / a.steps,
                               "ms_per_rollout": med / a.rollouts, "us_per_rollout_step": med * 1e3 / (a.steps * a.rollouts)}
-    seq = res["variants"]["sequential"]["ms_median"]
+    seq = res["variants"][base]["ms_median"]
     for k in variants:
-        res["variants"][k]["speedup_over_sequential"] = seq / res["variants"][k]["ms_median"]
+        res["variants"][k]["speedup_over_" + base] = seq / res["variants"][k]["ms_median"]
     # ---- kernel table of the batched path, and one plain forward at the same B, in a separate pass
     eng = model.engine(dev)
     for e in (eng, ds.engine):

@@ -21,7 +21,7 @@ AG_ERR_UNSUPPORTED = -4
 AG_ERR_NO_WEIGHTS = -5
 
 KERNEL_FAMILIES = ["edge_count", "edge_emit", "prep", "node_enc", "edge_enc", "mp", "node_prop", "node_final",
-                   "roll_init", "roll_update", "cost", "fps", "assemble", "rule"]
+                   "roll_init", "roll_update", "cost", "fps", "assemble", "rule", "surface"]
 
 # exactly the symbols include/adaptigraph_amd.h declares (tests/test_abi.py checks both directions)
 EXPORTS = ["ag_abi_version", "ag_ctx_create", "ag_ctx_destroy", "ag_last_error", "ag_ctx_load_weights",
@@ -33,7 +33,7 @@ EXPORTS = ["ag_abi_version", "ag_ctx_create", "ag_ctx_destroy", "ag_last_error",
            "ag_ctx_alloc_counts", "ag_rollout_work", "ag_backward", "ag_backward_inputs", "ag_cost_chamfer_backward",
            "ag_ctx_load_weights_device", "ag_adam_step", "ag_train_step", "ag_ppm_grad_step", "ag_ppm_adam_step", "ag_train_step_part",
            "ag_fps_batch", "ag_dataset_assemble", "ag_build_edges_graphs", "ag_eval_step",
-           "ag_edges_nonfixed_rule_graphs"]
+           "ag_edges_nonfixed_rule_graphs", "ag_edges_surface_rule_graphs"]
 
 OPTIONS = ["streams", "chunk", "latency", "ragged", "ell_graph", "self_dedupe", "repeat_sort", "edge_wgs", "edge_block_min",
            "enc_persist", "stagger_us", "device_decode", "zigzag", "share_first", "share_prefix", "stream_min_rows", "pipeline_fork"]
@@ -81,6 +81,16 @@ class AgRuleGraphsArgs(C.Structure):
                 [("bounds_points", C.c_int64), ("ratio", C.c_double)] +
                 [(n, C.c_int32) for n in ("B", "N", "n_tools", "base_cap", "idx_stride", "pad_rows", "edge_cap")] +
                 [(n, C.c_void_p) for n in ("d_recv", "d_send", "d_row_ptr", "d_n_edges_out", "d_thr")])
+
+
+class AgSurfaceRuleGraphsArgs(C.Structure):
+    """ag_surface_rule_graphs_args (include/adaptigraph_amd.h), field for field."""
+    _fields_ = ([("d_pos", C.c_void_p), ("pos_bstride", C.c_int64)] +
+                [(n, C.c_void_p) for n in ("d_mask", "d_tool_mask", "d_send_in", "d_row_ptr_in", "d_n_edges_in", "d_bounds_pos",
+                                           "d_bounds_first", "d_bounds_idx", "d_bounds_n")] +
+                [("bounds_points", C.c_int64), ("ratio", C.c_double)] +
+                [(n, C.c_int32) for n in ("B", "N", "n_tools", "base_cap", "idx_stride", "pad_rows", "bounds_order", "edge_cap")] +
+                [(n, C.c_void_p) for n in ("d_recv", "d_send", "d_row_ptr", "d_n_edges_out", "d_bounds", "d_planes")])
 
 
 _lib = None
@@ -147,6 +157,7 @@ def load():
     lib.ag_build_edges_graphs.argtypes = [vp, vp, vp, C.c_int64, vp, vp, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp]
     lib.ag_eval_step.argtypes = [vp, vp, C.POINTER(AgEvalStepArgs)]
     lib.ag_edges_nonfixed_rule_graphs.argtypes = [vp, vp, C.POINTER(AgRuleGraphsArgs)]
+    lib.ag_edges_surface_rule_graphs.argtypes = [vp, vp, C.POINTER(AgSurfaceRuleGraphsArgs)]
     lib.ag_ctx_set_profiling.argtypes = [vp, i32]
     lib.ag_ctx_kernel_stats.argtypes = [vp, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     lib.ag_ctx_reset_stats.argtypes = [vp]

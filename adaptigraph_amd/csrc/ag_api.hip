@@ -9,7 +9,7 @@ using namespace ag;
 namespace {
 
 const char* kFamilyNames[FAM_COUNT] = {"edge_count", "edge_emit", "prep", "node_enc", "edge_enc",
-                                       "mp", "node_prop", "node_final", "roll_init", "roll_update", "cost", "fps", "assemble", "rule"};
+                                       "mp", "node_prop", "node_final", "roll_init", "roll_update", "cost", "fps", "assemble", "rule", "surface"};
 
 struct OptName { const char* name; const char* env; int Options::* field; bool env_negates; int lo, hi; };
 const OptName kOptions[] = {
@@ -617,6 +617,42 @@ int ag_edges_nonfixed_rule_graphs(ag_ctx* c, void* stream, const ag_rule_graphs_
     a.recv = p->d_recv; a.send = p->d_send; a.row_ptr = p->d_row_ptr; a.n_out = p->d_n_edges_out; a.thr_out = p->d_thr;
     { Scoped pr(c, FAM_RULE);
       HIPCHK(c, launch_rule_graphs(a, call.st)); }
+    return AG_OK;
+}
+
+int ag_edges_surface_rule_graphs(ag_ctx* c, void* stream, const ag_surface_rule_graphs_args* p) {
+    if (!c) return AG_ERR_INVALID;
+    if (!p || !p->d_pos || !p->d_mask || !p->d_tool_mask || !p->d_send_in || !p->d_row_ptr_in || !p->d_n_edges_in || !p->d_bounds_pos ||
+        !p->d_bounds_first || !p->d_bounds_n || !p->d_recv || !p->d_send || !p->d_row_ptr || !p->d_n_edges_out)
+        return fail(c, AG_ERR_INVALID, "ag_edges_surface_rule_graphs: null pointer");
+    if (p->B < 1 || p->N < 1 || p->n_tools < 0 || p->n_tools > p->N || p->base_cap < 1 || p->edge_cap < 1 || p->bounds_points < 1 ||
+        p->pad_rows < 0 || (p->d_bounds_idx && p->idx_stride < 1) || (p->bounds_order != 0 && p->bounds_order != 1))
+        return fail(c, AG_ERR_INVALID, "ag_edges_surface_rule_graphs: bad sizes B=%d N=%d n_tools=%d base_cap=%d edge_cap=%d "
+                    "bounds_points=%lld pad_rows=%d idx_stride=%d bounds_order=%d", p->B, p->N, p->n_tools, p->base_cap, p->edge_cap,
+                    (long long)p->bounds_points, p->pad_rows, p->idx_stride, p->bounds_order);
+    if (p->pos_bstride != 0 && p->pos_bstride < (int64_t)p->N * 3)
+        return fail(c, AG_ERR_INVALID, "ag_edges_surface_rule_graphs: pos_bstride %lld is below N*3 = %d", (long long)p->pos_bstride,
+                    p->N * 3);
+    if (p->N > 4096) return fail(c, AG_ERR_UNSUPPORTED, "ag_edges_surface_rule_graphs: N=%d exceeds 4096", p->N);
+    if (p->n_tools > RULE_GRAPHS_MAX_TOOLS)
+        return fail(c, AG_ERR_UNSUPPORTED, "ag_edges_surface_rule_graphs: n_tools=%d exceeds the LDS-resident tool list (at most %d)",
+                    p->n_tools, RULE_GRAPHS_MAX_TOOLS);
+    if (p->d_send_in == p->d_send || p->d_row_ptr_in == p->d_row_ptr || p->d_n_edges_in == p->d_n_edges_out)
+        return fail(c, AG_ERR_INVALID, "ag_edges_surface_rule_graphs: input and output arrays must differ");
+    SlotGuard call;
+    int rc = begin_call(c, stream, call);
+    if (rc) return rc;
+    SurfaceGraphsArgs a{};                                // flags, scan and tool list of a graph live in LDS: no slab carve
+    a.pos = p->d_pos; a.pos_bstride = p->pos_bstride ? (long)p->pos_bstride : (long)p->N * 3; a.mask = p->d_mask; a.tool = p->d_tool_mask;
+    a.send_in = p->d_send_in; a.row_ptr_in = p->d_row_ptr_in; a.n_edges_in = p->d_n_edges_in; a.base_cap = p->base_cap;
+    a.B = p->B; a.N = p->N; a.n_tools = p->n_tools; a.edge_cap = p->edge_cap;
+    a.bnd_pos = p->d_bounds_pos; a.bnd_points = (long)p->bounds_points; a.bnd_first = (const long long*)p->d_bounds_first;
+    a.bnd_idx = p->d_bounds_idx; a.idx_stride = p->idx_stride; a.bnd_n = p->d_bounds_n; a.pad_rows = p->pad_rows;
+    a.bounds_order = p->bounds_order; a.ratio = (float)p->ratio; a.one_minus_ratio = (float)(1.0 - p->ratio);
+    a.recv = p->d_recv; a.send = p->d_send; a.row_ptr = p->d_row_ptr; a.n_out = p->d_n_edges_out;
+    a.bounds_out = p->d_bounds; a.planes_out = p->d_planes;
+    { Scoped pr(c, FAM_SURFACE);
+      HIPCHK(c, launch_surface_graphs(a, call.st)); }
     return AG_OK;
 }
 

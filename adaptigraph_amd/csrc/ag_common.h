@@ -62,7 +62,7 @@ struct WeightLayout {
 
 // ---- kernel families (profiling ids) ------------------------------------------------------------------
 enum Family { FAM_EDGE_COUNT = 0, FAM_EDGE_EMIT, FAM_PREP, FAM_NODE_ENC, FAM_EDGE_ENC, FAM_MP, FAM_NODE_PROP,
-              FAM_NODE_FINAL, FAM_ROLL_INIT, FAM_ROLL_UPDATE, FAM_COST, FAM_FPS, FAM_ASSEMBLE, FAM_RULE, FAM_COUNT };
+              FAM_NODE_FINAL, FAM_ROLL_INIT, FAM_ROLL_UPDATE, FAM_COST, FAM_FPS, FAM_ASSEMBLE, FAM_RULE, FAM_SURFACE, FAM_COUNT };
 
 // ---- per-context tuning / A-B switches.  Defaults come from the environment ONCE, at ag_ctx_create (the AG_* name in
 // brackets); ag_ctx_set_option changes them per context afterwards.  None of them changes a result (bit-identical paths),
@@ -183,6 +183,18 @@ struct RuleGraphsArgs {
     int* recv; int* send; int* row_ptr; int* n_out; float* thr_out;                 // thr_out (B,) may be null
 };
 hipError_t launch_rule_graphs(const RuleGraphsArgs& a, hipStream_t st);
+// the two-closest-planes rule (graph.py:175-221) for B graphs in one launch, one workgroup per graph (ag_rules_batch.hip): bounds,
+// plane choice and subset are formed on the device; no pair tables, so only N is limited
+struct SurfaceGraphsArgs {
+    const float* pos; long pos_bstride; const uint8_t* mask; const uint8_t* tool;
+    const int* send_in; const int* row_ptr_in; const int* n_edges_in; int base_cap; // the input graphs, as RuleGraphsArgs' base graphs
+    int B, N, n_tools, edge_cap;
+    const float* bnd_pos; long bnd_points; const long long* bnd_first; const int* bnd_idx; int idx_stride; const int* bnd_n;   // as RuleGraphsArgs
+    int pad_rows, bounds_order; float ratio, one_minus_ratio;                       // fp32(ratio), fp32(1 - ratio in double)
+    int* recv; int* send; int* row_ptr; int* n_out;
+    float* bounds_out; int* planes_out;                                             // (B, 6) / (B, 2), may be null
+};
+hipError_t launch_surface_graphs(const SurfaceGraphsArgs& a, hipStream_t st);
 hipError_t launch_edge_nonself(const int* recv, const int* send, const int* row_ptr, int B, int N, int edge_cap,
                                int* ns_edge, int* n_ns, const int* live, hipStream_t st);
 

@@ -31,7 +31,8 @@ import torch
 
 from . import _lib
 from .context import default_engine, ptr, current_stream, _require_gpu
-from .graph import EdgeList, BackoffPlan, RuleConfig, backoff_rounds, construct_edges_with_backoff, rule_attempt, rule_graphs_limit
+from .graph import (EdgeList, BackoffPlan, RuleConfig, backoff_rounds, construct_edges_with_backoff, rule_attempt, rule_graphs_limit,
+                    surface_graphs_limit)
 from .rollout import surface_bounds
 
 FPS_MAX_POINTS = 8192        # ag_fps_batch keeps a cloud in LDS (96 KB of the CU's 160 KB at this size)
@@ -119,6 +120,22 @@ def plane_bounds(obj_kp_padded, ratio):
     rollout.surface_bounds on the PADDED (max_nobj, 3) history frame n_his - 1, zero rows included as in the reference."""
     b = surface_bounds(np.asarray(obj_kp_padded, np.float32), ratio)
     return {k: b[k] for k in ("max_y", "min_y", "max_x", "max_z")}
+
+
+def start_graph_bounds(obj_kp_padded, ratio):
+    """The six bounds the eval script's construct_graph hands the edge builder (rollout/graph.py:446-458, 508-512), on the PADDED
+    (max_nobj, 3) history frame n_his - 1, written as the reference writes them on numpy float32 scalars: min_x / min_z are formed
+    from the UNSCALED maxima, then the maxima are scaled (rollout.surface_bounds scales first; the two agree at ratio 1)."""
+    kp = np.asarray(obj_kp_padded, np.float32)
+    max_y, min_y = np.max(kp[:, 1]), np.min(kp[:, 1])
+    max_x, max_z = np.max(kp[:, 0]), np.max(kp[:, 2])
+    min_x, min_z = np.min(kp[:, 0]), np.min(kp[:, 2])
+    min_x = (max_x - min_x) * (1 - ratio) + min_x
+    min_z = (max_z - min_z) * (1 - ratio) + min_z
+    max_y = max_y * ratio
+    max_x = max_x * ratio
+    max_z = max_z * ratio
+    return dict(max_y=max_y, min_y=min_y, max_x=max_x, max_z=max_z, min_x=min_x, min_z=min_z)
 
 
 def fps_batch(pos, pt_off, npts, fps_start, fps_radius, rad_start, max_nobj, max_pts, engine=None):
@@ -295,7 +312,7 @@ class DeviceDynDataset:
         return fps_batch(self._obj, tab[:, 0], tab[:, 1], dr.fps_start, dr.fps_radius, dr.rad_start, self.spec.max_nobj,
                          int(self._n_e.max()), engine=self.engine)
 
-    def batch(self, idx, draws=None, generator=None, dense=False, with_fps=False, per_sample_edges=False):
+    def batch(self, idx, draws=None, generator=None, dense=False, with_fps=False, per_sample_edges=False, _eval_start=False):
         """The collated batch of the samples `idx` (a sequence of pair indices): state, action, eef_future, action_future,
         state_future, attrs, p_rigid, p_instance, obj_mask, material_index, <material>_physics_param as the reference's DataLoader
         collates them, plus edges (an EdgeList over the B graphs, every graph within max_nR) and max_edges (= max_nR).
@@ -304,7 +321,10 @@ class DeviceDynDataset:
         Waits once, on the current stream, for the B edge counts, and once more per back-off round (last_waits).
         per_sample_edges=True: configs with a tool rule or a kNN range build their graphs sample by sample through
         construct_edges_with_backoff, with several waits per sample - the A/B partner of the batched rule path, and what a config
-        beyond ag_edges_nonfixed_rule_graphs' size limit falls back to (with one warning)."""
+        beyond ag_edges_nonfixed_rule_graphs' size limit falls back to (with one warning).
+        _eval_start (private, rollout_eval_batch's): with connect_tool_surface the graphs get the eval script's own rule - both tool
+        rules with construct_graph's six bounds (rollout/graph.py:446-458, 508-512) - where this, the training path, never passes
+        min_x / min_z on and so never fires the surface rule (dataset.py:310-314).  Every other config: no effect."""
         sp, dev, eng = self.spec, self.device, self.engine
         idx = np.asarray(idx, np.int64).reshape(-1)
         if len(idx) < 1 or idx.min() < 0 or idx.max() >= len(self):
@@ -341,7 +361,10 @@ class DeviceDynDataset:
         out["material_index"] = material_index
         for name, dim in self.materials.items():                                             # dataset.py:377-381
             out[name + "_physics_param"] = phys if name == sp.material else torch.zeros((B, dim), **f32)
+        surface = bool(_eval_start and sp.connect_tool_surface)
         limit = rule_graphs_limit(N, self.n_eef) if sp.connect_tool_all_non_fixed else None
+        if surface and limit is None:
+            limit = surface_graphs_limit(N, self.n_eef)
         if limit is not None and not sp.batched_edges and not per_sample_edges:
             if not self._warned_rule_limit:
                 import warnings
@@ -353,10 +376,11 @@ class DeviceDynDataset:
             edges, trail = self._edges_batched(out["state"], state_mask, eef_mask, thr2, cull, waits)
             self.last_waits = waits[0]
         elif per_sample_edges:
-            edges, trail = self._edges_per_sample(idx, out["state"], state_mask, eef_mask, fps_idx, n_obj, dr)
+            edges, trail = self._edges_per_sample(idx, out["state"], state_mask, eef_mask, fps_idx, n_obj, dr, eval_start=surface)
             self.last_waits = None
         else:
-            edges, trail = self._edges_rule_batched(out["state"], state_mask, eef_mask, thr2, cull, tab, fps_idx, n_obj, dr)
+            edges, trail = self._edges_rule_batched(out["state"], state_mask, eef_mask, thr2, cull, tab, fps_idx, n_obj, dr,
+                                                    cfg=self._rule_config(surface, 1))
         self.last_trail = trail
         self._last_build = dict(state_mask=state_mask, eef_mask=eef_mask, thr2=thr2, cull=cull)   # rollout_eval_batch reads them
         out["edges"] = edges
@@ -391,38 +415,43 @@ class DeviceDynDataset:
         self._backoff(el, counts, state, mask, tool, thr2, cull, trail, waits)
         return el, trail
 
-    def _edges_rule_batched(self, state, mask, tool, thr2, cull, tab, fps_idx, n_obj, dr):
+    def _edges_rule_batched(self, state, mask, tool, thr2, cull, tab, fps_idx, n_obj, dr, cfg=None):
         """Configs with the non-fixed rule and / or a kNN range.  All B base graphs at top-k into buffers of the structural bound
         (the rule removes edges as well as adding them, so max_nR is no capacity for its input), ONE rule launch into max_nR-wide
         buffers, one read-back of the counts (with the kNN draws).  Then graph.BackoffPlan's rounds over the sub-batch that is
         still over max_nR: a graph whose kNN went down reruns the rule on its unchanged base graph, graphs whose top-k went down
         share one base launch per top-k; one read-back per round (dataset.py:317-349).  The bounds of the rule's threshold are
         the un-augmented rows of frame n_his - 1, padding zeros included (dataset.py:186-209); min_x / min_z are never passed
-        on (dataset.py:310-314), so connect_tool_surface cannot fire here."""
+        on (dataset.py:310-314), so connect_tool_surface cannot fire here - unless cfg (a RuleConfig, default the training path's) says
+        so: the eval rollout's start graphs chain the surface rule behind it on the same bounds rows."""
         sp, N, nh = self.spec, self.N, self.spec.n_his
+        cfg = cfg or self._rule_config()
         B, rule, cap = mask.shape[0], sp.connect_tool_all_non_fixed, max(1, sp.max_nR)
         k = min(N, sp.topk)
-        base_cap = max(1, N * (k + self.n_eef) if k < N else N * N) if rule else cap
+        base_cap = max(1, N * (k + self.n_eef) if k < N else N * N) if (rule or cfg.surface) else cap
         last = state.data_ptr() + (nh - 1) * N * 3 * 4                                       # state[:, -1] in place
         bnd = (self._obj, tab[:, 0].contiguous(), fps_idx, n_obj, sp.max_nobj)
         base = self._build_graphs(last, nh * N * 3, mask, tool, thr2, cull, sp.topk, cap=base_cap)
-        el = self._ruled(last, nh * N * 3, mask, tool, base, dr.knn_thresh, bnd, cap)
+        el = self._ruled(last, nh * N * 3, mask, tool, base, dr.knn_thresh, bnd, cap, cfg=cfg)
         host = torch.cat([dr.knn_thresh, el.n_edges.to(torch.float64)]).cpu().numpy()        # the one wait
         plan = BackoffPlan(host[:B], sp.topk, sp.max_nR, sp.min_kNN, sp.knn_increment, has_rule=rule)
         plan.record(host[B:].astype(np.int64))
-        self._rule_rounds(plan, el, base, state, mask, tool, thr2, cull, bnd)
+        self._rule_rounds(plan, el, base, state, mask, tool, thr2, cull, bnd, cfg=cfg)
         self.last_waits = plan.rounds
         return el, [[(float(a), int(kk), int(c)) for a, kk, c in t] for t in plan.trail]
 
-    def _rule_config(self):
+    def _rule_config(self, surface=False, bounds_order=0):
+        """The training path's RuleConfig; surface=True: the eval rollout's, with the surface rule chained on (bounds_order 1 for the
+        start graphs, 0 inside the step loop)."""
         sp = self.spec
-        return RuleConfig(sp.connect_tool_all_non_fixed, self.n_eef, sp.connect_tool_surface_ratio, sp.connect_tool_all, self.engine)
+        return RuleConfig(sp.connect_tool_all_non_fixed, self.n_eef, sp.connect_tool_surface_ratio, sp.connect_tool_all, self.engine,
+                          surface=bool(surface), bounds_order=int(bounds_order))
 
-    def _ruled(self, pos, bstride, mask, tool, base, knn, bnd, cap, out=None):
-        return rule_attempt(self._rule_config(), pos, bstride, mask, tool, base, knn, bnd, cap, out=out)
+    def _ruled(self, pos, bstride, mask, tool, base, knn, bnd, cap, out=None, cfg=None):
+        return rule_attempt(cfg or self._rule_config(), pos, bstride, mask, tool, base, knn, bnd, cap, out=out)
 
-    def _rule_rounds(self, plan, el, base, state, mask, tool, thr2, cull, bnd):
-        backoff_rounds(self._rule_config(), plan, el, base, state[:, -1], mask, tool, thr2, cull, bnd)
+    def _rule_rounds(self, plan, el, base, state, mask, tool, thr2, cull, bnd, cfg=None):
+        backoff_rounds(cfg or self._rule_config(), plan, el, base, state[:, -1], mask, tool, thr2, cull, bnd)
 
     def _backoff(self, el, counts, state, mask, tool, thr2, cull, trail, waits=None):
         """The graphs of `el` whose count exceeds max_nR, rebuilt in place as a sub-batch at top-k - 1, top-k - 2, ... from
@@ -451,9 +480,10 @@ class DeviceDynDataset:
                 el.recv[dst], el.send[dst], el.row_ptr[dst], el.n_edges[dst] = se.recv[src], se.send[src], se.row_ptr[src], se.n_edges[src]
             over = over[~fit]
 
-    def _edges_per_sample(self, idx, state, mask, tool, fps_idx, n_obj, dr):
+    def _edges_per_sample(self, idx, state, mask, tool, fps_idx, n_obj, dr, eval_start=False):
         """Configs with a tool rule or a kNN range: sample by sample through construct_edges_with_backoff, stitched into one
-        EdgeList.  Correct and slow (several waits per sample)."""
+        EdgeList.  Correct and slow (several waits per sample).  eval_start: construct_graph's six bounds instead of the training
+        path's four (the eval rollout's start graphs beyond the batched rules' size limits)."""
         sp, dev, N = self.spec, self.device, self.N
         B, cap = len(idx), max(1, sp.max_nR)
         recv = torch.zeros((B, cap), dtype=torch.int32, device=dev)
@@ -473,7 +503,7 @@ class DeviceDynDataset:
                                               as_index=True, trail=trail, connect_tools_all=sp.connect_tool_all,
                                               connect_tools_surface=sp.connect_tool_surface,
                                               connect_tool_all_non_fixed=sp.connect_tool_all_non_fixed,
-                                              **plane_bounds(kp, sp.connect_tool_surface_ratio))
+                                              **(start_graph_bounds if eval_start else plane_bounds)(kp, sp.connect_tool_surface_ratio))
             n = trail[-1][2]
             recv[b, :n], send[b, :n] = el.recv[0, :n], el.send[0, :n]
             row_ptr[b], n_edges[b] = el.row_ptr[0], el.n_edges[0]

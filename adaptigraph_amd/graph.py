@@ -331,6 +331,59 @@ def nonfixed_rule_graphs(pos, pos_bstride, mask_u8, tool_u8, base, n_tools, kNN,
     return out
 
 
+def surface_graphs_limit(N, n_tools):
+    """None when ag_edges_surface_rule_graphs takes graphs of N particles with n_tools tool points, else the limit in words."""
+    if N > 4096:
+        return f"N = {N} exceeds 4096"
+    if n_tools > RULE_GRAPHS_MAX_TOOLS:
+        return f"n_tools = {n_tools} exceeds the LDS-resident tool list (at most {RULE_GRAPHS_MAX_TOOLS} tool points)"
+    return None
+
+
+def surface_rule_graphs(pos, pos_bstride, mask_u8, tool_u8, base, n_tools, bounds_pos, bounds_first, bounds_idx, bounds_n, pad_rows,
+                        ratio, bounds_order, edge_cap, engine=None, out=None, bounds_out=None, planes_out=None):
+    """ag_edges_surface_rule_graphs: the two-closest-planes rule (graph.py:175-221) on the B graphs `base` (an EdgeList as
+    ag_build_edges_graphs or ag_edges_nonfixed_rule_graphs wrote it) -> new EdgeList of capacity edge_cap.  Enqueue only.
+    Arguments as nonfixed_rule_graphs (no kNN: this rule has no filter).  bounds_order 0: the eval step loop's bounds
+    (rollout.surface_bounds), 1: construct_graph's (min_x / min_z from the unscaled maxima).  out: an EdgeList to write into;
+    bounds_out (B, 6) float32: max_y, min_y, max_x, max_z, min_x, min_z as the rule used them; planes_out (B, 2) int32: the chosen
+    planes as indices into max_y, min_x, max_x, min_z, max_z (-1 without contact).  n_edges[b] = -1 marks a refused graph: raise
+    where the counts are read."""
+    import ctypes as C
+    from . import _lib
+    dev = mask_u8.device
+    eng = engine or default_engine(dev)
+    B, N = mask_u8.shape
+    for t, dt, shape in ((mask_u8, torch.uint8, (B, N)), (tool_u8, torch.uint8, (B, N)), (bounds_first, torch.int64, (B,)),
+                         (bounds_n, torch.int32, (B,)), (base.n_edges, torch.int32, (B,)), (base.row_ptr, torch.int32, (B, N + 1))):
+        assert t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev, (t.dtype, tuple(t.shape), shape)
+    assert base.send.dtype == torch.int32 and base.send.shape[0] == B and base.send.is_contiguous()
+    assert bounds_pos.dtype == torch.float32 and bounds_pos.is_contiguous() and bounds_pos.shape[-1] == 3
+    assert bounds_idx is None or (bounds_idx.dtype == torch.int32 and bounds_idx.shape[0] == B and bounds_idx.is_contiguous())
+    assert bounds_out is None or (bounds_out.dtype == torch.float32 and tuple(bounds_out.shape) == (B, 6) and bounds_out.is_contiguous())
+    assert planes_out is None or (planes_out.dtype == torch.int32 and tuple(planes_out.shape) == (B, 2) and planes_out.is_contiguous())
+    edge_cap = max(1, int(edge_cap))
+    if out is None:
+        out = EdgeList(torch.empty((B, edge_cap), device=dev, dtype=torch.int32), torch.empty((B, edge_cap), device=dev, dtype=torch.int32),
+                       torch.empty((B, N + 1), device=dev, dtype=torch.int32), torch.empty((B,), device=dev, dtype=torch.int32), N)
+    assert out.edge_cap == edge_cap and out.recv.shape[0] == B
+    a = _lib.AgSurfaceRuleGraphsArgs()
+    a.d_pos = pos if isinstance(pos, int) else pos.data_ptr()
+    a.pos_bstride = int(pos_bstride)
+    for name, t in (("d_mask", mask_u8), ("d_tool_mask", tool_u8), ("d_send_in", base.send), ("d_row_ptr_in", base.row_ptr),
+                    ("d_n_edges_in", base.n_edges), ("d_bounds_pos", bounds_pos), ("d_bounds_first", bounds_first),
+                    ("d_bounds_idx", bounds_idx), ("d_bounds_n", bounds_n), ("d_recv", out.recv), ("d_send", out.send),
+                    ("d_row_ptr", out.row_ptr), ("d_n_edges_out", out.n_edges), ("d_bounds", bounds_out), ("d_planes", planes_out)):
+        setattr(a, name, t.data_ptr() if t is not None else None)
+    a.bounds_points = bounds_pos.numel() // 3
+    a.ratio = float(ratio)
+    a.B, a.N, a.n_tools, a.base_cap, a.edge_cap = B, N, int(n_tools), base.edge_cap, edge_cap
+    a.idx_stride = bounds_idx.shape[1] if bounds_idx is not None else 0
+    a.pad_rows, a.bounds_order = int(pad_rows), int(bounds_order)
+    eng.check(eng.lib.ag_edges_surface_rule_graphs(eng.ctx, current_stream(dev), C.byref(a)))
+    return out
+
+
 class BackoffPlan:
     """The max_nR back-off of construct_edges_with_backoff (dataset.py:317-349, rollout.py:173-222) for B graphs at once, as a
     pure host state machine: it is told the edge counts of an attempt and says which graphs need another one, and with what.
@@ -391,22 +444,34 @@ class BackoffPlan:
 @dataclass
 class RuleConfig:
     """What an attempt of the batched back-off needs besides its graphs: is the non-fixed rule on (else only the base graphs are
-    built), the tool points per graph, connect_tool_surface_ratio, connect_tool_all, the engine."""
+    built), the tool points per graph, connect_tool_surface_ratio, connect_tool_all, the engine; surface: the two-closest-planes
+    rule follows (chained behind the non-fixed rule when both are on), with its bounds in bounds_order (surface_rule_graphs)."""
     rule: bool
     n_tools: int
     ratio: float
     connect_tools_all: bool = False
     engine: object = None
+    surface: bool = False
+    bounds_order: int = 0
 
 
 def rule_attempt(cfg, pos, bstride, mask, tool, base, knn, bnd, cap, out=None):
-    """The non-fixed rule on the base graphs -> EdgeList of capacity cap (the base graphs themselves for a config without the
-    rule).  bnd: the bounds source (flat points, first (B,) int64, gather (B, stride) int32 or None, rows (B,) int32, pad_rows)."""
-    if not cfg.rule:
+    """The non-fixed rule on the base graphs, then the surface rule on its output (each only if the config has it; the base graphs
+    themselves for a config with neither) -> EdgeList of capacity cap.  Both rules read the same bounds source bnd: (flat points,
+    first (B,) int64, gather (B, stride) int32 or None, rows (B,) int32, pad_rows).  When both run, the graphs between them live in
+    a buffer as wide as the base graphs' - the surface rule removes edges too, so cap is no capacity for its input."""
+    if not cfg.rule and not cfg.surface:
         return base
     pts, first, idx, n, pad_rows = bnd
-    return nonfixed_rule_graphs(pos, bstride, mask, tool, base, cfg.n_tools, knn, pts, first, idx, n, pad_rows, cfg.ratio, cap,
-                                engine=cfg.engine, out=out)
+    el = base
+    if cfg.rule:
+        mid = max(base.edge_cap, cap) if cfg.surface else cap
+        el = nonfixed_rule_graphs(pos, bstride, mask, tool, base, cfg.n_tools, knn, pts, first, idx, n, pad_rows, cfg.ratio, mid,
+                                  engine=cfg.engine, out=None if cfg.surface else out)
+    if cfg.surface:
+        el = surface_rule_graphs(pos, bstride, mask, tool, el, cfg.n_tools, pts, first, idx, n, pad_rows, cfg.ratio, cfg.bounds_order,
+                                 cap, engine=cfg.engine, out=out)
+    return el
 
 
 def backoff_rounds(cfg, plan, el, base, last, mask, tool, thr2, cull, bnd):

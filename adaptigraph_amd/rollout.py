@@ -219,9 +219,12 @@ def rollout_eval_batch(model, ds, idx, rollout_steps=100, draws=None, keep_pred=
 
     Configs with the non-fixed rule and / or a kNN range advance together as well (_eval_rule_batched: after ag_eval_step the rule
     launch ag_edges_nonfixed_rule_graphs, fed from d_state_next, then the back-off in rounds; host_waits = steps + extra rounds).
-    Configs with connect_tool_surface (that rule can fire here and has no batched form), configs beyond the rule kernel's size
-    limit, or per_graph=True, take the same start batch through rollout_eval_step graph by graph, the error from the same kernel
-    at B = 1: correct and slow (several waits per step and graph).  keep_pred: also return every prediction and every step's edge lists.  keep_prev_fps and hetero of the reference's
+    Configs with connect_tool_surface take the same loop with ag_edges_surface_rule_graphs chained behind (or in place of) the
+    non-fixed rule, and their START graphs get the eval script's own rule: both tool rules with construct_graph's six bounds from
+    the padded rows of frame n_his - 1 (rollout/graph.py:446-458, 508-512) - ds.batch as the public calls it follows the training
+    path, which never fires the surface rule.  Configs beyond the rule kernels' size limits, or per_graph=True, take the same start
+    batch through rollout_eval_step graph by graph, the error from the same kernel at B = 1: correct and slow (several waits per
+    step and graph).  keep_pred: also return every prediction and every step's edge lists.  keep_prev_fps and hetero of the reference's
     script are out of scope: every start pair samples its own points, the physics parameter is the episode's."""
     sp, dev = ds.spec, ds.device
     idx = np.asarray(idx, np.int64).reshape(-1)
@@ -238,7 +241,7 @@ def rollout_eval_batch(model, ds, idx, rollout_steps=100, draws=None, keep_pred=
         raise ValueError("rollout_eval_batch: rollout_steps < 1")
     order = np.argsort(-lengths, kind="stable")                                          # sorted position -> caller's position
     dr = draws if draws is not None else ds.eval_draws(idx)
-    data = ds.batch(idx[order], _take(dr, order), with_fps=True)                         # (raises before any step if a start graph cannot fit)
+    data = ds.batch(idx[order], _take(dr, order), with_fps=True, _eval_start=True)       # (raises before any step if a start graph cannot fit)
     aux = ds._last_build
     eng = model.engine(dev)
     N, No, nh, cap = ds.N, sp.max_nobj, sp.n_his, max(1, sp.max_nR)
@@ -262,10 +265,11 @@ def rollout_eval_batch(model, ds, idx, rollout_steps=100, draws=None, keep_pred=
                 tab[i, j, 1] = ds._eef_off[e] + sch[i + 1][0] * ds.n_eef
                 tab[i, j, 2] = ds._eef_off[e] + sch[i + 1][1] * ds.n_eef
     waits = [0]
-    from .graph import rule_graphs_limit
-    rule_cfg = not sp.batched_edges                  # the non-fixed rule and / or a kNN range
-    # connect_tool_surface can fire in the eval rollout (all six bounds are passed on), and it has no batched form
-    rule_batched = rule_cfg and not sp.connect_tool_surface and not (sp.connect_tool_all_non_fixed and rule_graphs_limit(N, ds.n_eef))
+    from .graph import rule_graphs_limit, surface_graphs_limit
+    rule_cfg = not sp.batched_edges                  # a tool rule and / or a kNN range
+    # connect_tool_surface can fire in the eval rollout: all six bounds are passed on (rollout.py:168-222)
+    rule_batched = rule_cfg and not (sp.connect_tool_all_non_fixed and rule_graphs_limit(N, ds.n_eef)) \
+        and not (sp.connect_tool_surface and surface_graphs_limit(N, ds.n_eef))
     if per_graph or (rule_cfg and not rule_batched):
         _eval_per_graph(model, ds, eng, data, aux, dr, order, scheds, tab, errors, pred, kept, trails, keep_pred)
     elif rule_cfg:
@@ -334,10 +338,11 @@ def rollout_eval_batch(model, ds, idx, rollout_steps=100, draws=None, keep_pred=
 
 
 def _eval_rule_batched(ds, eng, data, aux, inputs, len_s, tab, errors, pred, kept, trails, keep_pred, waits):
-    """rollout_eval_batch's step loop for configs with the non-fixed rule and / or a kNN range (and without connect_tool_surface).
+    """rollout_eval_batch's step loop for configs with a tool rule and / or a kNN range.
     Per step: ag_eval_step unchanged - it writes the BASE next graphs at top-k into the second edge buffer -, then
-    ag_edges_nonfixed_rule_graphs on the graphs that go on, fed from d_state_next (bounds: the predicted rows of its last frame,
-    rollout.py:125-133; kNN: the start graph's draw, the config's midpoint), back into the first edge buffer, which the next
+    ag_edges_nonfixed_rule_graphs and / or ag_edges_surface_rule_graphs (chained when the config has both, the step loop's bound
+    order) on the graphs that go on, fed from d_state_next (bounds: the predicted rows of its last frame, pad_rows 0,
+    rollout.py:125-139; kNN: the start graph's draw, the config's midpoint), back into the first edge buffer, which the next
     step's forward reads; one read-back of their counts, then graph.BackoffPlan's rounds (DeviceDynDataset._rule_rounds) on those
     over max_nR.  Both edge buffers are max(max_nR, structural bound) wide - the rule can remove edges, so its input may exceed
     max_nR - and ag_eval_step is told edge_rows = max_nR; a config without the rule keeps the max_nR-wide double buffer."""
@@ -346,8 +351,10 @@ def _eval_rule_batched(ds, eng, data, aux, inputs, len_s, tab, errors, pred, kep
     attrs, action, phys, group, edges = inputs
     L_max, B = errors.shape
     rule, cap = sp.connect_tool_all_non_fixed, max(1, sp.max_nR)
+    cfg = ds._rule_config(sp.connect_tool_surface, 0)
+    ruled = rule or cfg.surface                                                          # a launch follows ag_eval_step
     k = min(N, sp.topk)
-    ecap = max(cap, N * (k + ds.n_eef) if k < N else N * N) if rule else cap
+    ecap = max(cap, N * (k + ds.n_eef) if k < N else N * N) if ruled else cap
     i32 = dict(dtype=torch.int32, device=dev)
     el = [EdgeList(torch.zeros((B, ecap), **i32), torch.zeros((B, ecap), **i32), edges.row_ptr.clone(), edges.n_edges.clone(), N),
           EdgeList(torch.zeros((B, ecap), **i32), torch.zeros((B, ecap), **i32), torch.zeros_like(edges.row_ptr),
@@ -387,15 +394,15 @@ def _eval_rule_batched(ds, eng, data, aux, inputs, len_s, tab, errors, pred, kep
             mask, tool = aux["state_mask"][:Bn], aux["eef_mask"][:Bn]
             # (the forward that read el[ec] is ahead of the rule on the stream: its buffer is free to take the ruled graphs)
             out = ds._ruled(state[nxt].data_ptr() + (nh - 1) * N * 3 * 4, nh * N * 3, mask, tool, base, knn_dev[:Bn], bnd, ecap,
-                            out=view(el[ec], Bn))
+                            out=view(el[ec], Bn), cfg=cfg)
             counts = out.n_edges.cpu().numpy()                                            # the step's one wait
             plan = BackoffPlan(knn_host[:Bn], sp.topk, sp.max_nR, sp.min_kNN, sp.knn_increment, has_rule=rule)
             plan.record(counts)
-            ds._rule_rounds(plan, out, base, state[nxt][:Bn], mask, tool, aux["thr2"][:Bn], aux["cull"][:Bn], bnd)
+            ds._rule_rounds(plan, out, base, state[nxt][:Bn], mask, tool, aux["thr2"][:Bn], aux["cull"][:Bn], bnd, cfg=cfg)
             waits[0] += plan.rounds
             for j in range(Bn):
                 trails[j].append([(float(p), int(kk), int(c)) for p, kk, c in plan.trail[j]])
-            if not rule:
+            if not ruled:
                 ec = en
         cur = nxt
     seen = int(status[:1].cpu()[0])                                                      # the last step's wait: the status word

@@ -704,6 +704,51 @@ typedef struct ag_rule_graphs_args {
 } ag_rule_graphs_args;
 int ag_edges_nonfixed_rule_graphs(ag_ctx* ctx, void* stream, const ag_rule_graphs_args* args);
 
+/* ---- the "tool to the two closest surface planes" rule (graph.py:175-221) for B graphs in one launch: bounds, plane choice and
+ * subset are formed on the device.  Per graph b, on the input list (ag_build_edges_graphs' output or, chained, the output of
+ * ag_edges_nonfixed_rule_graphs):
+ *   bounds : max / min of x, y and z over the rows the bounds source names (ag_rule_graphs_args' source, field for field: a zero row
+ *            takes part iff pad_rows > d_bounds_n[b]; a NaN makes the bounds of its axis NaN, as np.max does; so does no row at all),
+ *            then, in separately rounded fp32 operations with r = fp32(ratio) and q = fp32(1 - ratio formed in double):
+ *              bounds_order 0 (the eval step loop, rollout.py:132-139): max_a = max_a * r, min_a = (max_a*r - min_a) * q + min_a
+ *              bounds_order 1 (construct_graph, rollout/graph.py:446-458): min_a = (max_a - min_a) * q + min_a, then max_a = max_a * r
+ *            for a in {x, z}; max_y = max_y * r; min_y as it is.  The two orders agree at ratio 1.
+ *   contact: check = the number of input edges whose sender is a tool.  0: the input graph is copied through.
+ *   planes : value = N * (n0 * d_0 + n1 * d_1) in double, n1 = check, n0 = (#d_mask) * n_tools - check, d_k the fp32 squared distance
+ *            (one fsub, one fmul) of particle k's coordinate to the bound, k = 0 and min(1, N - 1) whatever their mask (graph.py:190-196
+ *            index with 0 / 1 values), for the planes max_y, min_x, max_x, min_z, max_z in this order (0 .. 4); the two smallest by
+ *            (value, index), NaN last.
+ *   subset : S = d_mask AND side(first) AND side(second), >= for the max planes and <= for the min planes; every tool becomes a
+ *            sender to every receiver in S, edges from a sender in S to a tool receiver are dropped, no tool<->tool edge remains
+ *            (ag_edges_apply_tool_rule at kNN 1).
+ * Guard, outputs and d_n_edges_out (-1 = refused graph; the TRUE count even above edge_cap, then nothing else is written for graph b)
+ * as ag_edges_nonfixed_rule_graphs.  A graph's result does not depend on the others in the launch.  Input and output arrays must
+ * not overlap.  Enqueue only: the call never waits for the GPU.
+ * Limits: N <= 4096, n_tools <= 64; beyond them AG_ERR_UNSUPPORTED before anything is enqueued. */
+typedef struct ag_surface_rule_graphs_args {
+    const float* d_pos;            /* graph b's (N,3) positions start at d_pos + b * pos_bstride floats (0: N*3)          */
+    int64_t pos_bstride;
+    const uint8_t* d_mask;         /* (B, N) valid particle; d_tool_mask (B, N) tool particle                            */
+    const uint8_t* d_tool_mask;
+    const int32_t* d_send_in;      /* (B, base_cap); d_row_ptr_in (B, N + 1); d_n_edges_in (B,)                          */
+    const int32_t* d_row_ptr_in;
+    const int32_t* d_n_edges_in;
+    const float* d_bounds_pos;     /* the bounds source, as ag_rule_graphs_args                                          */
+    const int64_t* d_bounds_first; /* (B,)                                                                               */
+    const int32_t* d_bounds_idx;   /* (B, idx_stride) or NULL                                                            */
+    const int32_t* d_bounds_n;     /* (B,)                                                                               */
+    int64_t bounds_points;
+    double ratio;                  /* connect_tool_surface_ratio                                                         */
+    int32_t B, N, n_tools, base_cap, idx_stride, pad_rows, bounds_order, edge_cap;
+    int32_t* d_recv;               /* (B, edge_cap); d_send alike; d_row_ptr (B, N + 1); d_n_edges_out (B,)              */
+    int32_t* d_send;
+    int32_t* d_row_ptr;
+    int32_t* d_n_edges_out;
+    float* d_bounds;               /* (B, 6) or NULL: max_y, min_y, max_x, max_z, min_x, min_z as the rule used them     */
+    int32_t* d_planes;             /* (B, 2) or NULL: the two chosen planes (0 .. 4), -1 -1 without contact              */
+} ag_surface_rule_graphs_args;
+int ag_edges_surface_rule_graphs(ag_ctx* ctx, void* stream, const ag_surface_rule_graphs_args* args);
+
 #ifdef __cplusplus
 }
 #endif

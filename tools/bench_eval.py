@@ -10,7 +10,9 @@ max_nR 1000) for 64 rollouts of 30 steps on synthetic episodes, three ways in on
 --config softbody runs softbody.yaml's entries instead (n_his 5, rest frame, pstep 4, max_nobj 300, five tool points, topk 10,
 max_nR 3500, tool-to-non-fixed rule, kNN range): the batched variant then advances the rule graphs together
 (ag_edges_nonfixed_rule_graphs per step, back-off in rounds), per_graph is the graph-by-graph path these configs took before; the
-sequential variant is the rope leg's only.
+sequential variant is the rope leg's only.  --config surface is the softbody leg with connect_tool_surface: True at ratio 0.8: the
+batched variant chains ag_edges_surface_rule_graphs behind the non-fixed rule in every step and every back-off attempt (kernel
+family "surface"), and the start graphs get the eval script's own rule.
 
 All three include building the start batch.  Reported: ms per variant (median of the rounds), per step and per rollout, the ratio
 to the sequential path, and - from a separate pass - the HIP-event time of each kernel family inside the batched path
@@ -37,7 +39,7 @@ import train_restate as TR  # noqa: E402
 from bench_dataset import DATASET, MATERIAL, SOFT_DATASET, SOFT_MATERIAL, make_episodes, make_soft_episodes  # noqa: E402
 from bench_train import CFG  # noqa: E402
 
-FAMILIES = ["fps", "assemble", "edge_count", "edge_emit", "rule", "prep", "node_enc", "edge_enc", "node_prop", "node_final", "roll_update"]
+FAMILIES = ["fps", "assemble", "edge_count", "edge_emit", "rule", "surface", "prep", "node_enc", "edge_enc", "node_prop", "node_final", "roll_update"]
 
 
 def sequential(model, ds, idx, steps):
@@ -74,16 +76,21 @@ def main():
     ap.add_argument("--rollouts", type=int, default=64)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--out", default=None)
-    ap.add_argument("--config", choices=["rope", "softbody"], default="rope")
+    ap.add_argument("--config", choices=["rope", "softbody", "surface"], default="rope")
     a = ap.parse_args()
-    soft = a.config == "softbody"
+    soft = a.config in ("softbody", "surface")
     dev = torch.device("cuda:0")
     T = a.steps + 15
     n_epis, per = 8, a.rollouts // 8
     assert per * n_epis == a.rollouts and per <= 8, "rollouts: a multiple of 8, at most 64"
     if soft:
         pairs, phys, obj, eef = make_soft_episodes(600, n_epis=n_epis, T=T)
-        ds = ag.DeviceDynDataset(SOFT_DATASET, SOFT_MATERIAL, pairs, phys, obj, eef, dev, phase="valid")
+        dcfg = SOFT_DATASET
+        if a.config == "surface":
+            import copy
+            dcfg = copy.deepcopy(SOFT_DATASET)
+            dcfg["datasets"][0].update(connect_tool_surface=True, connect_tool_surface_ratio=0.8)
+        ds = ag.DeviceDynDataset(dcfg, SOFT_MATERIAL, pairs, phys, obj, eef, dev, phase="valid")
         model = ag.DynamicsPredictor(dict(CFG, pstep=4), SOFT_MATERIAL, {"n_his": 5, "materials": ["softbody"]}, dev)
         model.load_state_dict({k: torch.from_numpy(v) for k, v in TR.make_weights(0, n_his=5).items()})
     else:
@@ -114,7 +121,8 @@ def main():
             sync()
             times[k].append((time.perf_counter() - t0) * 1e3)
     res = {"tool": "bench_eval", "device": torch.cuda.get_device_name(dev), "rounds": a.rounds, "rollouts": a.rollouts, "steps": a.steps,
-           "config": ("softbody: max_nobj 300 + 5 tool points, topk 10, max_nR 3500, non-fixed rule, kNN range [0.4, 1.0], n_his 5, pstep 4, "
+           "config": ("surface: softbody with connect_tool_surface at ratio 0.8; " if a.config == "surface" else "") +
+                     ("softbody: max_nobj 300 + 5 tool points, topk 10, max_nR 3500, non-fixed rule, kNN range [0.4, 1.0], n_his 5, pstep 4, "
                       "synthetic episodes of 600 points") if soft else
                      "rope: max_nobj 100 + 1 tool point, topk 10, max_nR 1000, synthetic episodes of 600 points",
            "n_obj_mean": float(ds.batch(idx, ds.eval_draws(idx), with_fps=True)["n_obj"].float().mean()),

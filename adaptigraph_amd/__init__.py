@@ -37,7 +37,7 @@ from .context import Engine, default_engine
 from .forward_dynamics import dynamics, dynamics_masked, dynamics_masked_diff, dynamics_mixed, rollout_work
 from .graph import (EdgeList, construct_edges_from_states_batch, construct_edges_from_states, construct_edges_index,
                     construct_edges_with_backoff, pad_torch, truncate_graph, construct_edges_graphs, nonfixed_rule_graphs, surface_rule_graphs,
-                    BackoffPlan, RuleConfig, rule_attempt, backoff_rounds)
+                    BackoffPlan, RuleConfig, rule_attempt, backoff_rounds, attempt_with_backoff)
 from .model import DynamicsPredictor
 from .plan_utils import decode_action
 from .losses import chamfer, chamfer_diff, mean_chamfer, box_loss, rope_penalty, cloth_penalty, granular_penalty
@@ -56,4 +56,4 @@ __all__ = ["hw_queues", "Engine", "default_engine", "dynamics", "dynamics_masked
            "clip_actions", "sample_action_seq", "optimize_action_mppi", "mpc_iteration", "Planner", "rollout_eval", "rollout_eval_step", "surface_bounds", "rollout_eval_batch", "eval_schedule", "EvalResult",
            "dynamics_masked_diff", "chamfer_diff", "dynamics_error_grad", "optimize_grad", "TrainStep", "PhysParamFit",
            "optimize_grad_device", "dynamics_error_grad_device", "DeviceDynDataset", "BatchDraws", "construct_edges_graphs",
-           "nonfixed_rule_graphs", "surface_rule_graphs", "BackoffPlan", "RuleConfig", "rule_attempt", "backoff_rounds"]
+           "nonfixed_rule_graphs", "surface_rule_graphs", "BackoffPlan", "RuleConfig", "rule_attempt", "backoff_rounds", "attempt_with_backoff"]

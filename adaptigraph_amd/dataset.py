@@ -3,9 +3,9 @@ batch at a time on the GPU.
 
 A batch is three launches on flat, unpadded episode buffers that were uploaded once - ag_fps_batch (both farthest-point stages),
 ag_dataset_assemble (every dense tensor, padding and augmentation included), ag_build_edges_graphs (B single-graph edge builds) -
-and ONE read-back of the B edge counts for the max_nR back-off.  Configs with the tool-to-non-fixed rule or a kNN range
-(softbody) add one launch, ag_edges_nonfixed_rule_graphs, on the B base graphs; their back-off runs in rounds over the sub-batch
-that is still over max_nR, one read-back per round (graph.BackoffPlan).  The dict that comes out goes unchanged into
+and ONE read-back of the B edge counts for the max_nR back-off.  Configs with the tool-to-non-fixed rule (softbody) add one
+launch, ag_edges_nonfixed_rule_graphs, on the B base graphs.  Every config backs off the same way (graph.attempt_with_backoff):
+in rounds over the sub-batch that is still over max_nR, one read-back per round.  The dict that comes out goes unchanged into
 TrainStep.step(data, max_edges=data['max_edges']), evaluate, accumulate and DynamicsPredictor(**data).
 
 Every random number of a batch is an explicit input (BatchDraws): a batch is a pure function of (idx, draws).  The default draws
@@ -31,8 +31,8 @@ import torch
 
 from . import _lib
 from .context import default_engine, ptr, current_stream, _require_gpu
-from .graph import (EdgeList, BackoffPlan, RuleConfig, backoff_rounds, construct_edges_with_backoff, rule_attempt, rule_graphs_limit,
-                    surface_graphs_limit)
+from .graph import (EdgeList, BackoffPlan, RuleConfig, attempt_with_backoff, construct_edges_graphs, construct_edges_with_backoff,
+                    rule_graphs_limit, surface_graphs_limit)
 from .rollout import surface_bounds
 
 FPS_MAX_POINTS = 8192        # ag_fps_batch keeps a cloud in LDS (96 KB of the CU's 160 KB at this size)
@@ -67,8 +67,9 @@ class DatasetSpec:
 
     @property
     def batched_edges(self):
-        """No tool rule and no kNN range (rope, cloth, granular, bunnybath, multiobj): all B graphs in one launch and nothing
-        after it.  The other configs (softbody) add the batched rule launch and back off in rounds (_edges_rule_batched)."""
+        """No tool rule and no kNN range (rope, cloth, granular, bunnybath, multiobj).  Every config builds its graphs through
+        DeviceDynDataset._edges_batch; this selects what such a config is spared there: the kNN draws are not read back (the
+        trails report 1.0), the rules' bounds source is not gathered, and per_sample_edges has nothing to switch to."""
         return not self.connect_tool_all_non_fixed and not self.connect_tool_surface and self.min_kNN >= 1.0
 
 
@@ -371,16 +372,12 @@ class DeviceDynDataset:
                 warnings.warn(f"DeviceDynDataset: {limit}; the graphs of this config are built sample by sample", RuntimeWarning)
                 self._warned_rule_limit = True
             per_sample_edges = True
-        if sp.batched_edges:
-            waits = [1]
-            edges, trail = self._edges_batched(out["state"], state_mask, eef_mask, thr2, cull, waits)
-            self.last_waits = waits[0]
-        elif per_sample_edges:
+        if per_sample_edges and not sp.batched_edges:
             edges, trail = self._edges_per_sample(idx, out["state"], state_mask, eef_mask, fps_idx, n_obj, dr, eval_start=surface)
             self.last_waits = None
         else:
-            edges, trail = self._edges_rule_batched(out["state"], state_mask, eef_mask, thr2, cull, tab, fps_idx, n_obj, dr,
-                                                    cfg=self._rule_config(surface, 1))
+            edges, trail = self._edges_batch(out["state"], state_mask, eef_mask, thr2, cull, tab, fps_idx, n_obj, dr,
+                                             self._rule_config(surface, 1))
         self.last_trail = trail
         self._last_build = dict(state_mask=state_mask, eef_mask=eef_mask, thr2=thr2, cull=cull)   # rollout_eval_batch reads them
         out["edges"] = edges
@@ -392,53 +389,29 @@ class DeviceDynDataset:
         return out
 
     # ------------------------------------------------------------------------------------------ edges
-    def _build_graphs(self, pos, bstride, mask, tool, thr2, cull, topk, cap=None):
-        sp, dev, eng = self.spec, self.device, self.engine
-        B, N, cap = mask.shape[0], self.N, max(1, sp.max_nR if cap is None else cap)
-        recv = torch.empty((B, cap), dtype=torch.int32, device=dev)
-        send = torch.empty((B, cap), dtype=torch.int32, device=dev)
-        row_ptr = torch.empty((B, N + 1), dtype=torch.int32, device=dev)
-        n_edges = torch.empty((B,), dtype=torch.int32, device=dev)
-        eng.check(eng.lib.ag_build_edges_graphs(eng.ctx, current_stream(dev), pos, bstride, ptr(mask), ptr(tool), B, N, ptr(thr2),
-                                                ptr(cull), int(topk), int(sp.connect_tool_all), cap, ptr(recv), ptr(send),
-                                                ptr(row_ptr), ptr(n_edges)))
-        return EdgeList(recv, send, row_ptr, n_edges, N)
-
-    def _edges_batched(self, state, mask, tool, thr2, cull, waits=None):
-        """All B graphs at top-k, one read-back of the counts; the graphs over max_nR are rebuilt as a sub-batch at top-k - 1,
-        top-k - 2, ... until they fit (dataset.py:317-349 with kNN at its minimum)."""
+    def _edges_batch(self, state, mask, tool, thr2, cull, tab, fps_idx, n_obj, dr, cfg):
+        """The one batched build (graph.attempt_with_backoff): all B base graphs at top-k in one launch, the
+        config's rule launches on them (cfg, a RuleConfig; none for a config with neither rule), ONE read-back of the counts, then
+        graph.BackoffPlan's rounds over the sub-batch that is still over max_nR, one read-back per round (dataset.py:317-349).
+        With a rule the base graphs go into buffers of the structural bound (a rule removes edges as well as adding them, so
+        max_nR is no capacity for its input) and the result into max_nR-wide ones; without, the base graphs are the result.  The
+        bounds of the rules are the un-augmented rows of frame n_his - 1, padding zeros included (dataset.py:186-209).  The
+        training path never passes min_x / min_z on (dataset.py:310-314), so connect_tool_surface fires only where cfg says so:
+        the eval rollout's start graphs chain the surface rule behind the non-fixed one on the same bounds rows.  Without
+        spec.batched_edges the kNN draws come back with the counts (a kNN range without the rule too: its trail reports them)."""
         sp, N, nh = self.spec, self.N, self.spec.n_his
-        last = state.data_ptr() + (nh - 1) * N * 3 * 4                                       # state[:, -1] in place
-        el = self._build_graphs(last, nh * N * 3, mask, tool, thr2, cull, sp.topk)
-        counts = el.n_edges.cpu().numpy()                                                    # the one wait
-        trail = [[(1.0, sp.topk, int(c))] for c in counts]
-        self._backoff(el, counts, state, mask, tool, thr2, cull, trail, waits)
-        return el, trail
-
-    def _edges_rule_batched(self, state, mask, tool, thr2, cull, tab, fps_idx, n_obj, dr, cfg=None):
-        """Configs with the non-fixed rule and / or a kNN range.  All B base graphs at top-k into buffers of the structural bound
-        (the rule removes edges as well as adding them, so max_nR is no capacity for its input), ONE rule launch into max_nR-wide
-        buffers, one read-back of the counts (with the kNN draws).  Then graph.BackoffPlan's rounds over the sub-batch that is
-        still over max_nR: a graph whose kNN went down reruns the rule on its unchanged base graph, graphs whose top-k went down
-        share one base launch per top-k; one read-back per round (dataset.py:317-349).  The bounds of the rule's threshold are
-        the un-augmented rows of frame n_his - 1, padding zeros included (dataset.py:186-209); min_x / min_z are never passed
-        on (dataset.py:310-314), so connect_tool_surface cannot fire here - unless cfg (a RuleConfig, default the training path's) says
-        so: the eval rollout's start graphs chain the surface rule behind it on the same bounds rows."""
-        sp, N, nh = self.spec, self.N, self.spec.n_his
-        cfg = cfg or self._rule_config()
-        B, rule, cap = mask.shape[0], sp.connect_tool_all_non_fixed, max(1, sp.max_nR)
+        B, cap, ruled = mask.shape[0], max(1, sp.max_nR), cfg.rule or cfg.surface
         k = min(N, sp.topk)
-        base_cap = max(1, N * (k + self.n_eef) if k < N else N * N) if (rule or cfg.surface) else cap
+        base_cap = max(1, N * (k + self.n_eef) if k < N else N * N) if ruled else cap
         last = state.data_ptr() + (nh - 1) * N * 3 * 4                                       # state[:, -1] in place
-        bnd = (self._obj, tab[:, 0].contiguous(), fps_idx, n_obj, sp.max_nobj)
-        base = self._build_graphs(last, nh * N * 3, mask, tool, thr2, cull, sp.topk, cap=base_cap)
-        el = self._ruled(last, nh * N * 3, mask, tool, base, dr.knn_thresh, bnd, cap, cfg=cfg)
-        host = torch.cat([dr.knn_thresh, el.n_edges.to(torch.float64)]).cpu().numpy()        # the one wait
-        plan = BackoffPlan(host[:B], sp.topk, sp.max_nR, sp.min_kNN, sp.knn_increment, has_rule=rule)
-        plan.record(host[B:].astype(np.int64))
-        self._rule_rounds(plan, el, base, state, mask, tool, thr2, cull, bnd, cfg=cfg)
+        bnd = (self._obj, tab[:, 0].contiguous(), fps_idx, n_obj, sp.max_nobj) if ruled else None
+        base = construct_edges_graphs(last, nh * N * 3, mask, tool, thr2, cull, sp.topk, sp.connect_tool_all, edge_cap=base_cap,
+                                      engine=self.engine)
+        plan = BackoffPlan([1.0] * B, sp.topk, sp.max_nR, sp.min_kNN, sp.knn_increment, has_rule=cfg.rule)
+        el = attempt_with_backoff(cfg, plan, last, nh * N * 3, base, dr.knn_thresh, state[:, -1], mask, tool, thr2, cull, bnd, cap,
+                                  read_knn=not sp.batched_edges)
         self.last_waits = plan.rounds
-        return el, [[(float(a), int(kk), int(c)) for a, kk, c in t] for t in plan.trail]
+        return el, plan.trail
 
     def _rule_config(self, surface=False, bounds_order=0):
         """The training path's RuleConfig; surface=True: the eval rollout's, with the surface rule chained on (bounds_order 1 for the
@@ -446,39 +419,6 @@ class DeviceDynDataset:
         sp = self.spec
         return RuleConfig(sp.connect_tool_all_non_fixed, self.n_eef, sp.connect_tool_surface_ratio, sp.connect_tool_all, self.engine,
                           surface=bool(surface), bounds_order=int(bounds_order))
-
-    def _ruled(self, pos, bstride, mask, tool, base, knn, bnd, cap, out=None, cfg=None):
-        return rule_attempt(cfg or self._rule_config(), pos, bstride, mask, tool, base, knn, bnd, cap, out=out)
-
-    def _rule_rounds(self, plan, el, base, state, mask, tool, thr2, cull, bnd, cfg=None):
-        backoff_rounds(cfg or self._rule_config(), plan, el, base, state[:, -1], mask, tool, thr2, cull, bnd)
-
-    def _backoff(self, el, counts, state, mask, tool, thr2, cull, trail, waits=None):
-        """The graphs of `el` whose count exceeds max_nR, rebuilt in place as a sub-batch at top-k - 1, top-k - 2, ... from
-        state[:, -1] until they fit; every attempt is appended to the graph's trail.  waits: a one-element list that counts the
-        read-backs (one per attempt)."""
-        sp, N = self.spec, self.N
-        over = np.nonzero(counts > sp.max_nR)[0]
-        k = sp.topk
-        while len(over):
-            k -= 1
-            if k < 1:
-                raise Exception("Exceeds max dims")                                          # utils.py:63-65 (the reference would loop on)
-            sub = torch.from_numpy(over).to(state.device)
-            pos = state[sub, -1].contiguous()
-            se = self._build_graphs(pos.data_ptr(), N * 3, mask[sub].contiguous(), tool[sub].contiguous(), thr2[sub].contiguous(),
-                                    cull[sub].contiguous(), k)
-            c = se.n_edges.cpu().numpy()
-            if waits is not None:
-                waits[0] += 1
-            for j, b in enumerate(over):
-                trail[b].append((1.0, k, int(c[j])))
-            fit = c <= sp.max_nR
-            if fit.any():
-                src = torch.from_numpy(np.nonzero(fit)[0]).to(state.device)
-                dst = sub[src]
-                el.recv[dst], el.send[dst], el.row_ptr[dst], el.n_edges[dst] = se.recv[src], se.send[src], se.row_ptr[src], se.n_edges[src]
-            over = over[~fit]
 
     def _edges_per_sample(self, idx, state, mask, tool, fps_idx, n_obj, dr, eval_start=False):
         """Configs with a tool rule or a kNN range: sample by sample through construct_edges_with_backoff, stitched into one

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 from dataclasses import dataclass
 
+import numpy as np
 import torch
 
 from .context import default_engine, ptr, current_stream, _require_gpu
@@ -162,7 +163,6 @@ def construct_edges_from_states(states, adj_thresh, mask, tool_mask, topk=10, co
     surface planes') are scalar decisions here - the same Python expressions as the reference, so thresholds round
     the same way - followed by ag_edges_apply_tool_rule on the device.  Like the reference this path synchronises
     (graph.py:129, :223)."""
-    import numpy as np
     dev = _require_gpu(states.device)
     eng = default_engine(dev)
     pos = states.to(torch.float32).contiguous()
@@ -289,22 +289,17 @@ def rule_graphs_limit(N, n_tools):
     return None
 
 
-def nonfixed_rule_graphs(pos, pos_bstride, mask_u8, tool_u8, base, n_tools, kNN, bounds_pos, bounds_first, bounds_idx, bounds_n,
-                         pad_rows, ratio, edge_cap, engine=None, out=None, thr_out=None):
-    """ag_edges_nonfixed_rule_graphs: the non-fixed rule (graph.py:125-171) and its kNN filter on the B base graphs `base` (an
-    EdgeList as ag_build_edges_graphs wrote it) -> new EdgeList of capacity edge_cap.  Enqueue only.
-    pos: a float32 tensor (B, N, 3) or a device address, graph b at + b * pos_bstride floats (0: N * 3); mask_u8 / tool_u8 (B, N)
-    uint8; kNN (B,) float64; the bounds source: bounds_pos flat (P, 3) float32, bounds_first (B,) int64, bounds_idx (B, stride) int32
-    or None, bounds_n (B,) int32, pad_rows, ratio (include/adaptigraph_amd.h).  out: an EdgeList to write into; thr_out: (B,)
-    float32 that receives the thresholds.  n_edges[b] = -1 marks a refused graph: raise where the counts are read."""
+def _rule_graphs(export, a, own, pos, pos_bstride, mask_u8, tool_u8, base, n_tools, bounds_pos, bounds_first, bounds_idx, bounds_n, pad_rows,
+                 ratio, edge_cap, engine, out):
+    """What the two rule launches share: the checks on the common tensors, the `out` allocation and the common fields of `a` (an
+    AgRuleGraphsArgs or AgSurfaceRuleGraphsArgs; the two structs name them alike); own: the rule's own (field, tensor or None)
+    pairs.  Launches eng.lib.<export> -> out."""
     import ctypes as C
-    from . import _lib
     dev = mask_u8.device
     eng = engine or default_engine(dev)
     B, N = mask_u8.shape
-    for t, dt, shape in ((mask_u8, torch.uint8, (B, N)), (tool_u8, torch.uint8, (B, N)), (kNN, torch.float64, (B,)),
-                         (bounds_first, torch.int64, (B,)), (bounds_n, torch.int32, (B,)), (base.n_edges, torch.int32, (B,)),
-                         (base.row_ptr, torch.int32, (B, N + 1))):
+    for t, dt, shape in ((mask_u8, torch.uint8, (B, N)), (tool_u8, torch.uint8, (B, N)), (bounds_first, torch.int64, (B,)),
+                         (bounds_n, torch.int32, (B,)), (base.n_edges, torch.int32, (B,)), (base.row_ptr, torch.int32, (B, N + 1))):
         assert t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev, (t.dtype, tuple(t.shape), shape)
     assert base.send.dtype == torch.int32 and base.send.shape[0] == B and base.send.is_contiguous()
     assert bounds_pos.dtype == torch.float32 and bounds_pos.is_contiguous() and bounds_pos.shape[-1] == 3
@@ -314,21 +309,36 @@ def nonfixed_rule_graphs(pos, pos_bstride, mask_u8, tool_u8, base, n_tools, kNN,
         out = EdgeList(torch.empty((B, edge_cap), device=dev, dtype=torch.int32), torch.empty((B, edge_cap), device=dev, dtype=torch.int32),
                        torch.empty((B, N + 1), device=dev, dtype=torch.int32), torch.empty((B,), device=dev, dtype=torch.int32), N)
     assert out.edge_cap == edge_cap and out.recv.shape[0] == B
-    a = _lib.AgRuleGraphsArgs()
     a.d_pos = pos if isinstance(pos, int) else pos.data_ptr()
     a.pos_bstride = int(pos_bstride)
     for name, t in (("d_mask", mask_u8), ("d_tool_mask", tool_u8), ("d_send_in", base.send), ("d_row_ptr_in", base.row_ptr),
-                    ("d_n_edges_in", base.n_edges), ("d_kNN", kNN), ("d_bounds_pos", bounds_pos), ("d_bounds_first", bounds_first),
+                    ("d_n_edges_in", base.n_edges), ("d_bounds_pos", bounds_pos), ("d_bounds_first", bounds_first),
                     ("d_bounds_idx", bounds_idx), ("d_bounds_n", bounds_n), ("d_recv", out.recv), ("d_send", out.send),
-                    ("d_row_ptr", out.row_ptr), ("d_n_edges_out", out.n_edges), ("d_thr", thr_out)):
+                    ("d_row_ptr", out.row_ptr), ("d_n_edges_out", out.n_edges)) + tuple(own):
         setattr(a, name, t.data_ptr() if t is not None else None)
     a.bounds_points = bounds_pos.numel() // 3
     a.ratio = float(ratio)
     a.B, a.N, a.n_tools, a.base_cap, a.edge_cap = B, N, int(n_tools), base.edge_cap, edge_cap
     a.idx_stride = bounds_idx.shape[1] if bounds_idx is not None else 0
     a.pad_rows = int(pad_rows)
-    eng.check(eng.lib.ag_edges_nonfixed_rule_graphs(eng.ctx, current_stream(dev), C.byref(a)))
+    eng.check(getattr(eng.lib, export)(eng.ctx, current_stream(dev), C.byref(a)))
     return out
+
+
+def nonfixed_rule_graphs(pos, pos_bstride, mask_u8, tool_u8, base, n_tools, kNN, bounds_pos, bounds_first, bounds_idx, bounds_n,
+                         pad_rows, ratio, edge_cap, engine=None, out=None, thr_out=None):
+    """ag_edges_nonfixed_rule_graphs: the non-fixed rule (graph.py:125-171) and its kNN filter on the B base graphs `base` (an
+    EdgeList as ag_build_edges_graphs wrote it) -> new EdgeList of capacity edge_cap.  Enqueue only.
+    pos: a float32 tensor (B, N, 3) or a device address, graph b at + b * pos_bstride floats (0: N * 3); mask_u8 / tool_u8 (B, N)
+    uint8; kNN (B,) float64; the bounds source: bounds_pos flat (P, 3) float32, bounds_first (B,) int64, bounds_idx (B, stride) int32
+    or None, bounds_n (B,) int32, pad_rows, ratio (include/adaptigraph_amd.h).  out: an EdgeList to write into; thr_out: (B,)
+    float32 that receives the thresholds.  n_edges[b] = -1 marks a refused graph: raise where the counts are read."""
+    from . import _lib
+    B = mask_u8.shape[0]
+    assert kNN.dtype == torch.float64 and tuple(kNN.shape) == (B,) and kNN.is_contiguous() and kNN.device == mask_u8.device, \
+        (kNN.dtype, tuple(kNN.shape), (B,))
+    return _rule_graphs("ag_edges_nonfixed_rule_graphs", _lib.AgRuleGraphsArgs(), (("d_kNN", kNN), ("d_thr", thr_out)), pos, pos_bstride,
+                        mask_u8, tool_u8, base, n_tools, bounds_pos, bounds_first, bounds_idx, bounds_n, pad_rows, ratio, edge_cap, engine, out)
 
 
 def surface_graphs_limit(N, n_tools):
@@ -349,39 +359,14 @@ def surface_rule_graphs(pos, pos_bstride, mask_u8, tool_u8, base, n_tools, bound
     bounds_out (B, 6) float32: max_y, min_y, max_x, max_z, min_x, min_z as the rule used them; planes_out (B, 2) int32: the chosen
     planes as indices into max_y, min_x, max_x, min_z, max_z (-1 without contact).  n_edges[b] = -1 marks a refused graph: raise
     where the counts are read."""
-    import ctypes as C
     from . import _lib
-    dev = mask_u8.device
-    eng = engine or default_engine(dev)
-    B, N = mask_u8.shape
-    for t, dt, shape in ((mask_u8, torch.uint8, (B, N)), (tool_u8, torch.uint8, (B, N)), (bounds_first, torch.int64, (B,)),
-                         (bounds_n, torch.int32, (B,)), (base.n_edges, torch.int32, (B,)), (base.row_ptr, torch.int32, (B, N + 1))):
-        assert t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev, (t.dtype, tuple(t.shape), shape)
-    assert base.send.dtype == torch.int32 and base.send.shape[0] == B and base.send.is_contiguous()
-    assert bounds_pos.dtype == torch.float32 and bounds_pos.is_contiguous() and bounds_pos.shape[-1] == 3
-    assert bounds_idx is None or (bounds_idx.dtype == torch.int32 and bounds_idx.shape[0] == B and bounds_idx.is_contiguous())
+    B = mask_u8.shape[0]
     assert bounds_out is None or (bounds_out.dtype == torch.float32 and tuple(bounds_out.shape) == (B, 6) and bounds_out.is_contiguous())
     assert planes_out is None or (planes_out.dtype == torch.int32 and tuple(planes_out.shape) == (B, 2) and planes_out.is_contiguous())
-    edge_cap = max(1, int(edge_cap))
-    if out is None:
-        out = EdgeList(torch.empty((B, edge_cap), device=dev, dtype=torch.int32), torch.empty((B, edge_cap), device=dev, dtype=torch.int32),
-                       torch.empty((B, N + 1), device=dev, dtype=torch.int32), torch.empty((B,), device=dev, dtype=torch.int32), N)
-    assert out.edge_cap == edge_cap and out.recv.shape[0] == B
     a = _lib.AgSurfaceRuleGraphsArgs()
-    a.d_pos = pos if isinstance(pos, int) else pos.data_ptr()
-    a.pos_bstride = int(pos_bstride)
-    for name, t in (("d_mask", mask_u8), ("d_tool_mask", tool_u8), ("d_send_in", base.send), ("d_row_ptr_in", base.row_ptr),
-                    ("d_n_edges_in", base.n_edges), ("d_bounds_pos", bounds_pos), ("d_bounds_first", bounds_first),
-                    ("d_bounds_idx", bounds_idx), ("d_bounds_n", bounds_n), ("d_recv", out.recv), ("d_send", out.send),
-                    ("d_row_ptr", out.row_ptr), ("d_n_edges_out", out.n_edges), ("d_bounds", bounds_out), ("d_planes", planes_out)):
-        setattr(a, name, t.data_ptr() if t is not None else None)
-    a.bounds_points = bounds_pos.numel() // 3
-    a.ratio = float(ratio)
-    a.B, a.N, a.n_tools, a.base_cap, a.edge_cap = B, N, int(n_tools), base.edge_cap, edge_cap
-    a.idx_stride = bounds_idx.shape[1] if bounds_idx is not None else 0
-    a.pad_rows, a.bounds_order = int(pad_rows), int(bounds_order)
-    eng.check(eng.lib.ag_edges_surface_rule_graphs(eng.ctx, current_stream(dev), C.byref(a)))
-    return out
+    a.bounds_order = int(bounds_order)
+    return _rule_graphs("ag_edges_surface_rule_graphs", a, (("d_bounds", bounds_out), ("d_planes", planes_out)), pos, pos_bstride, mask_u8,
+                        tool_u8, base, n_tools, bounds_pos, bounds_first, bounds_idx, bounds_n, pad_rows, ratio, edge_cap, engine, out)
 
 
 class BackoffPlan:
@@ -400,7 +385,7 @@ class BackoffPlan:
     rounds: the number of record() calls = read-backs."""
 
     def __init__(self, knn, topk, max_nR, min_kNN=1.0, knn_increment=0.1, has_rule=True):
-        self.kNN = [float(v) for v in knn]
+        self.kNN = list(map(float, knn))
         B = len(self.kNN)
         self.topk, self.max_nR, self.min_kNN, self.knn_increment = int(topk), int(max_nR), float(min_kNN), float(knn_increment)
         self.has_rule = bool(has_rule)
@@ -414,9 +399,16 @@ class BackoffPlan:
     def record(self, counts):
         """counts[j]: the edge count of graph self.active[j] in the attempt just made.  Returns the graphs of it that now fit."""
         assert len(counts) == len(self.active)
+        self.rounds += 1
+        counts = np.asarray(counts, np.int64).tolist()
+        kNN, k_now, trail = self.kNN, self.k_now, self.trail
+        if counts and min(counts) >= 0 and max(counts) <= self.max_nR:                   # every graph fits: no state to advance
+            for b, c in zip(self.active, counts):
+                trail[b].append((kNN[b], k_now[b], c))
+            fits, self.active = self.active, []
+            return fits
         nxt, fits = [], []
         for b, c in zip(self.active, counts):
-            c = int(c)
             if c < 0:
                 raise RuntimeError("internal: ag_edges_nonfixed_rule_graphs refused a graph (base edge list or tool count inconsistent)")
             while True:
@@ -437,7 +429,6 @@ class BackoffPlan:
                     nxt.append(b)
                     break
         self.active = nxt
-        self.rounds += 1
         return fits
 
 
@@ -474,13 +465,32 @@ def rule_attempt(cfg, pos, bstride, mask, tool, base, knn, bnd, cap, out=None):
     return el
 
 
+def attempt_with_backoff(cfg, plan, pos, bstride, base, knn, last, mask, tool, thr2, cull, bnd, cap, out=None, read_knn=False):
+    """The whole batched build behind the base graphs, for every config: rule_attempt on `base` (the graphs at plan.topk; pos /
+    bstride as construct_edges_graphs took them, knn (B,) float64 on the device), ONE read-back of the counts, plan.record, then
+    backoff_rounds -> EdgeList of capacity cap, every graph within plan.max_nR (or Exception('Exceeds max dims')).  read_knn: the
+    plan's kNN values are the draws `knn`, which only the device holds; they come back in the same transfer as the counts.
+    A config with neither rule launches nothing here: the counts are the base graphs' own, a lower top-k rebuilds into buffers of
+    their capacity, and knn / bnd may be None."""
+    el = rule_attempt(cfg, pos, bstride, mask, tool, base, knn, bnd, cap, out=out)
+    if read_knn:
+        host = torch.cat([knn, el.n_edges.to(torch.float64)]).cpu().numpy()                  # the one wait
+        plan.kNN, counts = host[:len(knn)].tolist(), host[len(knn):].astype(np.int64)
+    else:
+        counts = el.n_edges.cpu().numpy()                                                    # the one wait
+    plan.record(counts)
+    backoff_rounds(cfg, plan, el, base, last, mask, tool, thr2, cull, bnd)
+    return el
+
+
 def backoff_rounds(cfg, plan, el, base, last, mask, tool, thr2, cull, bnd):
     """BackoffPlan's rounds after the first attempt: per round the sub-batch plan.active, one group per top-k (the kNN group reruns
     the rule on its rows of `base`, a lower top-k rebuilds the base graphs from `last`, the (B, N, 3) positions), ONE read-back of
     the round's counts, and the graphs that now fit are copied into their rows of `el`.  Rows of el / base / last / mask / tool /
-    thr2 / cull / bnd correspond; a graph fits when its count is within plan.max_nR, whatever el's capacity."""
+    thr2 / cull / bnd correspond; a graph fits when its count is within plan.max_nR, whatever el's capacity.  The kNN values and the
+    bounds rows of a sub-batch are gathered only for a config whose rules read them (bnd may be None otherwise)."""
     N, dev = el.N, mask.device
-    pts, first, idx, n_rows, pad_rows = bnd
+    ruled = cfg.rule or cfg.surface
     while plan.active:
         groups = {}
         for b in plan.active:
@@ -496,10 +506,14 @@ def backoff_rounds(cfg, plan, el, base, last, mask, tool, thr2, cull, bnd):
             else:
                 b_el = construct_edges_graphs(pos, 0, m, t, thr2[sub].contiguous(), cull[sub].contiguous(), kk, cfg.connect_tools_all,
                                               edge_cap=base.edge_cap, engine=cfg.engine)
-            knn = torch.tensor([plan.kNN[b] for b in g], dtype=torch.float64).to(dev)
-            sub_bnd = (pts, first[sub], None if idx is None else idx[sub], n_rows[sub], pad_rows)
+            knn = sub_bnd = None
+            if ruled:
+                pts, first, idx, n_rows, pad_rows = bnd
+                knn = torch.tensor([plan.kNN[b] for b in g], dtype=torch.float64).to(dev)
+                sub_bnd = (pts, first[sub], None if idx is None else idx[sub], n_rows[sub], pad_rows)
             parts.append((sub, rule_attempt(cfg, pos, 0, m, t, b_el, knn, sub_bnd, el.edge_cap)))
-        counts = torch.cat([se.n_edges for _, se in parts]).cpu().numpy()                    # one wait per round
+        counts = [se.n_edges for _, se in parts]
+        counts = (counts[0] if len(counts) == 1 else torch.cat(counts)).cpu().numpy()        # one wait per round
         plan.active = [b for g in groups for b in g]                                         # the order of `counts`
         plan.record(counts)
         off = 0

@@ -21,7 +21,7 @@ import torch
 
 from . import _lib
 from .context import current_stream
-from .graph import EdgeList, construct_edges_with_backoff
+from .graph import EdgeList, BackoffPlan, attempt_with_backoff, construct_edges_with_backoff, rule_graphs_limit, surface_graphs_limit
 
 _GRAPH_KEYS = ("attrs", "p_rigid", "p_instance", "obj_mask", "eef_mask", "state_mask", "material_index")   # rollout.py:242-248
 
@@ -148,7 +148,7 @@ class EvalResult:
     pred: torch.Tensor | None = None   # (L_max, B, max_nobj, 3) with keep_pred; NaN behind each rollout's length
     edges: list | None = None     # with keep_pred: per step an EdgeList over the B graphs prediction i ran on (ended: 0 edges)
     host_waits: int = 0           # read-backs of the step loop: one per step (the counts; after the last step the status word)
-                                  # plus one per back-off attempt (rule configs: per back-off round).  The start batch's own waits are DeviceDynDataset.batch's.
+                                  # plus one per back-off round.  The start batch's own waits are DeviceDynDataset.batch's.
 
     def step_error(self):
         """rollout.py:439-444: the (min_step, B) float64 matrix of the steps every rollout reached (what error_short.txt holds)."""
@@ -217,10 +217,10 @@ def rollout_eval_batch(model, ds, idx, rollout_steps=100, draws=None, keep_pred=
     that go on, the sub-batch back-off at top-k - 1, ... for those over max_nR (Exception("Exceeds max dims") at top-k < 1), the
     swap.  A graph beyond max_nR never reaches a forward; the status word ag_eval_step raises if one did is checked at the end.
 
-    Configs with the non-fixed rule and / or a kNN range advance together as well (_eval_rule_batched: after ag_eval_step the rule
-    launch ag_edges_nonfixed_rule_graphs, fed from d_state_next, then the back-off in rounds; host_waits = steps + extra rounds).
-    Configs with connect_tool_surface take the same loop with ag_edges_surface_rule_graphs chained behind (or in place of) the
-    non-fixed rule, and their START graphs get the eval script's own rule: both tool rules with construct_graph's six bounds from
+    Configs with the non-fixed rule and / or a kNN range take the same loop (_eval_batched): after ag_eval_step the rule launch
+    ag_edges_nonfixed_rule_graphs, fed from d_state_next, and the back-off in rounds (host_waits = steps + extra rounds).
+    Configs with connect_tool_surface chain ag_edges_surface_rule_graphs behind (or in place of) the non-fixed rule, and their
+    START graphs get the eval script's own rule: both tool rules with construct_graph's six bounds from
     the padded rows of frame n_his - 1 (rollout/graph.py:446-458, 508-512) - ds.batch as the public calls it follows the training
     path, which never fires the surface rule.  Configs beyond the rule kernels' size limits, or per_graph=True, take the same start
     batch through rollout_eval_step graph by graph, the error from the same kernel at B = 1: correct and slow (several waits per
@@ -244,7 +244,7 @@ def rollout_eval_batch(model, ds, idx, rollout_steps=100, draws=None, keep_pred=
     data = ds.batch(idx[order], _take(dr, order), with_fps=True, _eval_start=True)       # (raises before any step if a start graph cannot fit)
     aux = ds._last_build
     eng = model.engine(dev)
-    N, No, nh, cap = ds.N, sp.max_nobj, sp.n_his, max(1, sp.max_nR)
+    N, No = ds.N, sp.max_nobj
     kw = {k: v for k, v in data.items() if k.endswith("_physics_param")}
     attrs, action, phys, group, edges, _ = model._inputs(dev, data["state"], data["attrs"], None, None, data["p_instance"], data["action"],
                                                          data["edges"], kw)
@@ -265,58 +265,13 @@ def rollout_eval_batch(model, ds, idx, rollout_steps=100, draws=None, keep_pred=
                 tab[i, j, 1] = ds._eef_off[e] + sch[i + 1][0] * ds.n_eef
                 tab[i, j, 2] = ds._eef_off[e] + sch[i + 1][1] * ds.n_eef
     waits = [0]
-    from .graph import rule_graphs_limit, surface_graphs_limit
-    rule_cfg = not sp.batched_edges                  # a tool rule and / or a kNN range
     # connect_tool_surface can fire in the eval rollout: all six bounds are passed on (rollout.py:168-222)
-    rule_batched = rule_cfg and not (sp.connect_tool_all_non_fixed and rule_graphs_limit(N, ds.n_eef)) \
-        and not (sp.connect_tool_surface and surface_graphs_limit(N, ds.n_eef))
-    if per_graph or (rule_cfg and not rule_batched):
+    limit = (sp.connect_tool_all_non_fixed and rule_graphs_limit(N, ds.n_eef)) or (sp.connect_tool_surface and surface_graphs_limit(N, ds.n_eef))
+    if per_graph or limit:
         _eval_per_graph(model, ds, eng, data, aux, dr, order, scheds, tab, errors, pred, kept, trails, keep_pred)
-    elif rule_cfg:
-        _eval_rule_batched(ds, eng, data, aux, (attrs, action, phys, group, edges), lengths[order], tab, errors, pred, kept, trails,
-                           keep_pred, waits)
     else:
-        tab_d = torch.from_numpy(tab).to(dev)
-        status = torch.zeros(4, dtype=torch.int32, device=dev)
-        state = [data["state"], data["state"].clone()]
-        act = [action, action.clone()]
-        el = [edges, EdgeList(torch.zeros_like(edges.recv), torch.zeros_like(edges.send), torch.zeros_like(edges.row_ptr),
-                              torch.zeros_like(edges.n_edges), N)]
-        len_s = lengths[order]
-        cur = 0
-        for s in range(L_max):
-            Bs, Bn = int((len_s > s).sum()), int((len_s > s + 1).sum())
-            nxt = 1 - cur
-            if keep_pred:
-                kept.append(EdgeList(el[cur].recv.clone(), el[cur].send.clone(), el[cur].row_ptr.clone(), el[cur].n_edges.clone(), N))
-                kept[-1].n_edges[Bs:] = 0
-            a = _eval_step_args(ds, Bs, sp.topk, cap)
-            a.d_state, a.d_action, a.d_attrs, a.d_phys, a.d_group = (t.data_ptr() for t in (state[cur], act[cur], attrs, phys, group))
-            a.d_recv, a.d_send, a.d_row_ptr, a.d_n_edges = (t.data_ptr() for t in (el[cur].recv, el[cur].send, el[cur].row_ptr, el[cur].n_edges))
-            a.d_fps_idx, a.d_n_obj, a.d_frames = data["fps_idx"].data_ptr(), data["n_obj"].data_ptr(), tab_d[s].data_ptr()
-            a.d_state_mask, a.d_eef_mask = aux["state_mask"].data_ptr(), aux["eef_mask"].data_ptr()
-            a.d_thr2, a.d_cull = aux["thr2"].data_ptr(), aux["cull"].data_ptr()
-            a.pred_given, a.step, a.err_stride = 0, s, B
-            a.d_pred, a.d_err = pred[s if keep_pred else 0].data_ptr(), errors.data_ptr()
-            a.d_state_next, a.d_action_next = state[nxt].data_ptr(), act[nxt].data_ptr()
-            a.d_recv_next, a.d_send_next, a.d_row_ptr_next, a.d_n_edges_next = (
-                t.data_ptr() for t in (el[nxt].recv, el[nxt].send, el[nxt].row_ptr, el[nxt].n_edges))
-            a.d_status = status.data_ptr()
-            eng.check(eng.lib.ag_eval_step(eng.ctx, current_stream(dev), C.byref(a)))
-            if Bn > 0:
-                counts = el[nxt].n_edges[:Bn].cpu().numpy()                              # the step's one wait
-                waits[0] += 1
-                step_trail = [[(1.0, sp.topk, int(c))] for c in counts]
-                view = EdgeList(el[nxt].recv[:Bn], el[nxt].send[:Bn], el[nxt].row_ptr[:Bn], el[nxt].n_edges[:Bn], N)
-                ds._backoff(view, counts, state[nxt][:Bn], aux["state_mask"][:Bn], aux["eef_mask"][:Bn], aux["thr2"][:Bn],
-                            aux["cull"][:Bn], step_trail, waits)
-                for j in range(Bn):
-                    trails[j].append(step_trail[j])
-            cur = nxt
-        seen = int(status[:1].cpu()[0])                                                  # the last step's wait: the status word
-        waits[0] += 1
-        if seen > 0:
-            raise Exception("Exceeds max dims")
+        _eval_batched(ds, eng, data, aux, (attrs, action, phys, group, edges), lengths[order], tab, errors, pred, kept, trails, keep_pred,
+                      waits)
     # ---- back to the caller's order
     o = torch.from_numpy(order).to(dev)
     out_err = torch.empty_like(errors)
@@ -337,16 +292,16 @@ def rollout_eval_batch(model, ds, idx, rollout_steps=100, draws=None, keep_pred=
     return EvalResult(out_err, lengths, scheds, out_trails, out_pred, out_edges, waits[0])
 
 
-def _eval_rule_batched(ds, eng, data, aux, inputs, len_s, tab, errors, pred, kept, trails, keep_pred, waits):
-    """rollout_eval_batch's step loop for configs with a tool rule and / or a kNN range.
-    Per step: ag_eval_step unchanged - it writes the BASE next graphs at top-k into the second edge buffer -, then
-    ag_edges_nonfixed_rule_graphs and / or ag_edges_surface_rule_graphs (chained when the config has both, the step loop's bound
-    order) on the graphs that go on, fed from d_state_next (bounds: the predicted rows of its last frame, pad_rows 0,
-    rollout.py:125-139; kNN: the start graph's draw, the config's midpoint), back into the first edge buffer, which the next
-    step's forward reads; one read-back of their counts, then graph.BackoffPlan's rounds (DeviceDynDataset._rule_rounds) on those
-    over max_nR.  Both edge buffers are max(max_nR, structural bound) wide - the rule can remove edges, so its input may exceed
-    max_nR - and ag_eval_step is told edge_rows = max_nR; a config without the rule keeps the max_nR-wide double buffer."""
-    from .graph import BackoffPlan
+def _eval_batched(ds, eng, data, aux, inputs, len_s, tab, errors, pred, kept, trails, keep_pred, waits):
+    """rollout_eval_batch's step loop, for every config that advances together.
+    Per step: ag_eval_step - it writes the BASE next graphs at top-k into the second edge buffer -, then
+    graph.attempt_with_backoff on the graphs that go on: ag_edges_nonfixed_rule_graphs and / or ag_edges_surface_rule_graphs
+    (chained when the config has both, the step loop's bound order), fed from d_state_next (bounds: the predicted rows of its last
+    frame, pad_rows 0, rollout.py:125-139; kNN: the start graph's draw, the config's midpoint), back into the first edge buffer,
+    which the next step's forward reads; one read-back of their counts, then graph.BackoffPlan's rounds on those over max_nR.
+    With a rule both edge buffers are max(max_nR, structural bound) wide - the rule can remove edges, so its input may exceed
+    max_nR - and ag_eval_step is told edge_rows = max_nR.  A config with neither rule keeps the max_nR-wide double buffer: no
+    launch follows the step, the base graphs are the next step's graphs and the two buffers swap roles."""
     sp, dev, N, nh = ds.spec, ds.device, ds.N, ds.spec.n_his
     attrs, action, phys, group, edges = inputs
     L_max, B = errors.shape
@@ -361,8 +316,9 @@ def _eval_rule_batched(ds, eng, data, aux, inputs, len_s, tab, errors, pred, kep
                    torch.zeros_like(edges.n_edges), N)]
     el[0].recv[:, :cap], el[0].send[:, :cap] = edges.recv, edges.send
     knn_host = [t[0][0][0] for t in trails]                                              # the start graphs' own kNN draws
-    knn_dev = torch.tensor(knn_host, dtype=torch.float64).to(dev)
-    first = torch.arange(B, dtype=torch.int64, device=dev) * (nh * N) + (nh - 1) * N     # last frame of d_state_next, in points
+    if ruled:
+        knn_dev = torch.tensor(knn_host, dtype=torch.float64).to(dev)
+        first = torch.arange(B, dtype=torch.int64, device=dev) * (nh * N) + (nh - 1) * N # last frame of d_state_next, in points
     view = (lambda e, n: EdgeList(e.recv[:n], e.send[:n], e.row_ptr[:n], e.n_edges[:n], N))
     tab_d = torch.from_numpy(tab).to(dev)
     status = torch.zeros(4, **i32)
@@ -389,19 +345,17 @@ def _eval_rule_batched(ds, eng, data, aux, inputs, len_s, tab, errors, pred, kep
         a.d_status = status.data_ptr()
         eng.check(eng.lib.ag_eval_step(eng.ctx, current_stream(dev), C.byref(a)))
         if Bn > 0:
-            base = view(el[en], Bn)
-            bnd = (state[nxt].view(-1, 3), first[:Bn], None, data["n_obj"][:Bn], 0)
-            mask, tool = aux["state_mask"][:Bn], aux["eef_mask"][:Bn]
-            # (the forward that read el[ec] is ahead of the rule on the stream: its buffer is free to take the ruled graphs)
-            out = ds._ruled(state[nxt].data_ptr() + (nh - 1) * N * 3 * 4, nh * N * 3, mask, tool, base, knn_dev[:Bn], bnd, ecap,
-                            out=view(el[ec], Bn), cfg=cfg)
-            counts = out.n_edges.cpu().numpy()                                            # the step's one wait
+            knn = bnd = out = None
+            if ruled:                                                                     # (the forward that read el[ec] is ahead of the
+                knn, out = knn_dev[:Bn], view(el[ec], Bn)                                 # rule on the stream: its buffer is free)
+                bnd = (state[nxt].view(-1, 3), first[:Bn], None, data["n_obj"][:Bn], 0)
             plan = BackoffPlan(knn_host[:Bn], sp.topk, sp.max_nR, sp.min_kNN, sp.knn_increment, has_rule=rule)
-            plan.record(counts)
-            ds._rule_rounds(plan, out, base, state[nxt][:Bn], mask, tool, aux["thr2"][:Bn], aux["cull"][:Bn], bnd, cfg=cfg)
+            attempt_with_backoff(cfg, plan, state[nxt].data_ptr() + (nh - 1) * N * 3 * 4, nh * N * 3, view(el[en], Bn), knn,
+                                 state[nxt][:Bn, -1], aux["state_mask"][:Bn], aux["eef_mask"][:Bn], aux["thr2"][:Bn], aux["cull"][:Bn],
+                                 bnd, ecap, out=out)                                      # the step's one wait, and one per round
             waits[0] += plan.rounds
             for j in range(Bn):
-                trails[j].append([(float(p), int(kk), int(c)) for p, kk, c in plan.trail[j]])
+                trails[j].append(plan.trail[j])
             if not ruled:
                 ec = en
         cur = nxt

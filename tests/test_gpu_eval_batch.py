@@ -272,6 +272,36 @@ def test_per_graph_path_equals_the_batched_path(dev):
     assert SAME_FAMILY[name] and torch.equal(_nn(pg.pred), _nn(res.pred))
 
 
+def test_a_knn_range_without_a_tool_rule_equals_the_single_graph_paths(dev):
+    """knn_range [0.4, 1.0] with min_knn 0.4 and no tool rule on the rope fixture: the back-off walks kNN down first (recorded, nothing
+    rebuilt) and then top-k.  The batched build equals the sample-by-sample one and the batched rollout the graph-by-graph one.
+    (The fixture's fourth rollout backs off at its start graph and inside the loop; without a rule kNN does not change a count.)"""
+    import adaptigraph_amd as ag
+    fx, _, model, _, _ = _case("eval_batch_rope", dev)
+    args = [copy.deepcopy(a) for a in ER.dataset_args(fx)]
+    args[0]["datasets"][0].update(knn_range=[0.4, 1.0], min_knn=0.4)
+    ds = ag.DeviceDynDataset(*args, device=dev, phase="valid")
+    sp = ds.spec
+    assert not sp.connect_tool_all_non_fixed and not sp.connect_tool_surface and sp.min_kNN == 0.4 and not sp.batched_edges
+    dr = ds.eval_draws(fx["samples"], fps_start=fx["fps_start"], rad_start=fx["rad_start"])
+    built = {}
+    for per_sample in (False, True):
+        e = ds.batch(fx["samples"], dr, per_sample_edges=per_sample)["edges"]
+        built[per_sample] = (e, [_trail(t) for t in ds.last_trail])
+    (ea, ta), (eb, tb) = built[False], built[True]
+    assert ta == tb and any(len(t) > 2 and t[1][0] < t[0][0] and t[-1][1] < sp.topk for t in ta)        # kNN went down, then top-k
+    assert torch.equal(ea.n_edges, eb.n_edges) and torch.equal(ea.row_ptr, eb.row_ptr)
+    for b, n in enumerate(ea.n_edges.tolist()):
+        assert n <= sp.max_nR and torch.equal(ea.recv[b, :n], eb.recv[b, :n]) and torch.equal(ea.send[b, :n], eb.send[b, :n]), b
+    res = ag.rollout_eval_batch(model, ds, fx["samples"], draws=dr, keep_pred=True)
+    pg = ag.rollout_eval_batch(model, ds, fx["samples"], draws=dr, keep_pred=True, per_graph=True)
+    assert pg.lengths.tolist() == res.lengths.tolist() and pg.schedule == res.schedule
+    for j in range(len(fx["samples"])):
+        _same_graphs(pg, j, res, j, int(res.lengths[j]))
+    assert any(len(t) > 2 and t[1][0] < t[0][0] and t[-1][1] < sp.topk for tr in res.trails for t in tr[1:])  # inside the loop too
+    assert torch.equal(_nn(pg.errors), _nn(res.errors)) and torch.equal(_nn(pg.pred), _nn(res.pred))
+
+
 # ------------------------------------------------------------------------------------------------ 5. it enqueues
 def test_eval_step_enqueues_and_the_rollout_waits_once_per_step(dev):
     import adaptigraph_amd as ag

@@ -1,7 +1,8 @@
 """CPU checks of the batched two-closest-planes rule: the export and its declaration, the numpy restatement of the kernel
 (tests/surface_restate.py) on every builder call the reference made for tests/golden/eval_batch_surface.npz - start graphs in
 construct_graph's bound order, rebuilt graphs in the step loop's -, and graph.rule_attempt / backoff_rounds chaining the two rule
-launches, driven through a stub engine that records what would be launched."""
+launches and graph.attempt_with_backoff on a config with neither rule, driven through a stub engine that records what would be
+launched."""
 import ctypes as C
 import json
 import os
@@ -12,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+import dataset_restate as DR
 import eval_restate as ER
 import surface_restate as SR
 from oracle import adaptigraph_oracle as O
@@ -142,7 +144,8 @@ def test_the_two_bound_orders_agree_at_ratio_one_and_differ_below_it():
 
 # ------------------------------------------------------------------------------------------------ chaining, with a stub engine
 class _StubLib:
-    """Records the launches rule_attempt / backoff_rounds would make; writes the edge counts it is told to into the outputs."""
+    """Records the launches rule_attempt / backoff_rounds would make; writes the edge counts it is told to into the outputs, and a
+    base launch marks each graph it builds: recv[b, 0] = 100 * topk + b."""
 
     def __init__(self, counts):
         self.calls, self.counts = [], counts
@@ -155,6 +158,9 @@ class _StubLib:
     def ag_build_edges_graphs(self, ctx, stream, pos, bstride, mask, tool, B, N, thr2, cull, topk, all_, cap, recv, send, rp, n):
         self.calls.append(("base", B, topk, cap))
         self._write(n.value, B, "base")
+        out = (C.c_int32 * (B * cap)).from_address(recv.value)
+        for b in range(B):
+            out[b * cap] = 100 * topk + b
         return 0
 
     def ag_edges_nonfixed_rule_graphs(self, ctx, stream, ref):
@@ -254,6 +260,52 @@ def test_backoff_rounds_rerun_both_rules_in_every_attempt(cpu_stream):
     assert plan.rounds == 2 and not plan.active and el.n_edges.tolist() == [30, 38, 36]
     assert plan.trail == [[(0.5, 5, 30)], [(0.5, 5, 41), (0.4, 5, 38)], [(0.4, 5, 45), (0.4, 4, 36)]]
     assert plan.has_rule                                                  # (still "the non-fixed rule is on")
+
+
+def test_attempt_with_backoff_on_a_config_with_neither_rule_is_the_top_k_loop(cpu_stream):
+    """The counts of tests/golden/dataset_backoff's four trails (top-k 20, max_nR 260) fed to attempt_with_backoff under a RuleConfig
+    with neither rule: only base launches, one per round at top-k 19, 18, ..., 4 on the sub-batch that is still over max_nR (two
+    graphs down to top-k 8, then one), each into buffers of the base graphs' capacity; the fixture's trails; a graph that fits lands
+    in its own row of the result and in no other."""
+    from adaptigraph_amd.graph import BackoffPlan, RuleConfig, attempt_with_backoff
+    trails = [[tuple(a) for a in t] for t in DR.load_fixture("dataset_backoff")["trail"]]
+    assert [len(t) for t in trails] == [1, 1, 17, 13]
+    B, N, topk, max_nR = 4, 10, 20, 260
+    pos, mask, tool, _ = _inputs(B, N)
+    thr2 = cull = torch.ones(B)
+    base = _graphs(B, N, max_nR)
+    base.n_edges[:] = torch.tensor([t[0][2] for t in trails], dtype=torch.int32)
+    later = [t[r][2] for r in range(1, 17) for t in trails if len(t) > r]                     # round by round, in graph order
+    eng = _StubEngine(dict(base=list(later)))
+    plan = BackoffPlan([1.0] * B, topk, max_nR, 1.0, 0.1, has_rule=False)
+    el = attempt_with_backoff(RuleConfig(False, 2, 1.0, engine=eng), plan, pos, 0, base, None, pos, mask, tool, thr2, cull, None, max_nR)
+    assert el is base and eng.lib.counts["base"] == []
+    assert eng.lib.calls == [("base", 2 if k >= 8 else 1, k, max_nR) for k in range(19, 3, -1)]
+    assert plan.rounds == 17 and not plan.active and plan.trail == trails
+    assert el.n_edges.tolist() == [t[-1][2] for t in trails] == [112, 185, 253, 255]
+    # rows 0 and 1 were never rebuilt; row 2 is graph 0 of the top-k 4 launch, row 3 graph 1 of the top-k 8 launch
+    assert el.recv[:, 0].tolist() == [0, 0, 400, 801]
+
+
+def test_knn_attempts_without_the_rule_cost_no_launch_and_no_round(cpu_stream):
+    """has_rule=False with a kNN above min_kNN: the kNN attempts are recorded with the unchanged count - no launch, no round -, then
+    top-k goes down.  The plan's kNN values are the device's draws, read with the counts."""
+    from adaptigraph_amd.graph import BackoffPlan, RuleConfig, attempt_with_backoff
+    B, N, max_nR = 2, 10, 40
+    pos, mask, tool, _ = _inputs(B, N)
+    thr2 = cull = torch.ones(B)
+    base = _graphs(B, N, max_nR)
+    base.n_edges[:] = torch.tensor([50, 30], dtype=torch.int32)
+    eng = _StubEngine(dict(base=[35]))
+    plan = BackoffPlan([1.0] * B, 5, max_nR, 0.4, 0.1, has_rule=False)
+    knn = torch.tensor([0.6, 0.4], dtype=torch.float64)
+    el = attempt_with_backoff(RuleConfig(False, 2, 1.0, engine=eng), plan, pos, 0, base, knn, pos, mask, tool, thr2, cull, None, max_nR,
+                              read_knn=True)
+    assert eng.lib.calls == [("base", 1, 4, max_nR)] and plan.rounds == 2 and not plan.active
+    k1 = 0.6 - 0.1
+    k2 = k1 - 0.1
+    assert k2 <= 0.4 and plan.trail == [[(0.6, 5, 50), (k1, 5, 50), (k2, 5, 50), (k2, 4, 35)], [(0.4, 5, 30)]]
+    assert el is base and el.n_edges.tolist() == [35, 30] and el.recv[:, 0].tolist() == [400, 0]
 
 
 def test_the_fixture_meta_lists_what_the_generator_asserted():

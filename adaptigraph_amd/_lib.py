@@ -73,24 +73,25 @@ class AgEvalStepArgs(C.Structure):
                                            "d_row_ptr_next", "d_n_edges_next", "d_status")])
 
 
+def _rule_graphs_fields(inputs=(), sizes=(), outputs=()):
+    """The fields the two batched rule structs share, with a struct's own ones where it has them: input pointers behind d_n_edges_in,
+    int32 sizes behind pad_rows, output pointers last."""
+    return ([("d_pos", C.c_void_p), ("pos_bstride", C.c_int64)] +
+            [(n, C.c_void_p) for n in ("d_mask", "d_tool_mask", "d_send_in", "d_row_ptr_in", "d_n_edges_in") + inputs +
+             ("d_bounds_pos", "d_bounds_first", "d_bounds_idx", "d_bounds_n")] +
+            [("bounds_points", C.c_int64), ("ratio", C.c_double)] +
+            [(n, C.c_int32) for n in ("B", "N", "n_tools", "base_cap", "idx_stride", "pad_rows") + sizes + ("edge_cap",)] +
+            [(n, C.c_void_p) for n in ("d_recv", "d_send", "d_row_ptr", "d_n_edges_out") + outputs])
+
+
 class AgRuleGraphsArgs(C.Structure):
     """ag_rule_graphs_args (include/adaptigraph_amd.h), field for field."""
-    _fields_ = ([("d_pos", C.c_void_p), ("pos_bstride", C.c_int64)] +
-                [(n, C.c_void_p) for n in ("d_mask", "d_tool_mask", "d_send_in", "d_row_ptr_in", "d_n_edges_in", "d_kNN", "d_bounds_pos",
-                                           "d_bounds_first", "d_bounds_idx", "d_bounds_n")] +
-                [("bounds_points", C.c_int64), ("ratio", C.c_double)] +
-                [(n, C.c_int32) for n in ("B", "N", "n_tools", "base_cap", "idx_stride", "pad_rows", "edge_cap")] +
-                [(n, C.c_void_p) for n in ("d_recv", "d_send", "d_row_ptr", "d_n_edges_out", "d_thr")])
+    _fields_ = _rule_graphs_fields(inputs=("d_kNN",), outputs=("d_thr",))
 
 
 class AgSurfaceRuleGraphsArgs(C.Structure):
     """ag_surface_rule_graphs_args (include/adaptigraph_amd.h), field for field."""
-    _fields_ = ([("d_pos", C.c_void_p), ("pos_bstride", C.c_int64)] +
-                [(n, C.c_void_p) for n in ("d_mask", "d_tool_mask", "d_send_in", "d_row_ptr_in", "d_n_edges_in", "d_bounds_pos",
-                                           "d_bounds_first", "d_bounds_idx", "d_bounds_n")] +
-                [("bounds_points", C.c_int64), ("ratio", C.c_double)] +
-                [(n, C.c_int32) for n in ("B", "N", "n_tools", "base_cap", "idx_stride", "pad_rows", "bounds_order", "edge_cap")] +
-                [(n, C.c_void_p) for n in ("d_recv", "d_send", "d_row_ptr", "d_n_edges_out", "d_bounds", "d_planes")])
+    _fields_ = _rule_graphs_fields(sizes=("bounds_order",), outputs=("d_bounds", "d_planes"))
 
 
 _lib = None

@@ -1,5 +1,5 @@
-// Private to the host files of the C-ABI (ag_api.hip, ag_api_rollout.hip, ag_api_train.hip): the context, its call slots, the
-// workspace slab and the helpers the three share.  Everything declared here is defined once, in ag_api.hip.
+// Private to the host files of the C-ABI (ag_api.hip, ag_api_edges.hip, ag_api_rollout.hip, ag_api_train.hip, ...): the context, its
+// call slots, the workspace slab and the helpers they share.  Everything declared here is defined once, in ag_api.hip.
 #pragma once
 #include "../../include/adaptigraph_amd.h"
 #include "ag_common.h"

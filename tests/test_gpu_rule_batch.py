@@ -193,6 +193,60 @@ def test_the_batched_rule_equals_the_one_graph_path(dev, si, B):
         assert np.array_equal(r1[0, :n[b]], r[b, :n[b]]) and np.array_equal(s1[0, :n[b]], s[b, :n[b]]), b
 
 
+def test_rows_striped_two_per_thread_equal_the_one_graph_path(dev):
+    """1023 + 2 particles: a 1024-thread workgroup owns two rows per thread, its last busy thread one, the rest none - the striping
+    of the guard, the tool list and the merge that no smaller size reaches.  Three graphs of a 14-graph batch: every particle valid
+    with kNN 1.0, a jittered cloud with kNN 0.5, a lattice (tied distances) with keepK = #pairs - 1."""
+    import adaptigraph_amd as ag
+    c = make_batch(1023, 2, 14, 0.8, True, True, seed=80)
+    sel = [0, 4, 13]
+    assert [c["kNN"][0], c["kNN"][4]] == [1.0, 0.5] and 0.5 < c["kNN"][13] < 1.0 and all(c["n_obj"][b] > 700 for b in sel)
+    _, out, thr = run_rule(ag, c, upload(c, dev, sel))
+    n, r, s, rp = lists(out)
+    assert np.array_equal(thr.cpu().numpy().view(np.uint32), c["thr"][sel].view(np.uint32))
+    for j, b in enumerate(sel):
+        wn, wr, ws, wrp = partner(ag, c, dev, b)
+        assert n[j] == wn, (b, n[j], wn)
+        assert np.array_equal(r[j, :wn], wr) and np.array_equal(s[j, :wn], ws) and np.array_equal(rp[j], wrp), b
+        assert (ws >= 1023).sum() > 0                                    # the rule's tool senders are in the list
+
+
+def apply_tool_rule(dev, c, base, subset, kNN, n_tools, edge_cap):
+    """ag_edges_apply_tool_rule itself on graph 0 of c, into outputs filled with -7 -> (n_out, recv, send, row_ptr)."""
+    from adaptigraph_amd.context import current_stream, default_engine, ptr
+    eng = default_engine(dev)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)      # noqa: E731
+    pos, mask, tool, sub = t(c["pos"][0]), t(c["mask"][0]).view(torch.uint8), t(c["tool"][0]).view(torch.uint8), t(subset).view(torch.uint8)
+    full = lambda n: torch.full((n,), -7, dtype=torch.int32, device=dev)  # noqa: E731
+    recv, send, row_ptr, n_out = full(edge_cap), full(edge_cap), full(c["N"] + 1), full(1)
+    eng.check(eng.lib.ag_edges_apply_tool_rule(eng.ctx, current_stream(dev), ptr(pos), ptr(mask), ptr(tool), c["N"], n_tools,
+                                               ptr(base.send), ptr(base.row_ptr), ptr(sub), float(kNN), edge_cap, ptr(recv), ptr(send),
+                                               ptr(row_ptr), ptr(n_out)))
+    return int(n_out.item()), recv.cpu().numpy(), send.cpu().numpy(), row_ptr.cpu().numpy()
+
+
+@pytest.mark.parametrize("kNN", [1.0, 0.5])
+def test_the_one_graph_export_keeps_its_own_overflow_and_tool_count_contracts(dev, kNN):
+    """include/adaptigraph_amd.h on ag_edges_apply_tool_rule, at 7 + 2 particles: above edge_cap the TRUE count and all of row_ptr
+    are written and recv / send are not; with a wrong n_tools the count is -1 and nothing else is written."""
+    import adaptigraph_amd as ag
+    c = make_batch(7, 2, 1, 1.0, False, False, seed=9)
+    d = upload(c, dev)
+    N, M = c["N"], c["M"]
+    base = ag.construct_edges_graphs(d["pos"], 0, d["mask"], d["tool"], d["thr2"], d["cull"], TOPK, False, edge_cap=N * (TOPK + M))
+    subset = c["mask"][0] & (c["pos"][0, :, 1] > c["thr"][0])
+    assert subset.sum() >= 2
+    wide = N * (TOPK + M) + N * M
+    n, r, s, rp = apply_tool_rule(dev, c, base, subset, kNN, M, wide)
+    assert 2 <= n <= wide and rp[0] == 0 and rp[N] == n and (np.diff(rp) >= 0).all() and (r[n:] == -7).all() and (s[n:] == -7).all()
+    assert np.array_equal(r[:n], np.repeat(np.arange(N), np.diff(rp))) and (s[:n] >= 0).all() and (s[:n] < N).all()
+    n2, r2, s2, rp2 = apply_tool_rule(dev, c, base, subset, kNN, M, n - 1)
+    assert n2 == n and np.array_equal(rp2, rp) and (r2 == -7).all() and (s2 == -7).all()
+    for wrong in (M - 1, M + 1):
+        n3, r3, s3, rp3 = apply_tool_rule(dev, c, base, subset, kNN, wrong, wide)
+        assert n3 == -1 and (r3 == -7).all() and (s3 == -7).all() and (rp3 == -7).all(), wrong
+
+
 def test_a_graph_over_edge_cap_reports_its_count_and_writes_nothing(dev):
     import adaptigraph_amd as ag
     c = make_batch(65, 5, 9, 1.0, True, True, seed=5)

@@ -195,6 +195,23 @@ def test_the_batched_surface_rule_equals_the_one_graph_path(dev, si, mi, B):
             assert np.array_equal(r1[0, :n[b]], r[b, :n[b]]) and np.array_equal(s1[0, :n[b]], s[b, :n[b]]), b
 
 
+def test_rows_striped_two_per_thread_equal_the_one_graph_path(dev):
+    """1023 + 2 particles: a 1024-thread workgroup owns two rows per thread, its last busy thread one, the rest none.  Three graphs
+    of a 5-graph batch behind the non-fixed rule: every particle valid, S = every valid particle, and a kNN of 0.5."""
+    import adaptigraph_amd as ag
+    c = make_batch(1023, 2, 5, 0.8, True, 0, True, seed=41)
+    sel = [0, 3, 4]
+    assert all(c["n_obj"][b] > 400 for b in sel) and c["kNN"][4] == 0.5
+    _, out, bd, _ = run_rule(ag, c, upload(c, dev, sel))
+    n, r, s, rp = lists(out)
+    bd = bd.cpu().numpy()
+    for j, b in enumerate(sel):
+        assert np.array_equal(bd[j], np.array([c["bounds"][b][k] for k in SR.BOUND_KEYS], F32), equal_nan=True), b
+        wn, wr, ws, wrp = partner(ag, c, dev, b)
+        assert n[j] == wn, (b, n[j], wn)
+        assert np.array_equal(r[j, :wn], wr) and np.array_equal(s[j, :wn], ws) and np.array_equal(rp[j], wrp), b
+
+
 @pytest.mark.parametrize("chained", [False, True])
 def test_rule_attempt_chains_the_two_launches(dev, chained):
     import adaptigraph_amd as ag

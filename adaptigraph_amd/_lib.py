@@ -33,7 +33,10 @@ EXPORTS = ["ag_abi_version", "ag_ctx_create", "ag_ctx_destroy", "ag_last_error",
            "ag_ctx_alloc_counts", "ag_rollout_work", "ag_backward", "ag_backward_inputs", "ag_cost_chamfer_backward",
            "ag_ctx_load_weights_device", "ag_adam_step", "ag_train_step", "ag_ppm_grad_step", "ag_ppm_adam_step", "ag_train_step_part",
            "ag_fps_batch", "ag_dataset_assemble", "ag_build_edges_graphs", "ag_eval_step",
-           "ag_edges_nonfixed_rule_graphs", "ag_edges_surface_rule_graphs"]
+           "ag_edges_nonfixed_rule_graphs", "ag_edges_surface_rule_graphs",
+           "ag_set_loss", "ag_set_loss_backward", "ag_train_step_losses"]
+
+AG_LOSS_MSE, AG_LOSS_CHAMFER, AG_LOSS_HAUSDORFF = 0, 1, 2
 
 OPTIONS = ["streams", "chunk", "latency", "ragged", "ell_graph", "self_dedupe", "repeat_sort", "edge_wgs", "edge_block_min",
            "enc_persist", "stagger_us", "device_decode", "zigzag", "share_first", "share_prefix", "stream_min_rows", "pipeline_fork"]
@@ -71,6 +74,11 @@ class AgEvalStepArgs(C.Structure):
                                           "store_rest_state", "pred_given", "step", "err_stride")] +
                 [(n, C.c_void_p) for n in ("d_pred", "d_err", "d_state_next", "d_action_next", "d_recv_next", "d_send_next",
                                            "d_row_ptr_next", "d_n_edges_next", "d_status")])
+
+
+class AgLossSpec(C.Structure):
+    """ag_loss_spec (include/adaptigraph_amd.h), field for field."""
+    _fields_ = [("n_terms", C.c_int32), ("kind", C.c_int32 * 4), ("weight", C.c_float * 4)]
 
 
 def _rule_graphs_fields(inputs=(), sizes=(), outputs=()):
@@ -136,6 +144,9 @@ def load():
     lib.ag_train_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, C.POINTER(vp),
                                   i32, vp, vp, vp, i32, i32, i32, C.POINTER(vp), vp, vp, vp]
     lib.ag_train_step_part.argtypes = lib.ag_train_step.argtypes + [i32, i32]
+    lib.ag_train_step_losses.argtypes = lib.ag_train_step_part.argtypes + [C.POINTER(AgLossSpec), vp]
+    lib.ag_set_loss.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]
+    lib.ag_set_loss_backward.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
     lib.ag_ppm_grad_step.argtypes = [vp, vp, C.POINTER(AgRolloutParams), vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, C.POINTER(vp),
                                      i32, i32, vp, vp, vp, vp]
     lib.ag_ppm_adam_step.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, f64, f64, f64, f64, f64, vp, vp, vp, i32, vp, vp, vp,

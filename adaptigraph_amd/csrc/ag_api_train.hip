@@ -40,6 +40,16 @@ int load_weights_device(ag_ctx* c, hipStream_t st, const float* const* d_w) {
     return enqueue_self_rows(c, st);
 }
 
+int train_step_impl(ag_ctx* c, void* stream, const float* d_state, const float* d_attrs, const float* d_action, const float* d_phys,
+                    const float* d_group, int32_t n_inst, const int32_t* d_recv, const int32_t* d_send, const int32_t* d_row_ptr,
+                    const int32_t* d_n_edges, int32_t edge_cap, int32_t B, int32_t N, int32_t n_p, const float* const* d_w,
+                    int32_t n_future, const float* d_state_future, const float* d_eef_future, const float* d_action_future,
+                    int32_t store_rest_state, int32_t edge_rows, int32_t want_grad, float* const* d_grad_w, float* d_loss,
+                    float* d_pred, int32_t* d_status, int32_t B_total, int32_t accumulate, const ag_loss_spec* spec,
+                    float* d_loss_terms);
+int set_loss_call(ag_ctx* c, void* stream, const float* d_x, const float* d_y, int B, int N, int M, int B_total, int kind,
+                  float* d_out, int32_t* d_work, const float* d_grad_out, float* d_grad_x, bool backward);
+
 }  // namespace
 
 extern "C" {
@@ -157,6 +167,64 @@ int ag_train_step_part(ag_ctx* c, void* stream, const float* d_state, const floa
                        int32_t n_future, const float* d_state_future, const float* d_eef_future, const float* d_action_future,
                        int32_t store_rest_state, int32_t edge_rows, int32_t want_grad, float* const* d_grad_w, float* d_loss,
                        float* d_pred, int32_t* d_status, int32_t B_total, int32_t accumulate) {
+    return train_step_impl(c, stream, d_state, d_attrs, d_action, d_phys, d_group, n_inst, d_recv, d_send, d_row_ptr, d_n_edges,
+                           edge_cap, B, N, n_p, d_w, n_future, d_state_future, d_eef_future, d_action_future, store_rest_state,
+                           edge_rows, want_grad, d_grad_w, d_loss, d_pred, d_status, B_total, accumulate, nullptr, nullptr);
+}
+
+int ag_train_step_losses(ag_ctx* c, void* stream, const float* d_state, const float* d_attrs, const float* d_action, const float* d_phys,
+                         const float* d_group, int32_t n_inst, const int32_t* d_recv, const int32_t* d_send, const int32_t* d_row_ptr,
+                         const int32_t* d_n_edges, int32_t edge_cap, int32_t B, int32_t N, int32_t n_p, const float* const* d_w,
+                         int32_t n_future, const float* d_state_future, const float* d_eef_future, const float* d_action_future,
+                         int32_t store_rest_state, int32_t edge_rows, int32_t want_grad, float* const* d_grad_w, float* d_loss,
+                         float* d_pred, int32_t* d_status, int32_t B_total, int32_t accumulate, const ag_loss_spec* spec,
+                         float* d_loss_terms) {
+    if (!c) return AG_ERR_INVALID;
+    if (!spec) return fail(c, AG_ERR_INVALID, "ag_train_step_losses: null loss spec");
+    if (spec->n_terms < 1 || spec->n_terms > 4) return fail(c, AG_ERR_INVALID, "ag_train_step_losses: %d loss terms (1..4)", spec->n_terms);
+    bool set_term = false;
+    for (int k = 0; k < spec->n_terms; ++k) {
+        if (spec->kind[k] < AG_LOSS_MSE || spec->kind[k] > AG_LOSS_HAUSDORFF)
+            return fail(c, AG_ERR_INVALID, "ag_train_step_losses: term %d has unknown kind %d", k, spec->kind[k]);
+        if (!std::isfinite(spec->weight[k])) return fail(c, AG_ERR_INVALID, "ag_train_step_losses: term %d has a non-finite weight", k);
+        set_term = set_term || spec->kind[k] != AG_LOSS_MSE;
+        if (spec->kind[k] == AG_LOSS_HAUSDORFF && (B_total != B || accumulate != 0))
+            return fail(c, AG_ERR_UNSUPPORTED, "ag_train_step_losses: a Hausdorff term is a max over the whole batch and does not split "
+                        "into parts (B=%d, B_total=%d, accumulate=%d)", B, B_total, accumulate);
+    }
+    if (accumulate != 0 && !d_loss_terms)
+        return fail(c, AG_ERR_INVALID, "ag_train_step_losses: accumulate needs d_loss_terms (the parts' running per-term sums)");
+    if (set_term && n_p >= 1 && 2 * (size_t)n_p > chamfer_max_points())
+        return fail(c, AG_ERR_UNSUPPORTED, "ag_train_step_losses: 2 * n_p = %d exceeds the set-loss LDS tile (%zu points)", 2 * n_p,
+                    chamfer_max_points());
+    return train_step_impl(c, stream, d_state, d_attrs, d_action, d_phys, d_group, n_inst, d_recv, d_send, d_row_ptr, d_n_edges,
+                           edge_cap, B, N, n_p, d_w, n_future, d_state_future, d_eef_future, d_action_future, store_rest_state,
+                           edge_rows, want_grad, d_grad_w, d_loss, d_pred, d_status, B_total, accumulate, spec, d_loss_terms);
+}
+
+int ag_set_loss(ag_ctx* c, void* stream, const float* d_x, const float* d_y, int32_t B, int32_t N, int32_t M, int32_t B_total,
+                int32_t kind, float* d_out, int32_t* d_work) {
+    return set_loss_call(c, stream, d_x, d_y, B, N, M, B_total, kind, d_out, d_work, nullptr, nullptr, false);
+}
+
+int ag_set_loss_backward(ag_ctx* c, void* stream, const float* d_x, const float* d_y, int32_t B, int32_t N, int32_t M, int32_t B_total,
+                         int32_t kind, const float* d_grad_out, float* d_grad_x, const int32_t* d_work) {
+    if (c && (!d_grad_out || !d_grad_x)) return fail(c, AG_ERR_INVALID, "ag_set_loss_backward: null pointer");
+    return set_loss_call(c, stream, d_x, d_y, B, N, M, B_total, kind, nullptr, const_cast<int32_t*>(d_work), d_grad_out, d_grad_x, true);
+}
+
+}  // extern "C"
+
+namespace {
+
+// ag_train_step_part (spec null: MSE x 1 by the launches it always made) and ag_train_step_losses (a validated spec)
+int train_step_impl(ag_ctx* c, void* stream, const float* d_state, const float* d_attrs, const float* d_action, const float* d_phys,
+                    const float* d_group, int32_t n_inst, const int32_t* d_recv, const int32_t* d_send, const int32_t* d_row_ptr,
+                    const int32_t* d_n_edges, int32_t edge_cap, int32_t B, int32_t N, int32_t n_p, const float* const* d_w,
+                    int32_t n_future, const float* d_state_future, const float* d_eef_future, const float* d_action_future,
+                    int32_t store_rest_state, int32_t edge_rows, int32_t want_grad, float* const* d_grad_w, float* d_loss,
+                    float* d_pred, int32_t* d_status, int32_t B_total, int32_t accumulate, const ag_loss_spec* spec,
+                    float* d_loss_terms) {
     if (!c) return AG_ERR_INVALID;
     if (!c->have_w) return fail(c, AG_ERR_NO_WEIGHTS, "ag_train_step before ag_ctx_load_weights / ag_ctx_load_weights_device");
     if (!d_state || !d_attrs || !d_action || !d_phys || !d_group || !d_recv || !d_send || !d_row_ptr || !d_n_edges || !d_state_future ||
@@ -192,8 +260,24 @@ int ag_train_step_part(ag_ctx* c, void* stream, const float* d_state, const floa
     const size_t n_state = (size_t)B * n_his * N * 3, n_act = (size_t)B * N * 3, n_pred = (size_t)B * n_p * 3;
     float* S = nullptr; float* A = nullptr; float* P = nullptr; float* motion = nullptr; double* part = nullptr;
     float* dpos = nullptr; float* D[2] = {nullptr, nullptr};
+    // a loss list: which kernels a step needs, the weights per kind (terms of one kind share their passes)
+    bool has_mse = false, has_set = false;
+    double w_mse = 0.0; float w_ch = 0.f, w_hd = 0.f;
+    for (int k = 0; spec && k < spec->n_terms; ++k) {
+        if (spec->kind[k] == AG_LOSS_MSE) { has_mse = true; w_mse += (double)spec->weight[k]; }
+        else { has_set = true; (spec->kind[k] == AG_LOSS_CHAMFER ? w_ch : w_hd) += spec->weight[k]; }
+    }
+    SetLossDev sd{};                                             // the set terms' clouds: prediction against state_future[:, fi]
+    sd.x_bstride = (long)n_p * 3; sd.y_bstride = (long)n_future * n_p * 3; sd.B = B; sd.N = n_p; sd.M = n_p;
+    int* nn_all = nullptr; int* win_all = nullptr; float* terms = d_loss_terms;
     rc = carve_slab(c, *sl, [&](Slab& s) {
         f.carve(c, s);
+        if (has_set) {
+            nn_all = s.take<int>((size_t)n_future * B * 2 * n_p);    // every step's arg-min tables and winners wait for the backward
+            win_all = s.take<int>((size_t)n_future * 4);
+            sd.part = s.take<double>(set_loss_part_doubles(B)); sd.pidx = s.take<int>(set_loss_part_ints(B));
+        }
+        if (spec && !d_loss_terms) terms = s.take<float>((size_t)n_future * spec->n_terms);
         S = s.take<float>((size_t)(n_future - 1) * n_state);     // model inputs of steps 1.. (step 0: the caller's)
         A = s.take<float>((size_t)(n_future - 1) * n_act);
         P = d_pred ? d_pred : s.take<float>((size_t)n_future * n_pred);
@@ -215,7 +299,25 @@ int ag_train_step_part(ag_ctx* c, void* stream, const float* d_state, const floa
         rc = enqueue_forward(c, f, state_of(fi), d_attrs, action_of(fi), d_phys, d_group, d_recv, d_send, d_row_ptr, f.n_eff, B, pred,
                              motion, st);
         if (rc) return rc;
-        HIPCHK(c, launch_step_loss(pred, d_state_future, B, n_p, n_future, fi, B_total, accumulate ? 1 : 0, part, d_loss, st));
+        if (!spec) HIPCHK(c, launch_step_loss(pred, d_state_future, B, n_p, n_future, fi, B_total, accumulate ? 1 : 0, part, d_loss, st));
+        else {
+            // train.py:100-102 with a loss list: the MSE partial sums, one nearest-neighbour pass for every set term, one finaliser
+            StepLossDev fl{};
+            fl.n_terms = spec->n_terms;
+            for (int k = 0; k < spec->n_terms; ++k) { fl.kind[k] = spec->kind[k]; fl.weight[k] = spec->weight[k]; }
+            fl.B = B; fl.n_p = n_p; fl.B_total = B_total; fl.fi = fi; fl.n_future = n_future; fl.accumulate = accumulate ? 1 : 0;
+            fl.loss = d_loss; fl.terms = terms;
+            if (has_mse) {
+                HIPCHK(c, launch_mse_part(pred, d_state_future, B, n_p, n_future, fi, part, st));
+                fl.mse_part = part; fl.n_mse_part = (int)train_glue_doubles(); fl.mse_n = (long)B_total * n_p * 3;
+            }
+            if (has_set) {
+                sd.x = pred; sd.y = d_state_future + (size_t)fi * n_p * 3; sd.nn = nn_all + (size_t)fi * B * 2 * n_p;
+                HIPCHK(c, launch_set_nn(sd, st));
+                fl.set_part = sd.part; fl.set_idx = sd.pidx; fl.win = win_all + 4 * fi;
+            }
+            HIPCHK(c, launch_step_loss_final(fl, st));
+        }
         if (fi + 1 < n_future)
             HIPCHK(c, launch_next_state(state_of(fi), pred, d_eef_future, d_action_future, B, N, n_p, n_his, n_future, fi, rest,
                                         S + (size_t)fi * n_state, A + (size_t)fi * n_act, st));
@@ -231,7 +333,18 @@ int ag_train_step_part(ag_ctx* c, void* stream, const float* d_state, const floa
     t.n_edges = f.n_eff; t.dpos = dpos;
     for (int fi = n_future - 1; fi >= 0; --fi) {
         const float* dnext = fi + 1 < n_future ? D[1] : nullptr;     // total dLoss/dstate of step fi + 1
-        HIPCHK(c, launch_pred_grad(P + (size_t)fi * n_pred, d_state_future, dnext, B, N, n_p, n_his, n_future, fi, B_total, dpos, st));
+        if (!spec) HIPCHK(c, launch_pred_grad(P + (size_t)fi * n_pred, d_state_future, dnext, B, N, n_p, n_his, n_future, fi, B_total, dpos, st));
+        else {
+            const float mse_scale = has_mse ? (float)(w_mse * 2.0 / ((double)B_total * n_p * 3)) : 0.f;
+            HIPCHK(c, launch_pred_grad_scaled(P + (size_t)fi * n_pred, d_state_future, dnext, B, N, n_p, n_his, n_future, fi, mse_scale,
+                                              dpos, st));
+            if (has_set) {                                          // the set terms add their share; every dpos element has one writer
+                sd.x = P + (size_t)fi * n_pred; sd.y = d_state_future + (size_t)fi * n_p * 3; sd.nn = nn_all + (size_t)fi * B * 2 * n_p;
+                SetGradDev sg{};
+                sg.w_chamfer = w_ch; sg.w_hausdorff = w_hd; sg.B_total = B_total; sg.win = win_all + 4 * fi; sg.gx = dpos; sg.add = 1;
+                HIPCHK(c, launch_set_grad(sd, sg, st));
+            }
+        }
         t.state = state_of(fi); t.action = action_of(fi);
         t.dstate = fi > 0 ? D[0] : nullptr;                          // step 0's input is data
         for (int b0 = 0; b0 < B; b0 += bw.Bb) HIPCHK(c, train_backward_chunk(t, b0, std::min(bw.Bb, B - b0), bw.wsf, bw.wsi, bw.slab, st));
@@ -242,6 +355,53 @@ int ag_train_step_part(ag_ctx* c, void* stream, const float* d_state, const floa
     }
     return AG_OK;
 }
+
+// ag_set_loss (backward false) and ag_set_loss_backward: the nearest-neighbour pass and the finaliser, then - backward - the
+// gradient.  d_work (B*(N+M) + 4 int32, optional): the arg-min tables and the Hausdorff winners.  The forward leaves them there;
+// a backward that is given them skips its own pass (the gradient kernel clamps what it reads from a table, so a stale buffer
+// gives a wrong gradient, never a wild read).
+int set_loss_call(ag_ctx* c, void* stream, const float* d_x, const float* d_y, int B, int N, int M, int B_total, int kind,
+                  float* d_out, int32_t* d_work, const float* d_grad_out, float* d_grad_x, bool backward) {
+    if (!c) return AG_ERR_INVALID;
+    if (!d_x || !d_y || (!backward && !d_out)) return fail(c, AG_ERR_INVALID, "ag_set_loss: null pointer");
+    if (B < 1 || N < 1 || M < 1 || B_total < B) return fail(c, AG_ERR_INVALID, "ag_set_loss: bad sizes B=%d N=%d M=%d B_total=%d", B, N, M, B_total);
+    if (kind != AG_LOSS_CHAMFER && kind != AG_LOSS_HAUSDORFF) return fail(c, AG_ERR_INVALID, "ag_set_loss: kind %d is no set loss", kind);
+    if (kind == AG_LOSS_HAUSDORFF && B_total != B)
+        return fail(c, AG_ERR_UNSUPPORTED, "ag_set_loss: the Hausdorff loss is a max over the whole batch and does not split into parts");
+    if ((size_t)N + (size_t)M > chamfer_max_points())
+        return fail(c, AG_ERR_UNSUPPORTED, "ag_set_loss: N+M=%d exceeds the set-loss LDS tile (%zu points)", N + M, chamfer_max_points());
+    SlotGuard call;
+    int rc = begin_call(c, stream, call);
+    if (rc) return rc;
+    hipStream_t st = call.st; CallSlot* sl = call.sl;
+    SetLossDev sd{};
+    sd.x = d_x; sd.y = d_y; sd.x_bstride = (long)N * 3; sd.y_bstride = (long)M * 3; sd.B = B; sd.N = N; sd.M = M;
+    const size_t n_nn = (size_t)B * ((size_t)N + M);
+    const bool given = backward && d_work;                       // the forward's tables: no pass of our own
+    int* win = nullptr; float* val = nullptr;
+    rc = carve_slab(c, *sl, [&](Slab& s) {
+        sd.nn = d_work ? d_work : s.take<int>(n_nn);
+        win = d_work ? d_work + n_nn : s.take<int>(4);
+        if (!given) { sd.part = s.take<double>(set_loss_part_doubles(B)); sd.pidx = s.take<int>(set_loss_part_ints(B)); }
+        val = d_out ? d_out : s.take<float>(1);
+    });
+    if (rc) return rc;
+    Scoped pr(c, FAM_COST);
+    if (!given) {
+        HIPCHK(c, launch_set_nn(sd, st));
+        HIPCHK(c, launch_set_final(sd, B_total, kind, val, win, st));
+    }
+    if (!backward) return AG_OK;
+    SetGradDev sg{};
+    sg.gout = d_grad_out; sg.B_total = B_total; sg.win = win; sg.gx = d_grad_x; sg.add = 0;
+    (kind == AG_LOSS_CHAMFER ? sg.w_chamfer : sg.w_hausdorff) = 1.f;
+    HIPCHK(c, launch_set_grad(sd, sg, st));
+    return AG_OK;
+}
+
+}  // namespace
+
+extern "C" {
 
 int ag_ppm_grad_step(ag_ctx* c, void* stream, const ag_rollout_params* p, const float* d_state0, const uint8_t* d_obj_mask,
                      const float* d_eef_xz, const float* d_eef_delta, const int32_t* h_repeat, const int32_t* d_repeat,

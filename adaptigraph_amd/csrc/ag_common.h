@@ -419,6 +419,44 @@ hipError_t launch_next_state(const float* state, const float* pred, const float*
 hipError_t launch_pred_grad(const float* pred, const float* fut, const float* dnext, int B, int N, int n_p, int n_his, int n_future,
                             int fi, int B_total, float* dpos, hipStream_t st);
 hipError_t launch_dstate_carry(float* d, const float* dnext, int B, int N, int n_his, int rest, hipStream_t st);
+// the two halves of launch_step_loss / launch_pred_grad that a step with a loss list (ag_train_step_losses) uses on their own:
+// the MSE partial sums (same kernel, same launch), and dLoss/dpred with the MSE factor given (mse_scale = weight * 2 / n; 0 with
+// no MSE term: dpos is then dnext's rows, or zero)
+hipError_t launch_mse_part(const float* pred, const float* fut, int B, int n_p, int n_future, int fi, double* part, hipStream_t st);
+hipError_t launch_pred_grad_scaled(const float* pred, const float* fut, const float* dnext, int B, int N, int n_p, int n_his,
+                                   int n_future, int fi, float mse_scale, float* dpos, hipStream_t st);
+
+// ---- set losses of the training side (ag_setloss.hip; ag_set_loss, ag_set_loss_backward, ag_train_step_losses): Chamfer and
+// Hausdorff over a batch of cloud pairs, reference src/dynamics/gnn/loss.py.  Kinds as AG_LOSS_* of the C-ABI.
+constexpr int SET_LOSS_MSE = 0, SET_LOSS_CHAMFER = 1, SET_LOSS_HAUSDORFF = 2;
+struct SetLossDev {
+    const float* x; const float* y;     // graph b's clouds start at x + b * x_bstride (N,3) and y + b * y_bstride (M,3)
+    long x_bstride, y_bstride;
+    int B, N, M;                        // N + M <= chamfer_max_points()
+    int* nn;                            // (B, N+M): nearest y of every x, then nearest x of every y
+    double* part; int* pidx;            // set_loss_part_doubles(B) / set_loss_part_ints(B): per-graph partials, see k_set_nn
+};
+struct SetGradDev {
+    const float* gout;                  // device scalar dLoss/dout, or null (= 1)
+    float w_chamfer, w_hausdorff;       // the terms' weights (0: term absent)
+    int B_total;                        // rows of the whole optimiser step: the Chamfer means' denominator
+    const int* win;                     // the finaliser's Hausdorff winners {b, i, b, j} (read only with w_hausdorff != 0)
+    float* gx; int add;                 // (B,N,3): overwritten, or added to (every element has one writer)
+};
+struct StepLossDev {                    // closes step fi of a chained training step with a loss list
+    int n_terms, kind[4]; float weight[4];
+    const double* mse_part; int n_mse_part; long mse_n;   // k_mse_part's partial sums and B_total * n_p * 3; null: no MSE term
+    const double* set_part; const int* set_idx;           // k_set_nn's partials; null: no set term
+    int B, n_p, B_total, fi, n_future, accumulate;
+    float* loss; float* terms;          // (n_future + 1), (n_future, n_terms)
+    int* win;                           // 4 ints of this step
+};
+size_t set_loss_part_doubles(int B);
+size_t set_loss_part_ints(int B);
+hipError_t launch_set_nn(const SetLossDev& a, hipStream_t st);
+hipError_t launch_set_final(const SetLossDev& a, int B_total, int kind, float* out, int* win, hipStream_t st);
+hipError_t launch_step_loss_final(const StepLossDev& a, hipStream_t st);
+hipError_t launch_set_grad(const SetLossDev& a, const SetGradDev& g, hipStream_t st);
 
 // ---- device-resident physics-parameter fit (ag_ppm.hip; ag_ppm_grad_step, ag_ppm_adam_step): the glue of the masked rollout
 // (forward_dynamics.py:209-399) around the forwards and the backward chunks, and the per-start reduction + Adam.  Rows [0,L) of a

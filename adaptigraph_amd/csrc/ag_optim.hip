@@ -352,10 +352,13 @@ inline unsigned blocks(long n) { return (unsigned)((n + 255) / 256); }
 
 size_t train_glue_doubles() { return kLossBlocks; }
 
+hipError_t launch_mse_part(const float* pred, const float* fut, int B, int n_p, int n_future, int fi, double* part, hipStream_t st) {
+    hipLaunchKernelGGL(k_mse_part, dim3(kLossBlocks), dim3(256), 0, st, pred, fut, B, n_p, n_future, fi, part);
+    return hipGetLastError();
+}
 hipError_t launch_step_loss(const float* pred, const float* fut, int B, int n_p, int n_future, int fi, int B_total, int accumulate,
                             double* part, float* loss, hipStream_t st) {
-    hipLaunchKernelGGL(k_mse_part, dim3(kLossBlocks), dim3(256), 0, st, pred, fut, B, n_p, n_future, fi, part);
-    hipError_t e = hipGetLastError();
+    hipError_t e = launch_mse_part(pred, fut, B, n_p, n_future, fi, part, st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_mse_final, dim3(1), dim3(64), 0, st, part, (long)B_total * n_p * 3, fi, n_future, accumulate, loss);
     return hipGetLastError();
@@ -366,12 +369,15 @@ hipError_t launch_next_state(const float* state, const float* pred, const float*
                        n_future - 1, fi, rest, state_next, action_next);
     return hipGetLastError();
 }
+hipError_t launch_pred_grad_scaled(const float* pred, const float* fut, const float* dnext, int B, int N, int n_p, int n_his,
+                                   int n_future, int fi, float mse_scale, float* dpos, hipStream_t st) {
+    hipLaunchKernelGGL(k_pred_grad, dim3(blocks((long)B * n_p * 3)), dim3(256), 0, st, pred, fut, dnext, B, N, n_p, n_his, n_future,
+                       fi, mse_scale, dpos);
+    return hipGetLastError();
+}
 hipError_t launch_pred_grad(const float* pred, const float* fut, const float* dnext, int B, int N, int n_p, int n_his, int n_future,
                             int fi, int B_total, float* dpos, hipStream_t st) {
-    const float scale = (float)(2.0 / ((double)B_total * n_p * 3));
-    hipLaunchKernelGGL(k_pred_grad, dim3(blocks((long)B * n_p * 3)), dim3(256), 0, st, pred, fut, dnext, B, N, n_p, n_his, n_future,
-                       fi, scale, dpos);
-    return hipGetLastError();
+    return launch_pred_grad_scaled(pred, fut, dnext, B, N, n_p, n_his, n_future, fi, (float)(2.0 / ((double)B_total * n_p * 3)), dpos, st);
 }
 hipError_t launch_dstate_carry(float* d, const float* dnext, int B, int N, int n_his, int rest, hipStream_t st) {
     hipLaunchKernelGGL(k_dstate_carry, dim3(blocks((long)B * n_his * N * 3)), dim3(256), 0, st, d, dnext, B, N, n_his, rest);

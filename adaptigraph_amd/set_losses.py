@@ -1,0 +1,152 @@
+"""Set losses of the reference's training side (src/dynamics/gnn/loss.py) on the HIP engine.
+
+    loss_funcs = [(torch.nn.MSELoss(), 1), (ChamferLoss(), 0.5), (HausdorffLoss(), 0.25)]      # train.py:65
+    loss = sum(weight * func(pred, label) for func, weight in loss_funcs)                      # train.py:100-102
+
+ChamferLoss (loss.py:4-22) and HausdorffLoss (loss.py:63-82) are torch.nn.Modules called as loss(pred, label) with pred (B,N,3)
+and label (B,M,3) on the GPU; each returns a 0-d device tensor and is a torch.autograd.Function over ag_set_loss /
+ag_set_loss_backward: no (B,N,M,3) tensor is ever formed.  The gradient goes toward pred only - the label is data, and a label
+that requires grad raises NotImplementedError.  Every row counts (no masks), as in the reference's training losses.  TrainStep
+takes the same terms by name (losses=[("mse", 1), ("chamfer", 0.5)]) and runs them inside the device-resident step.
+
+EarthMoverLoss (loss.py:25-60) is not provided: its assignment is an exact linear-sum-assignment solve on the host.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import _lib
+from .context import default_engine, ptr, current_stream, _require_gpu
+
+
+class _SetLossFunction(torch.autograd.Function):
+    """ag_set_loss forward, ag_set_loss_backward backward.  The forward leaves its arg-min tables in `work`; the backward reads them
+    instead of searching again."""
+
+    @staticmethod
+    def forward(ctx, x, y, kind):
+        dev = x.device
+        eng = default_engine(dev)
+        B, N, _ = x.shape
+        M = y.shape[1]
+        out = torch.empty((), device=dev, dtype=torch.float32)
+        work = torch.empty(B * (N + M) + 4, device=dev, dtype=torch.int32)
+        eng.check(eng.lib.ag_set_loss(eng.ctx, current_stream(dev), ptr(x), ptr(y), B, N, M, B, kind, ptr(out), ptr(work)))
+        ctx.save_for_backward(x, y, work)
+        ctx.kind = kind
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        x, y, work = ctx.saved_tensors
+        dev = x.device
+        eng = default_engine(dev)
+        B, N, _ = x.shape
+        M = y.shape[1]
+        g_out = g_out.to(torch.float32).reshape(1).contiguous()
+        g_x = torch.empty_like(x)
+        eng.check(eng.lib.ag_set_loss_backward(eng.ctx, current_stream(dev), ptr(x), ptr(y), B, N, M, B, ctx.kind, ptr(g_out),
+                                               ptr(g_x), ptr(work)))
+        return g_x, None, None
+
+
+def _set_loss(pred, label, kind, name):
+    dev = _require_gpu(pred.device)
+    if label.requires_grad:
+        raise NotImplementedError(f"{name}: the label is data; a gradient toward it is not implemented")
+    if pred.dim() != 3 or label.dim() != 3 or pred.shape[2] != 3 or label.shape[2] != 3 or pred.shape[0] != label.shape[0]:
+        raise AssertionError(f"{name}: pred (B,N,3) and label (B,M,3) expected, got {tuple(pred.shape)} and {tuple(label.shape)}")
+    x = pred.to(torch.float32).contiguous()
+    y = label.detach().to(device=dev, dtype=torch.float32).contiguous()
+    return _SetLossFunction.apply(x, y, kind)
+
+
+class ChamferLoss(torch.nn.Module):
+    """loss.py:4-22: mean over all B*N nearest distances pred -> label plus mean over all B*M nearest distances label -> pred."""
+
+    def forward(self, pred, label):
+        return _set_loss(pred, label, _lib.AG_LOSS_CHAMFER, "ChamferLoss")
+
+
+class HausdorffLoss(torch.nn.Module):
+    """loss.py:63-82: the largest nearest distance pred -> label over the whole batch plus the largest label -> pred."""
+
+    def forward(self, pred, label):
+        return _set_loss(pred, label, _lib.AG_LOSS_HAUSDORFF, "HausdorffLoss")
+
+
+class LossSpec:
+    """The loss list of a training step, parsed and checked on the host: [(term, weight), ...] with a term "mse", "chamfer" or
+    "hausdorff", or an instance of torch.nn.MSELoss, ChamferLoss or HausdorffLoss.  Pure host object (no device, no library), the
+    pattern of StepParts: every argument error is raised here, before anything is enqueued.  None = [("mse", 1)] through the
+    entry points TrainStep always used (.default)."""
+
+    MAX_TERMS = 4
+    KINDS = {"mse": _lib.AG_LOSS_MSE, "chamfer": _lib.AG_LOSS_CHAMFER, "hausdorff": _lib.AG_LOSS_HAUSDORFF}
+
+    def __init__(self, losses=None):
+        self.default = losses is None
+        terms = [("mse", 1.0)] if losses is None else list(losses)
+        if not 1 <= len(terms) <= self.MAX_TERMS:
+            raise ValueError(f"TrainStep: {len(terms)} loss terms, 1 to {self.MAX_TERMS} are served")
+        self.names, self.kinds, self.weights = [], [], []
+        for item in terms:
+            try:
+                term, weight = item
+            except (TypeError, ValueError):
+                raise ValueError(f"TrainStep: a loss term is a (term, weight) pair, got {item!r}") from None
+            name = self._name(term)
+            w = float(weight)
+            if w != w or w in (float("inf"), float("-inf")):
+                raise ValueError(f"TrainStep: the weight of loss term {name!r} is {w}")
+            self.names.append(name)
+            self.kinds.append(self.KINDS[name])
+            self.weights.append(w)
+
+    @classmethod
+    def _name(cls, term):
+        if isinstance(term, str):
+            key = term.lower()
+            if key in cls.KINDS:
+                return key
+            if key in ("emd", "earthmover", "earth_mover", "earthmoverloss"):
+                cls._refuse_earth_mover()
+            raise ValueError(f"TrainStep: unknown loss term {term!r} (known: {sorted(cls.KINDS)})")
+        if isinstance(term, torch.nn.MSELoss):
+            if term.reduction != "mean":
+                raise ValueError(f"TrainStep: MSELoss(reduction={term.reduction!r}); the step computes the mean")
+            return "mse"
+        if isinstance(term, ChamferLoss):
+            return "chamfer"
+        if isinstance(term, HausdorffLoss):
+            return "hausdorff"
+        if type(term).__name__ == "EarthMoverLoss":
+            cls._refuse_earth_mover()
+        raise ValueError(f"TrainStep: unknown loss term {term!r} (known: {sorted(cls.KINDS)} or their modules)")
+
+    @staticmethod
+    def _refuse_earth_mover():
+        raise NotImplementedError("TrainStep: the Earth-mover loss is not implemented: its assignment solve is a host step "
+                                  "(scipy.optimize.linear_sum_assignment per graph in the reference, loss.py:42), which the "
+                                  "device-resident step cannot run")
+
+    @property
+    def n_terms(self):
+        return len(self.kinds)
+
+    @property
+    def has_hausdorff(self):
+        return _lib.AG_LOSS_HAUSDORFF in self.kinds
+
+    def forbid_parts(self, what):
+        """A batch max does not split: accumulate / step_parts / a process group with a Hausdorff term."""
+        if self.has_hausdorff:
+            raise ValueError(f"TrainStep.{what} with a Hausdorff term: its max runs over the whole batch and does not split into "
+                             f"parts or ranks; use step() on one rank, or drop the term")
+
+    def c_struct(self):
+        s = _lib.AgLossSpec()
+        s.n_terms = self.n_terms
+        for k, (kind, w) in enumerate(zip(self.kinds, self.weights)):
+            s.kind[k], s.weight[k] = kind, w
+        return s

@@ -11,6 +11,11 @@ mixed-size batch with a tight max_edges each, or the shards of a data-parallel b
 ag_train_step_part with the row count of the WHOLE step as the MSE denominator, so its loss and gradients are its share of the
 full batch's (MSELoss is a mean over B * n_p * 3 and n_p is the same in every part: loss = sum over parts of B_part / B_total *
 loss_part, exactly); the shares are summed on the device in call order and Adam is applied once.
+
+losses=[(term, weight), ...] replaces the hard-wired MSE by the reference's loss list (train.py:65, 100-102): "mse", "chamfer"
+and "hausdorff" (or torch.nn.MSELoss, ChamferLoss, HausdorffLoss instances; set_losses.py), up to four terms, run by
+ag_train_step_losses inside the same device-resident step.  Chamfer is a batch mean like MSE and splits into parts the same way;
+Hausdorff is a batch max and is refused with accumulate, step_parts or a group.
 """
 from __future__ import annotations
 
@@ -20,6 +25,7 @@ import torch
 
 from .autograd import _vp_array
 from .context import Engine, ptr, current_stream, _require_gpu
+from .set_losses import LossSpec
 
 _ADAM_FIXED = {"amsgrad": False, "maximize": False}
 
@@ -120,10 +126,19 @@ class TrainStep:
     (all_reduce SUM) and takes the MAX of the overflow word, so a graph that overflowed on one rank skips the step on every rank:
     weights, m and v stay identical everywhere, and check() raises on every rank.  No count is exchanged behind the caller's
     back.  With the nccl (RCCL) backend the three collectives are enqueued on the current stream and apply() still does not wait
-    for the GPU; with gloo torch stages the tensors through the host, so apply() waits (a rehearsal backend)."""
+    for the GPU; with gloo torch stages the tensors through the host, so apply() waits (a rehearsal backend).
+
+    losses: None (MSE x 1, the step as it always was, through ag_train_step / ag_train_step_part) or the reference's loss list
+    [(term, weight), ...] of up to four terms, a term being "mse", "chamfer", "hausdorff" or an instance of torch.nn.MSELoss,
+    ChamferLoss, HausdorffLoss (LossSpec checks it on the host).  step, evaluate, accumulate, apply and step_parts then run
+    ag_train_step_losses; .last_loss_terms holds every step's terms before weighting, (n_future, n_terms) on the device.  A
+    Hausdorff term is a max over the whole batch: accumulate, step_parts and group= raise ValueError with one."""
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, n_future=3, store_rest_state=False,
-                 group=None, global_rows=None):
+                 group=None, global_rows=None, losses=None):
+        self.losses = LossSpec(losses)                          # host checks first: nothing below runs for a bad list
+        if group is not None:
+            self.losses.forbid_parts("__init__(group=...)")
         params = model.ordered_parameters()
         dev = _require_gpu(params[0].device)                     # no CPU fallback, as every other op
         self.model, self.device = model, dev
@@ -153,6 +168,9 @@ class TrainStep:
         self._small = torch.zeros(self.n_future + 2, dtype=torch.int32, device=dev)
         self._loss = self._small[:self.n_future + 1].view(torch.float32)
         self._flag = self._small[self.n_future + 1:]
+        # every step's terms before weighting, (n_future, n_terms); None on the default path, which never forms them
+        self.last_loss_terms = None if self.losses.default else torch.zeros(self.n_future, self.losses.n_terms, device=dev)
+        self._spec = None if self.losses.default else self.losses.c_struct()
         self._step = 0                                                  # host counter of enqueued optimiser steps
         self.last_pred = None
         self.group = group
@@ -167,7 +185,8 @@ class TrainStep:
         eng.check(eng.lib.ag_ctx_load_weights_device(eng.ctx, current_stream(self.device), self._w_arr))
 
     def _run(self, data, max_edges, want_grad, total=None, accumulate=False):
-        """total None: ag_train_step on the batch; else ag_train_step_part with B_total = total."""
+        """total None: ag_train_step on the batch; else ag_train_step_part with B_total = total.  With a loss list both are
+        ag_train_step_losses (B_total = B, accumulate = 0 for the whole batch)."""
         model, dev, eng = self.model, self.device, self.engine
         kw = {k: v for k, v in data.items() if k.endswith("_physics_param")}
         with torch.no_grad():
@@ -191,12 +210,14 @@ class TrainStep:
                 ptr(edges.recv), ptr(edges.send), ptr(edges.row_ptr), ptr(edges.n_edges), edges.edge_cap, B, N, n_p, self._w_arr,
                 nf, ptr(fut), ptr(eef), ptr(act_f), int(self.store_rest_state), max(1, int(max_edges)), int(want_grad), self._g_arr,
                 ptr(self._loss), ptr(pred), ptr(self._status))
+        spec = () if self._spec is None else (C.byref(self._spec), ptr(self.last_loss_terms))
         if total is None:
-            eng.check(eng.lib.ag_train_step(*args))
+            eng.check(eng.lib.ag_train_step_losses(*args, B, 0, *spec) if spec else eng.lib.ag_train_step(*args))
             self.last_pred = pred
             return self._loss[nf].clone()
         before = self._loss[:nf].clone() if accumulate else None
-        eng.check(eng.lib.ag_train_step_part(*args, int(total), int(accumulate)))
+        part = eng.lib.ag_train_step_losses if spec else eng.lib.ag_train_step_part
+        eng.check(part(*args, int(total), int(accumulate), *spec))
         self.last_pred = self.last_pred + [pred] if accumulate else [pred]
         if not accumulate:
             return self._loss[nf].clone()
@@ -216,6 +237,7 @@ class TrainStep:
         must be the same on every part; a ValueError is raised before anything is enqueued.  max_edges bounds THIS part's graphs.
         Returns this part's share of loss_sum as a 0-d device tensor (for a later part: what it added to the running fp32 loss
         vector); .last_pred is a list with one (n_future, B_part, n_p, 3) tensor per part."""
+        self.losses.forbid_parts("accumulate")
         if total is None and not self._parts.open:
             total = self.global_rows
         total, acc = self._parts.add(data["state"].shape[0], total)
@@ -226,6 +248,8 @@ class TrainStep:
         g = None if self.group is True else self.group
         dist.all_reduce(self._grad_flat, op=dist.ReduceOp.SUM, group=g)
         dist.all_reduce(self._loss, op=dist.ReduceOp.SUM, group=g)
+        if self.last_loss_terms is not None:
+            dist.all_reduce(self.last_loss_terms, op=dist.ReduceOp.SUM, group=g)
         self._flag.copy_(self._status[:1])
         dist.all_reduce(self._flag, op=dist.ReduceOp.MAX, group=g)
         self._status[:1].copy_(self._flag)
@@ -246,6 +270,7 @@ class TrainStep:
         batch of mixed graph sizes without padding every graph to the largest: sort the graphs by edge count, split them into a
         few buckets, and pass each bucket's own bound - the edge-side GEMMs of a bucket then run over its bound, not the batch's.
         Returns loss_sum (0-d device tensor)."""
+        self.losses.forbid_parts("step_parts")
         parts = list(parts)
         bounds = list(max_edges) if isinstance(max_edges, (list, tuple)) else [max_edges] * len(parts)
         if len(bounds) != len(parts) or not parts:

@@ -30,7 +30,7 @@
  *       ag_ctx_load_weights, ag_ctx_set_precision     always (host repack + copies)
  *       ag_forward, ag_rollout                        once, at the end: they return the overflow verdict (AG_ERR_MAX_NR)
  *       ag_backward, ag_backward_inputs               at the start (edge counts) and at the end
- *       ag_ctx_load_weights_device, ag_adam_step, ag_train_step, ag_train_step_part, ag_ppm_grad_step, ag_ppm_adam_step   NEVER: they only enqueue on the caller's stream; an overflowed
+ *       ag_ctx_load_weights_device, ag_adam_step, ag_train_step, ag_train_step_part, ag_train_step_losses, ag_set_loss, ag_set_loss_backward, ag_ppm_grad_step, ag_ppm_adam_step   NEVER: they only enqueue on the caller's stream; an overflowed
  *           graph is reported in device memory (d_status), which the caller reads when it chooses to
  *       ag_rollout_work                               for its plan (and a base rollout, if none is kept): it returns host numbers
  *       ag_ctx_rollout_counts (after a device-planned call without prefix sharing), ag_ctx_share_counts   wait for the device
@@ -531,6 +531,61 @@ int ag_train_step_part(ag_ctx* ctx, void* stream, const float* d_state, const fl
                        const float* d_action_future, int32_t store_rest_state, int32_t edge_rows, int32_t want_grad,
                        float* const* d_grad_w, float* d_loss, float* d_pred, int32_t* d_status, int32_t B_total,
                        int32_t accumulate);
+
+/* ---- set losses of the training side (reference src/dynamics/gnn/loss.py: ChamferLoss :4-22, HausdorffLoss :63-82) and the
+ * training step with a list of losses (train.py:65, 100-102: loss_funcs = [(func, weight), ...]).  Additive exports. ---- */
+#define AG_LOSS_MSE 0
+#define AG_LOSS_CHAMFER 1
+#define AG_LOSS_HAUSDORFF 2
+typedef struct ag_loss_spec {
+    int32_t n_terms;            /* 1..4 */
+    int32_t kind[4];            /* AG_LOSS_* */
+    float weight[4];            /* finite */
+} ag_loss_spec;
+
+/* One set loss over a batch of cloud pairs: d_x (B,N,3) the prediction, d_y (B,M,3) the label -> d_out[0].  With
+ * d(b,i,j) = sqrt(dx*dx + dy*dy + dz*dz) in fp32 (every operation rounded on its own), mx(b,i) = min_j d, my(b,j) = min_i d:
+ *   AG_LOSS_CHAMFER    sum_{b,i} mx / (B_total * N) + sum_{b,j} my / (B_total * M)   (loss.py:14-17; B_total >= B: the rows of
+ *                      the whole batch when this call holds a part of it - the parts' values then add up to the whole's)
+ *   AG_LOSS_HAUSDORFF  max_{b,i} mx + max_{b,j} my                                    (loss.py:74-77; B_total must equal B, else
+ *                      AG_ERR_UNSUPPORTED: a max does not split into parts)
+ * The sums run in fp64 in a fixed order (inside a graph, then over the graphs in index order) and are rounded once.  Arg-min and
+ * arg-max take the lowest index among equals.  A NaN coordinate makes the loss NaN.  N + M must fit the LDS tile of
+ * ag_cost_chamfer (<= ~13k points), else AG_ERR_UNSUPPORTED before anything is enqueued.  No masks: every row counts, as in the
+ * reference's training losses.
+ * d_work: NULL, or B*(N+M) + 4 int32 that receive the arg-min tables (per graph: nearest y of every x, then nearest x of every
+ * y) and the Hausdorff winners {b, i, b, j}.  Enqueue only. */
+int ag_set_loss(ag_ctx* ctx, void* stream, const float* d_x, const float* d_y, int32_t B, int32_t N, int32_t M, int32_t B_total,
+                int32_t kind, float* d_out, int32_t* d_work);
+
+/* Gradient of ag_set_loss toward x as torch autograd defines it on loss.py: the same inputs, d_grad_out[0] = dLoss/dout ->
+ * d_grad_x (B,N,3), fully written.  Each min routes to its arg-min, the norm has zero gradient at zero distance, Hausdorff
+ * reaches only its two winning pairs.  The label is data: no gradient toward y.  d_work: NULL (the nearest-neighbour pass runs
+ * again), or the buffer an ag_set_loss call on the same inputs and kind filled (its tables are used; indices are clamped before
+ * they address anything).  No atomics: repeated calls give the same bits.  Enqueue only. */
+int ag_set_loss_backward(ag_ctx* ctx, void* stream, const float* d_x, const float* d_y, int32_t B, int32_t N, int32_t M,
+                         int32_t B_total, int32_t kind, const float* d_grad_out, float* d_grad_x, const int32_t* d_work);
+
+/* ag_train_step_part with a list of losses: every argument of ag_train_step_part in the same order, then
+ *   spec          1..4 terms (kind, weight); per step loss = the fp32 sum over the list, in list order, of weight * term
+ *                 (train.py:100-102), a set term being ag_set_loss of the step's prediction (B,n_p,3) against
+ *                 d_state_future[:, fi].  d_loss keeps its layout (n_future step losses, then their fp32 sum), the backward
+ *                 starts from the list's gradient.  Terms of one kind share their kernels; one nearest-neighbour pass per step
+ *                 serves every set term.
+ *   d_loss_terms  NULL, or (n_future, n_terms) floats: every step's terms before weighting.  Required when accumulate != 0:
+ *                 the parts' running sums live there, each part's share joining in fp64 before the one rounding.
+ * B_total and accumulate act on MSE and Chamfer terms as in ag_train_step_part (both are means over the batch: a part's share
+ * is B / B_total).  A Hausdorff term with B_total != B or accumulate != 0 returns AG_ERR_UNSUPPORTED; an unknown kind, a
+ * non-finite weight or n_terms outside 1..4 AG_ERR_INVALID; 2 * n_p beyond the LDS tile with a set term AG_ERR_UNSUPPORTED - all
+ * before anything is enqueued.  spec = {1, {AG_LOSS_MSE}, {1}} gives ag_train_step_part's bits; ag_train_step and
+ * ag_train_step_part themselves are unchanged and never run this path.  Enqueue only. */
+int ag_train_step_losses(ag_ctx* ctx, void* stream, const float* d_state, const float* d_attrs, const float* d_action,
+                         const float* d_phys, const float* d_group, int32_t n_inst, const int32_t* d_recv, const int32_t* d_send,
+                         const int32_t* d_row_ptr, const int32_t* d_n_edges, int32_t edge_cap, int32_t B, int32_t N, int32_t n_p,
+                         const float* const* d_w, int32_t n_future, const float* d_state_future, const float* d_eef_future,
+                         const float* d_action_future, int32_t store_rest_state, int32_t edge_rows, int32_t want_grad,
+                         float* const* d_grad_w, float* d_loss, float* d_pred, int32_t* d_status, int32_t B_total,
+                         int32_t accumulate, const ag_loss_spec* spec, float* d_loss_terms);
 
 /* ---- training batches on the device: the sampling, assembly and graph half of DynDataset.__getitem__
  * (src/dynamics/dataset/dataset.py:117-383).  Episode positions live in two flat fp32 buffers (object points, end-effector

@@ -20,6 +20,11 @@ That the fused step really does not wait is what tests/test_gpu_train_step.py::t
       is compared with) alternated in the same process with the same batch as K equal parts through accumulate ... apply, for
       every K given; and a mixed-size batch (half the graphs built with topk 10, half with topk 5) as one call with the common
       max_edges against two buckets with their own.  --parts 4 --no-mixed --only-parts under rocprofv3 gives the 4-part kernel table.
+  python tools/bench_train.py --losses mse:1,chamfer:0.5,hausdorff:0.25 --out FILE
+      the loss-list leg INSTEAD of the three variants, four legs alternated in the same process on the same batch: fused_default
+      (TrainStep(), the MSE step as it always was), fused_losses (TrainStep(losses=...): ag_train_step_losses), engine_default and
+      engine_losses (the autograd path with MSE alone and with the same list, its set terms being adaptigraph_amd.ChamferLoss /
+      HausdorffLoss).  --only-losses NAME runs one of them (for a kernel trace).
 """
 import argparse
 import json
@@ -200,6 +205,98 @@ def run_parts(a, dev, data, W):
             f.write(line + "\n")
 
 
+def parse_losses(text):
+    """'mse:1,chamfer:0.5' -> [("mse", 1.0), ("chamfer", 0.5)]; checked by LossSpec."""
+    out = [(t.split(":")[0].strip(), float(t.split(":")[1])) for t in text.split(",")]
+    ag.LossSpec(out)
+    return out
+
+
+def chain_loss_funcs(step, inp, n_future, loss_funcs):
+    """TR.chain_loss with train.py:100-102's loss = sum(weight * func(pred, gt))."""
+    state, action, n_p = inp["state"], inp["action"], inp["n_p"]
+    loss = 0
+    for fi in range(n_future):
+        gt = inp["state_future"][:, fi]
+        pred, _ = step(state, action)
+        p = pred[:, :gt.shape[1], :3].clone()
+        loss = loss + sum([w * func(p, gt) for func, w in loss_funcs])
+        if fi < n_future - 1:
+            nxt = inp["eef_future"][:, fi].clone().unsqueeze(1)
+            nxt[:, -1, :n_p] = pred[:, :n_p]
+            state = torch.cat([state[:, 1:], nxt], 1)
+            action = inp["action_future"][:, fi]
+    return loss
+
+
+def run_losses(a, dev, data, W):
+    losses = parse_losses(a.losses)
+    mods = {"mse": torch.nn.MSELoss(), "chamfer": ag.ChamferLoss(), "hausdorff": ag.HausdorffLoss()}
+
+    def new_model():
+        model = ag.DynamicsPredictor(CFG, {"material_index": {"rope": 0}, "rope": {"physics_params": [{"name": "s", "use": True}]}},
+                                     {"n_his": 4, "materials": ["rope"]}, dev)
+        model.load_state_dict({k: torch.from_numpy(v) for k, v in W.items()})
+        return model.to(dev)
+    batch = {k: data[k] for k in BATCH_KEYS + ("edges",)}
+    max_edges = int(data["ne"].max())
+
+    def fused(spec):
+        ts = ag.TrainStep(new_model(), lr=0.001, n_future=3, losses=spec)
+        return lambda: ts.step(batch, max_edges=max_edges)
+
+    def engine(funcs):
+        model = new_model().train()
+        opt = torch.optim.Adam(model.parameters(), lr=0.001)
+        g = {k: data[k] for k in ("attrs", "p_instance", "phys_physics_param", "edges")}
+
+        def it():
+            opt.zero_grad()
+            loss = chain_loss_funcs(lambda s, x: model(state=s, action=x, **g), data, 3, funcs)
+            loss.backward()
+            opt.step()
+            return loss
+        return it
+    legs = {"fused_default": fused(None), "fused_losses": fused(losses), "engine_default": engine([(mods["mse"], 1)]),
+            "engine_losses": engine([(mods[n], w) for n, w in losses])}
+    if a.only_losses:
+        legs = {a.only_losses: legs[a.only_losses]}
+    for fn in legs.values():
+        for _ in range(a.warmup):
+            fn()
+    torch.cuda.synchronize()
+    times, last = {k: [] for k in legs}, {}
+    for _ in range(a.rounds):
+        for k, fn in legs.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(a.iters):
+                loss = fn()
+            torch.cuda.synchronize()
+            times[k].append((time.perf_counter() - t0) * 1e3 / a.iters)
+            last[k] = float(loss.detach())
+    res = {"tool": "bench_train --losses", "device": torch.cuda.get_device_name(dev), "rounds": a.rounds, "iters_per_round": a.iters,
+           "losses": [[n, w] for n, w in losses],
+           "config": dict(B=int(data["attrs"].shape[0]), N=int(data["attrs"].shape[1]), n_p=data["n_p"], n_future=3, pstep=3,
+                          optimizer="Adam lr 1e-3", edges_mean=float(data["ne"].mean()), edges_max=int(data["ne"].max())),
+           "note": "every leg in one process, alternated round by round; ms per optimiser step, median over the rounds"}
+    for k, r in times.items():
+        res[k] = {"ms_per_iter_median": float(np.median(r)), "ms_per_iter_rounds": [round(x, 3) for x in r], "ms_min": min(r),
+                  "ms_max": max(r), "last_loss": last[k]}
+    med = lambda k: res[k]["ms_per_iter_median"]   # noqa: E731
+    if "fused_default" in res and "fused_losses" in res:
+        res["set_terms_add_ms_fused"] = med("fused_losses") - med("fused_default")
+    if "engine_default" in res and "engine_losses" in res:
+        res["set_terms_add_ms_engine"] = med("engine_losses") - med("engine_default")
+    if "fused_losses" in res and "engine_losses" in res:
+        res["engine_losses_over_fused_losses"] = med("engine_losses") / med("fused_losses")
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
 WAITS = {"ag_forward": 1, "ag_backward": 2, "ag_ctx_load_weights": 1, "ag_train_step": 0, "ag_adam_step": 0,
          "ag_ctx_load_weights_device": 0}
 CALLS = {k: 0 for k in WAITS}
@@ -261,12 +358,16 @@ def main():
     ap.add_argument("--parts", default=None, help="K[,K...]: the parts leg (see the module docstring)")
     ap.add_argument("--no-mixed", action="store_true", help="with --parts: leave the mixed-size batch out")
     ap.add_argument("--only-parts", action="store_true", help="with --parts: the K-part legs alone (for a kernel trace)")
+    ap.add_argument("--losses", default=None, help="term:weight[,term:weight...]: the loss-list leg (see the module docstring)")
+    ap.add_argument("--only-losses", choices=["fused_default", "fused_losses", "engine_default", "engine_losses"], default=None)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     data = make_batch(dev, B=a.batch)
     W = TR.make_weights(0)
     if a.parts:
         return run_parts(a, dev, data, W)
+    if a.losses:
+        return run_losses(a, dev, data, W)
     count_calls()
     makers = {"engine": engine_variant, "fused": fused_variant, "torch": torch_variant}
     variants = {k: mk(dev, data, W) for k, mk in makers.items() if a.only in (None, k)}

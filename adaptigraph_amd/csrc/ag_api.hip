@@ -27,6 +27,7 @@ const OptName kOptions[] = {
     {"device_decode", "AG_DEVICE_DECODE", &Options::device_decode, false, -1, 1},
     {"zigzag", "AG_ZIGZAG", &Options::zigzag, false, 0, 1},
     {"share_first", "AG_SHARE_FIRST", &Options::share_first, false, -1, 1},
+    {"zero_skip", "AG_ZERO_SKIP", &Options::zero_skip, false, 0, 1},
     {"share_prefix", "AG_SHARE_PREFIX", &Options::share_prefix, false, -1, 1},
     {"stream_min_rows", "AG_STREAM_MIN_ROWS", &Options::stream_min_rows, false, 0, 0x7fffffff},
     {"pipeline_fork", "AG_PIPELINE_FORK", &Options::pipeline_fork, false, 0, 1},
@@ -148,6 +149,7 @@ void carve_work(const ag_ctx* c, Slab& s, Work& w, int Bc, int N, int n_inst, in
     w.g.C = s.take<float>(((size_t)Bc * c_cap + 256) * NFP);   // + room for the two self-loop constant rows
     w.g.B = Bc; w.g.N = N; w.g.n_inst = n_inst; w.g.edge_cap = edge_cap; w.g.c_cap = c_cap; w.g.n_p = N_o;
     w.g.enc_persist = c->opt.enc_persist; w.g.stagger_us = c->opt.stagger_us; w.g.zigzag = c->opt.zigzag; w.g.diag = c->diag;
+    w.g.zero_skip = c->opt.zero_skip && c->w_finite;
     if (own_edges) {
         w.ell = s.take<int>(rows * (size_t)std::max(1, ell_stride));
         w.deg = s.take<int>(rows);
@@ -416,6 +418,8 @@ int ag_ctx_set_option(ag_ctx* c, const char* name, int32_t value) {
 
 int ag_ctx_get_option(ag_ctx* c, const char* name, int32_t* out) {
     if (!c || !name || !out) return AG_ERR_INVALID;
+    // read-only: what the next call's chains will do - the option, and the guard on the loaded weights
+    if (!strcmp(name, "zero_skip_active")) { *out = c->opt.zero_skip && c->w_finite ? 1 : 0; return AG_OK; }
     for (const OptName& n : kOptions)
         if (!strcmp(name, n.name)) { *out = c->opt.*(n.field); return AG_OK; }
     return fail(c, AG_ERR_INVALID, "unknown option '%s'", name);
@@ -470,6 +474,8 @@ int ag_ctx_load_weights(ag_ctx* c, const float* const* t, int32_t n) {
     std::vector<uint16_t> img(his4 ? (size_t)B3_PHASES * B3_PHASE_BYTES / 2 : 0, 0);
     std::vector<float> wl(his4 ? lat_weights_floats() : 0, 0.f);
     pack_weights_host(c->dims.rel_dim, t, blob.data(), his4 ? img.data() : nullptr, his4 ? wl.data() : nullptr);
+    // zero skip leaves out products with an activation that is exactly 0: the same bits only while no weight is inf or NaN
+    c->w_finite = std::all_of(blob.begin(), blob.end(), [](float v) { return std::isfinite(v); });
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipMemcpy(c->d_w, blob.data(), blob.size() * 4, hipMemcpyHostToDevice));
     if (his4) {

@@ -36,6 +36,7 @@ int load_weights_device(ag_ctx* c, hipStream_t st, const float* const* d_w) {
     HIPCHK(c, launch_pack_weights(c->dims.rel_dim, d_w, c->d_w, his4 ? reinterpret_cast<uint16_t*>(c->d_wb3) : nullptr,
                                   his4 ? c->d_wlat : nullptr, st));
     c->have_w = true;
+    c->w_finite = false;   // values the host never sees (an optimiser may have produced inf): zero skip stays off for them
     ++c->weights_version;
     return enqueue_self_rows(c, st);
 }

@@ -98,6 +98,10 @@ struct Options {
     int pipeline_fork = 0;    // [AG_PIPELINE_FORK]  1: a call forks onto in-library streams even while a call issued on ANOTHER caller
                               //                     stream is still running (0: such a call stays on its stream - the caller is
                               //                     already spreading independent calls over streams, adaptigraph_amd/planner.py)
+    int zero_skip = 1;        // [AG_ZERO_SKIP]      exact-fp32 chains: a k-step of a 160-wide layer whose two input features are exactly
+                              //                     zero in all 32 rows of a wavefront is branched over (ag_mlp.hip: mma_act).  Exact for
+                              //                     finite weights; a weight upload that holds a non-finite value turns it off for that
+                              //                     model (0 * inf must stay NaN), and so does a device-side upload, which no host code sees
     int share_first = -1;     // [AG_SHARE_FIRST]    first forward of a dynamics() call: the relation encoder runs ONCE over the
                               //                     object-object edges of the start state's tool-free graph and every candidate reads
                               //                     those C rows (-1: batches of 8 candidates or more, 0 never, 1 whenever possible)
@@ -247,6 +251,7 @@ struct GraphBufs {
     const int* send_pk; const float* C_share; int share_kb;
     int n_his;                             // 4 (0 = 4), or 5 on the forward path (feature rows then have pitch F15_PITCH)
     int enc_persist, stagger_us, zigzag;   // Options of the owning context
+    int zero_skip;                         // Options::zero_skip, and the loaded weights are known to be finite (ag_ctx::w_finite)
     void* diag;                            // diagnostic build (-DAG_DIAG, ag_diag.hip) only: the context's probe state, else null
 };
 constexpr int B3_PHASE_BYTES = 2 * 5 * 3 * 64 * 16;   // 30,720

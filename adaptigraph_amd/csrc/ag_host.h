@@ -85,6 +85,7 @@ struct ag_ctx {
     float* d_wlat = nullptr;     // weight image of the latency-mode chains (ag_lat.hip), n_his = 4 models only
     int precision = 0;           // 0: exact fp32 MFMA (default), 1: bf16x3 split on the bf16 matrix pipe
     bool have_w = false;
+    bool w_finite = false;       // the packed weights were seen on the host and are all finite: zero skip (Options::zero_skip) may run
     int chunk = 0;
     ag::Options opt;             // per-context switches: environment defaults read once at create, ag_ctx_set_option afterwards
     void* diag = nullptr;        // diagnostic build only: probe state of this context (ag_diag.hip)

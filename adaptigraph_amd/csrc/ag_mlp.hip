@@ -57,6 +57,22 @@ static_assert(32 * STG_TILE_PITCH <= STG_FLOATS, "tile staging fits the per-wave
 constexpr int CHAIN_LDS_FLOATS = 2 * BUF_FLOATS + (WG / 64) * STG_FLOATS;
 
 struct Act { f32x16 t[5]; };
+// Zero skip (mma_act) per chain, fixed at build time.  The propagate chains (k_node_prop) have it: -4.7 % / -6.7 % per launch on the
+// flagship batch.  The relation-encoder chain does not: 8 % of its k-steps are dead there, but its wavefronts run MFMA-bound from
+// quarter barrier to quarter barrier, a quarter costs what its slowest wavefront costs, and the mask, branches and waits cost
+// 6 % where nothing is dead (measured: +1.7 % per launch, +0.8 % per rollout).  k_node_enc is built like the relation-encoder chain
+// and is not on the flagship path (the class table goes through the latency-mode chain); unmeasured, so it stays as it was.
+// docs/EXPERIMENTS.md, "Zero skip in the fp32 chains".  -DAG_ZS_EDGE=1 / -DAG_ZS_ENC=1 / -DAG_ZS_NODE=0: experiment builds.
+#ifndef AG_ZS_EDGE
+#define AG_ZS_EDGE 0
+#endif
+#ifndef AG_ZS_ENC
+#define AG_ZS_ENC 0
+#endif
+#ifndef AG_ZS_NODE
+#define AG_ZS_NODE 1
+#endif
+constexpr bool ZS_EDGE = AG_ZS_EDGE != 0, ZS_ENC = AG_ZS_ENC != 0, ZS_NODE = AG_ZS_NODE != 0;
 
 // ------------------------------------------------------------------------------------------------ staging
 // global -> LDS DMA (global_load_lds, 16 B per lane): NFLOATS (a multiple of 256) in 1-KB pieces, each wave-instruction
@@ -85,23 +101,40 @@ __device__ __forceinline__ void dma_copy(float* lds_dst, const float* __restrict
 // chunks [Q0,Q1) of a layer whose LDS image starts at chunk Q0; input = previous accumulator tiles.
 // (Reading the fragments of chunk q+1 under the MFMAs of chunk q was measured twice - with two MFMA-issuing wavefronts per
 // SIMD, and in the fused propagate chains where the partner wavefront is gathering half of the time: no gain, +20 VGPRs.)
-template <int Q0, int Q1, int MB>
-__device__ __forceinline__ void mma_act(const float* wl, const Act& in, f32x16* acc, int lane) {
+//
+// Zero skip (Options::zero_skip): `lv` has one bit per k-step, wave-uniform, in scalar registers (live_of).  A k-step whose
+// two input features are exactly zero in all 32 rows of the wavefront adds 0*w + 0*w' to every accumulator - nothing, for
+// finite weights - so its MB MFMAs are branched over; a chunk of four such steps also leaves out its weight-fragment reads.
+// Only MFMAs and ds_reads sit under the branches: every DMA, barrier and store is executed by every wavefront as before.
+struct Live { unsigned m[3]; };                                   // bit s & 31 of m[s >> 5]: k-step s has a non-zero input
+template <int Q0, int Q1, int MB, bool SKIP>
+__device__ __forceinline__ void mma_act(const float* wl, const Act& in, f32x16* acc, int lane, const Live& lv) {
 #pragma unroll
     for (int q = Q0; q < Q1; ++q) {
-        f32x4 a[MB];
-#pragma unroll
-        for (int mb = 0; mb < MB; ++mb)
-            a[mb] = *reinterpret_cast<const f32x4*>(wl + ((q - Q0) * MB + mb) * 256 + lane * 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int s = 4 * q + e;
-            const int t = s < 64 ? s / 16 : 4;
-            const int r = s < 64 ? s % 16 : s - 64;
-            const float b = in.t[t][r];
+        const unsigned nib = SKIP ? (lv.m[(4 * q) >> 5] >> ((4 * q) & 31)) & 15u : 15u;   // a chunk never straddles a word
+        if (__builtin_expect(nib != 0u, 1)) {                         // live is the fall-through path: no taken branch when nothing is dead
+            f32x4 a[MB];
 #pragma unroll
             for (int mb = 0; mb < MB; ++mb)
-                acc[mb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mb][e], b, acc[mb], 0, 0, 0);
+                a[mb] = *reinterpret_cast<const f32x4*>(wl + ((q - Q0) * MB + mb) * 256 + lane * 4);
+            if (SKIP) {
+                // the fragments are awaited HERE, once, on every path: a read left in flight by a skipped step makes the
+                // compiler wait in the middle of the next chunk's reads, before the one that reuses its registers
+#pragma unroll
+                for (int mb = 0; mb < MB; ++mb) asm volatile("" : "+v"(a[mb]));
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int s = 4 * q + e;
+                const int t = s < 64 ? s / 16 : 4;
+                const int r = s < 64 ? s % 16 : s - 64;
+                const float b = in.t[t][r];
+                if (__builtin_expect((nib & (1u << e)) != 0u, 1)) {
+#pragma unroll
+                    for (int mb = 0; mb < MB; ++mb)
+                        acc[mb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mb][e], b, acc[mb], 0, 0, 0);
+                }
+            }
         }
         // one m-block: nothing else stops the scheduler from hoisting all 19 weight reads (76 VGPRs)
         if (MB == 1) __builtin_amdgcn_sched_barrier(0);
@@ -150,6 +183,24 @@ __device__ __forceinline__ void relu_one(Act& a, int lane) {   // ReLU, then for
         for (int r = 0; r < 16; ++r) a.t[t][r] = __builtin_fmaxf(a.t[t][r], 0.0f);
     a.t[4][10] = lane >= 32 ? 1.0f : a.t[4][10];
     materialize(a);
+}
+
+// Live mask of the 76 k-steps of `a` as the input of a 160-wide layer: step s (register (t, r), both lane halves = its two
+// features) is live iff any of the 64 lanes holds a non-zero.  NaN and inf count as non-zero.  Slot 150 is 1.0 after relu_one,
+// so its step (74) comes out live without being named here.  `on` == 0 (option off, or non-finite weights): every step live.
+__device__ __forceinline__ Live live_of(const Act& a, int on) {
+    Live lv = {{~0u, ~0u, ~0u}};
+    if (on) {
+        lv.m[0] = lv.m[1] = lv.m[2] = 0u;
+#pragma unroll
+        for (int s = 0; s < 4 * KCH; ++s) {
+            const int t = s < 64 ? s / 16 : 4;
+            const int r = s < 64 ? s % 16 : s - 64;
+            const bool any = __builtin_amdgcn_ballot_w64(a.t[t][r] != 0.0f) != 0;
+            lv.m[s >> 5] |= any ? 1u << (s & 31) : 0u;
+        }
+    }
+    return lv;
 }
 
 // row-major (pitch NFP) <-> accumulator layout.  Lane (j = lane&31, h = lane>>5) owns, of row j, the 16-byte
@@ -237,24 +288,25 @@ __device__ __forceinline__ void store_rows_t(const Act& a, float* __restrict__ b
 // Postcondition: the first NEXT floats of `next` (the following phase) are in buffer 0 and a barrier has passed.
 // PRE: the caller has already issued the DMA of quarter 1 into buffer 1 (it did so BEFORE a burst of row stores: waits
 // count vector-memory operations in issue order, so a DMA issued behind the stores could not be awaited without them).
-template <int NEXT, bool ZERO = true, bool PRE = false>
+// SKIP: consult `lv`, the live mask of `in` (zero skip, see mma_act); else every k-step is issued and `lv` is not read.
+template <int NEXT, bool ZERO = true, bool PRE = false, bool SKIP = false>
 __device__ __forceinline__ void layer160(float* lds, const float* __restrict__ w, const float* __restrict__ next,
-                                         const Act& in, Act& out, int tid, int lane) {
+                                         const Act& in, Act& out, int tid, int lane, const Live& lv = Live()) {
     float* b0 = lds;
     float* b1 = lds + BUF_FLOATS;
     if (ZERO) zero(out);                                     // else: accumulate on top of what `out` holds
     // every sweep runs with the NEXT quarter's DMA in flight into the other buffer (free since the last barrier)
     if (!PRE) dma_copy<Q_FLOATS>(b1, w + Q_FLOATS, tid);
-    mma_act<0, QCH, 5>(b0, in, out.t, lane);
+    mma_act<0, QCH, 5, SKIP>(b0, in, out.t, lane, lv);
     __syncthreads();
     dma_copy<Q_FLOATS>(b0, w + 2 * Q_FLOATS, tid);
-    mma_act<QCH, 2 * QCH, 5>(b1, in, out.t, lane);
+    mma_act<QCH, 2 * QCH, 5, SKIP>(b1, in, out.t, lane, lv);
     __syncthreads();
     dma_copy<Q3_FLOATS>(b1, w + 3 * Q_FLOATS, tid);
-    mma_act<2 * QCH, 3 * QCH, 5>(b0, in, out.t, lane);
+    mma_act<2 * QCH, 3 * QCH, 5, SKIP>(b0, in, out.t, lane, lv);
     __syncthreads();
     if (NEXT > 0) dma_copy<(NEXT > 0 ? NEXT : 256)>(b0, next, tid);
-    mma_act<3 * QCH, KCH, 5>(b1, in, out.t, lane);
+    mma_act<3 * QCH, KCH, 5, SKIP>(b1, in, out.t, lane, lv);
     if (NEXT > 0) __syncthreads();
 }
 
@@ -290,6 +342,7 @@ struct GDev {
     // non-zero upper bits takes its C row from the shared base table (row = receiver * share_kb + position)
     const float* C_share; unsigned share_kb;
     int f_pitch, cur_off;                     // feature-row pitch and offset of the current position in it (n_his 4: 12, 9)
+    int zero_skip;                            // Options::zero_skip and finite weights: the 160-wide layers branch over all-zero k-steps
 #ifdef AG_DIAG
     unsigned long long* dbg;   // diagnostic build (ag_diag.hip) only: stamps per workgroup, never read by kernels
 #endif
@@ -613,11 +666,11 @@ __global__ __launch_bounds__(WG, 2) void k_edge_enc(GDev g) {
     mma_feat<EDGE_L1_CHUNKS, (RD + 2) / 2>(lds + BUF_FLOATS, f, y.t, lane);     // RD inputs + bias: 9 (n_his 4) / 11 steps of 12
     __syncthreads();
     relu_one(y, lane);
-    layer160<Q_FLOATS>(lds, wts + WL::E_L2, wts + WL::E_L3, y, x, tid, lane);
+    layer160<Q_FLOATS, true, false, ZS_EDGE>(lds, wts + WL::E_L2, wts + WL::E_L3, y, x, tid, lane, live_of(y, g.zero_skip));
     relu_one(x, lane);
-    layer160<Q_FLOATS>(lds, wts + WL::E_L3, wts + WL::E_W1, x, y, tid, lane);
+    layer160<Q_FLOATS, true, false, ZS_EDGE>(lds, wts + WL::E_L3, wts + WL::E_W1, x, y, tid, lane, live_of(x, g.zero_skip));
     relu_one(y, lane);
-    layer160<0>(lds, wts + WL::E_W1, nullptr, y, x, tid, lane);
+    layer160<0, true, false, ZS_EDGE>(lds, wts + WL::E_W1, nullptr, y, x, tid, lane, live_of(y, g.zero_skip));
     store_rows_t(x, g.C, (int)((long)b * g.c_cap + el), valid, stg, lane);
 #ifdef AG_DIAG
     if (g.dbg && tid == 0) {
@@ -654,16 +707,17 @@ __global__ __launch_bounds__(WG, 2) void k_node_enc(GDev g) {
     mma_feat<NODE_L1_CHUNKS>(lds + BUF_FLOATS, f, y.t, lane);
     __syncthreads();
     relu_one(y, lane);
-    layer160<Q_FLOATS>(lds, g.w + WL::N_L2, g.w + WL::N_L3, y, x, tid, lane);
+    layer160<Q_FLOATS, true, false, ZS_ENC>(lds, g.w + WL::N_L2, g.w + WL::N_L3, y, x, tid, lane, live_of(y, g.zero_skip));
     relu_one(x, lane);
-    layer160<Q_FLOATS>(lds, g.w + WL::N_L3, g.w + WL::N_WA, x, y, tid, lane);
+    layer160<Q_FLOATS, true, false, ZS_ENC>(lds, g.w + WL::N_L3, g.w + WL::N_WA, x, y, tid, lane, live_of(x, g.zero_skip));
     relu_one(y, lane);                                       // y = p_enc (slot 150 = 1 for the bias of Wa)
+    const Live lv = live_of(y, g.zero_skip);                 // p_enc feeds Wa, W2 and W3
     store_rows_t(y, g.eff, (int)row, valid, stg, lane);
-    layer160<Q_FLOATS>(lds, g.w + WL::N_WA, g.w + WL::N_W2, y, x, tid, lane);
+    layer160<Q_FLOATS, true, false, ZS_ENC>(lds, g.w + WL::N_WA, g.w + WL::N_W2, y, x, tid, lane, lv);
     store_rows_t(x, g.P, (int)row, valid, stg, lane);
-    layer160<Q_FLOATS>(lds, g.w + WL::N_W2, g.w + WL::N_W3, y, x, tid, lane);
+    layer160<Q_FLOATS, true, false, ZS_ENC>(lds, g.w + WL::N_W2, g.w + WL::N_W3, y, x, tid, lane, lv);
     store_rows_t(x, g.U, (int)row, valid, stg, lane);
-    layer160<0>(lds, g.w + WL::N_W3, nullptr, y, x, tid, lane);
+    layer160<0, true, false, ZS_ENC>(lds, g.w + WL::N_W3, nullptr, y, x, tid, lane, lv);
     store_rows_t(x, g.V, (int)row, valid, stg, lane);
 }
 
@@ -712,8 +766,11 @@ __global__ __launch_bounds__(WG, 2) void k_node_prop(GDev g) {
     materialize(y);
     add_rows_part<2, 5>(y, ceff ? g.c_eff : g.eff, (ceff ? crow : rowc) + pin_after(y), lane);
     __syncthreads();                                         // Wb quarter 0 is in buffer 0
-    layer160<Q_FLOATS, false>(lds, g.w + WL::P_WB, g.w + (LAST ? WL::P_P0 : WL::N_W2), x, y, tid, lane);
+    // (x = agg: sums of ReLU outputs.  The seeded accumulator is the one place where a skipped step can show: in the sign of an
+    // exact zero, -0 + 0*w being +0.)
+    layer160<Q_FLOATS, false, false, ZS_NODE>(lds, g.w + WL::P_WB, g.w + (LAST ? WL::P_P0 : WL::N_W2), x, y, tid, lane, live_of(x, g.zero_skip));
     relu_one(y, lane);                                       // y = new particle effect (slot 150 forced to 1)
+    const Live lv = live_of(y, g.zero_skip);                 // the new effect feeds W2 and W3, or P0
 #ifdef AG_DIAG
     if (g.dbg && tid == 0) g.dbg[blockIdx.x * 4 + 2] = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -722,10 +779,10 @@ __global__ __launch_bounds__(WG, 2) void k_node_prop(GDev g) {
         // barrier leaves the stores in flight: they then have two quarter sweeps to drain instead of one
         dma_copy<Q_FLOATS>(lds + BUF_FLOATS, g.w + WL::N_W2 + Q_FLOATS, tid);
         store_rows_t(y, g.eff, (int)row, valid, stg, lane);
-        layer160<Q_FLOATS, true, true>(lds, g.w + WL::N_W2, g.w + WL::N_W3, y, x, tid, lane);
+        layer160<Q_FLOATS, true, true, ZS_NODE>(lds, g.w + WL::N_W2, g.w + WL::N_W3, y, x, tid, lane, lv);
         dma_copy<Q_FLOATS>(lds + BUF_FLOATS, g.w + WL::N_W3 + Q_FLOATS, tid);
         store_rows_t(x, g.U, (int)row, valid, stg, lane);
-        layer160<0, true, true>(lds, g.w + WL::N_W3, nullptr, y, x, tid, lane);
+        layer160<0, true, true, ZS_NODE>(lds, g.w + WL::N_W3, nullptr, y, x, tid, lane, lv);
         store_rows_t(x, g.V, (int)row, valid, stg, lane);
 #ifdef AG_DIAG
         if (g.dbg && tid == 0) {
@@ -734,14 +791,14 @@ __global__ __launch_bounds__(WG, 2) void k_node_prop(GDev g) {
         }
 #endif
     } else {
-        layer160<Q_FLOATS>(lds, g.w + WL::P_P0, g.w + WL::P_P1, y, x, tid, lane);
+        layer160<Q_FLOATS, true, false, ZS_NODE>(lds, g.w + WL::P_P0, g.w + WL::P_P1, y, x, tid, lane, lv);
         relu_one(x, lane);
-        layer160<OUT3_FLOATS>(lds, g.w + WL::P_P1, g.w + WL::P_P2, x, y, tid, lane);
+        layer160<OUT3_FLOATS, true, false, ZS_NODE>(lds, g.w + WL::P_P1, g.w + WL::P_P2, x, y, tid, lane, live_of(x, g.zero_skip));
         relu_one(y, lane);
         f32x16 m[1];
 #pragma unroll
         for (int r = 0; r < 16; ++r) m[0][r] = 0.0f;
-        mma_act<0, KCH, 1>(lds, y, m, lane);
+        mma_act<0, KCH, 1, false>(lds, y, m, lane, Live());
         // motion xyz = output features 0,1,2 = registers 0,1,2 of lanes 0..31
         const int b = pb, i = pi;
         if (valid && lane < 32 && i < g.n_p) {
@@ -1102,6 +1159,7 @@ static GDev to_dev(const float* w, const GraphBufs& g) {
     d.rowlist = g.rowlist; d.n_rows = g.n_rows;
     d.C_share = nullptr; d.share_kb = 0;
     d.f_pitch = feat_pitch(g.n_his); d.cur_off = g.n_his == 5 ? 12 : 9;
+    d.zero_skip = g.zero_skip;
     // Options::stagger_us: offset between the two workgroups of a CU in the fused propagate chains.  Off by default: it removes
     // the "both computing / both gathering" states (probe: 8 % -> 0 % of CU time) but the kernel time moves by <= 1 %
     // either way (two streams: 169 vs 171 ms per rollout with 30 us; four streams: 484.9 vs 482.9 ms per rollout without)

@@ -169,6 +169,12 @@ int ag_ctx_set_chunk(ag_ctx* ctx, int32_t candidates_per_chunk);
  *   "pipeline_fork"  [AG_PIPELINE_FORK]   0 (default): a call that starts while a call issued on ANOTHER caller stream is still running
  *                                         does not fork onto in-library streams (the caller is already spreading independent calls
  *                                         over streams); 1: it forks as usual
+ *   "zero_skip"      [AG_ZERO_SKIP]       1 (default): the exact-fp32 chains branch over a k-step of a 160-wide layer whose two input
+ *                                         features are exactly zero in all 32 rows of a wavefront (ReLU outputs that are off over a
+ *                                         local patch).  Same results for finite weights; ag_ctx_load_weights turns it off for a
+ *                                         model that holds an inf or NaN weight, ag_ctx_load_weights_device / ag_adam_step always
+ *                                         (no host code sees those values).  ag_ctx_get_option "zero_skip_active" (read-only) = 1
+ *                                         when the option is on and the guard has not turned it off
  * Unknown names and values outside an option's range return AG_ERR_INVALID (ranges: stream_min_rows 0..INT32_MAX, pipeline_fork 0..1, streams 0..4, chunk 0..2^20, latency -1..1,
  * the 0/1 switches 0..1, edge_wgs 1..65536, edge_block_min -1..INT32_MAX, enc_persist 0..2^20, stagger_us 0..1000,
  * device_decode -1..1, share_first -1..1, share_prefix -1..1). */

@@ -1,0 +1,161 @@
+#!/usr/bin/env python
+"""How many k-steps of the fp32 chains are all zero?  A CPU census for Options::zero_skip (csrc/ag_mlp.hip: mma_act).
+
+numpy only, no GPU.  Inputs are bench.py's own: random_weights(0), the jittered 45 x 45 cloth, the first draw of the 1024
+actions.  A few candidates of that batch are stepped by the oracle for the first forwards of look-ahead step 0; for every
+forward the hidden activations of the model are recomputed with the oracle's feature assembly (model_forward_single) and
+laid out as the engine sees them:
+  * relation-encoder chain (k_edge_enc): the candidate's edges in the reference's order (receiver-major), self-loops left
+    out (they take a constant C row), 32 consecutive ones per wavefront;
+  * propagate chains (k_node_prop): dense rows candidate * N + particle, 32 consecutive ones per wavefront (a wavefront that
+    straddles two candidates is counted with the rows of the simulated candidate only);
+  * k-step s of a 160-wide layer = features (lo, lo + 4), lo = 32 t + (r & 3) + 8 (r >> 2), (t, r) = (s / 16, s % 16) for
+    s < 64 and (4, s - 64) above: the packed K order.  Slot 150 is the bias slot (always 1.0), 151 is padding (always 0).
+Printed per layer: the share of (wavefront, k-step) pairs whose two features are zero in all rows of the wavefront - the
+MFMAs zero_skip leaves out - and the share of (wavefront, 4-step chunk) pairs that are dead as a whole (their weight-fragment
+reads go too).  Not modelled: the shared first forward (its object-object edges are encoded once per call, not per candidate).
+
+  python tools/zero_skip_census.py [--forwards 3] [--candidates 0,341,682,1023] [--json out.json]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+F32 = np.float32
+NSTEP = 76
+
+
+def step_features():
+    lo = []
+    for s in range(NSTEP):
+        t, r = (s // 16, s % 16) if s < 64 else (4, s - 64)
+        lo.append(32 * t + (r & 3) + 8 * (r >> 2))
+    return np.asarray(lo)
+
+
+LO = step_features()
+
+
+def dead_share(act, first_row=0):
+    """act (rows, 150) ReLU outputs in engine row order -> (dead k-steps, dead chunks, wavefront x k-step pairs, wavefront x chunk pairs)"""
+    rows = act.shape[0]
+    a = np.zeros((rows, 160), bool)
+    a[:, :150] = act != 0
+    a[:, 150] = True                                          # bias slot
+    step_live_row = a[:, LO] | a[:, LO + 4]                   # (rows, 76)
+    wave = (first_row + np.arange(rows)) // 32
+    wave -= wave[0]
+    n_wave = int(wave[-1]) + 1
+    live = np.zeros((n_wave, NSTEP), bool)
+    np.logical_or.at(live, wave, step_live_row)
+    chunk_live = live.reshape(n_wave, NSTEP // 4, 4).any(2)
+    return int((~live).sum()), int((~chunk_live).sum()), live.size, chunk_live.size
+
+
+def layers_of_forward(O, W, hist, attrs, recv, send, group, action, phys, pstep):
+    """the hidden activations of one forward, as model_forward_single computes them; yields (chain, layer, rows x 150)"""
+    n_his, N, _ = hist.shape
+    res = hist[1:] - hist[:-1]
+    snt = np.ascontiguousarray(np.concatenate([res, hist[-1:]], 0).transpose(1, 0, 2)).reshape(N, n_his * 3)
+    p_inputs = np.concatenate([attrs, phys[:, None], action], 1).astype(F32)
+    gdiff = np.abs(group[recv] - group[send]).sum(1, keepdims=True)
+    rel_inputs = np.concatenate([attrs[recv], attrs[send], gdiff, snt[recv] - snt[send]], 1).astype(F32)
+    ns = recv != send                                         # the relation encoder's work list
+
+    def enc(x, pre):
+        hs = []
+        for i in (0, 2, 4):
+            x = O._relu(O._linear(x, W[f"{pre}.model.{i}.weight"], W[f"{pre}.model.{i}.bias"]))
+            hs.append(x)
+        return hs
+    r1, r2, r_enc = enc(rel_inputs, "relation_encoder")
+    yield "edge", "L2", r1[ns]
+    yield "edge", "L3", r2[ns]
+    yield "edge", "W1", r_enc[ns]
+    p_enc = enc(p_inputs, "particle_encoder")[2]
+    eff = p_enc
+    Wrp, brp = W["relation_propagator.linear.weight"], W["relation_propagator.linear.bias"]
+    Wpp, bpp = W["particle_propagator.linear.weight"], W["particle_propagator.linear.bias"]
+    for ps in range(pstep):
+        eff_rel = O._relu(O._linear(np.concatenate([r_enc, eff[recv], eff[send]], 1), Wrp, brp))
+        agg = np.zeros((N, eff_rel.shape[1]), F32)
+        np.add.at(agg, recv, eff_rel)
+        eff = O._relu(O._linear(np.concatenate([p_enc, agg], 1), Wpp, bpp) + eff)
+        last = ps + 1 == pstep
+        yield "node_last" if last else "node", "Wb", agg
+        yield ("node_last", "P0", eff) if last else ("node", "W2,W3", eff)
+    h = O._relu(O._linear(eff, W["non_rigid_predictor.linear_0.weight"], W["non_rigid_predictor.linear_0.bias"]))
+    yield "node_last", "P1", h
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--forwards", type=int, default=3)
+    ap.add_argument("--candidates", default="0,341,682,1023")
+    ap.add_argument("--json", default=None)
+    args = ap.parse_args()
+    import bench
+    from oracle import adaptigraph_oracle as O
+
+    rng = np.random.default_rng(0)
+    cloud = bench.cloth_cloud(45, rng)
+    N_o = cloud.shape[0]
+    task = bench.make_task(max_nR=int(1.2 * 6 * (N_o + 1)) + 64)
+    W = bench.random_weights(0)
+    actions = bench.make_actions(1024, 2, 10, cloud, rng)
+    picks = [int(c) for c in args.candidates.split(",")]
+    a = actions[picks, :1].copy()
+    a[..., 3] = args.forwards + 0.5                           # the first forwards of look-ahead step 0 are the same ones
+    trace = []
+    O.dynamics(W, 3, cloud, a, task, trace=trace)
+    dec, _ = O.decode_action(a, task["push_length"])
+    _, delta = O.tool_keypoints(dec, a[..., 2], task)
+    N = N_o + 1
+    attrs = np.zeros((N, 2), F32); attrs[:N_o, 0] = 1; attrs[N_o:, 1] = 1
+    group = np.zeros((N, 1), F32); group[:N_o] = 1
+    phys = np.zeros(N, F32); phys[:N_o] = 0.5
+    tot = {}
+    per_forward = []
+    for ci, (cand, recs) in enumerate(zip(picks, trace)):
+        action = np.zeros((N, 3), F32); action[N_o:] = delta[ci, 0]
+        states = [recs[0]["state_last"]] * 3
+        for k, rec in enumerate(recs):
+            states.append(rec["state_last"])
+            hist = np.stack(states[-4:], 0).astype(F32)
+            n_ns = int((rec["recv"] != rec["send"]).sum())
+            n_tool = int(((rec["recv"] != rec["send"]) & ((rec["recv"] >= N_o) | (rec["send"] >= N_o))).sum())
+            row = {"candidate": cand, "forward": k + 1, "edges": n_ns, "tool_edges": n_tool}
+            for chain, layer, act in layers_of_forward(O, W, hist, attrs, rec["recv"], rec["send"], group, action, phys, 3):
+                d = dead_share(act, 0 if chain == "edge" else cand * N)
+                key = (chain, layer)
+                tot[key] = tuple(x + y for x, y in zip(tot.get(key, (0, 0, 0, 0)), d))
+                row[f"{chain}.{layer}"] = round(d[0] / d[2], 4)
+            per_forward.append(row)
+    print(f"zero-skip census: bench batch, candidates {picks}, forwards 1..{args.forwards} of look-ahead step 0")
+    print(f"{'chain':10s} {'layer':6s} {'dead k-steps':>13s} {'dead chunks':>12s}   (wavefront x k-step pairs)")
+    out = {"candidates": picks, "forwards": args.forwards, "layers": [], "per_forward": per_forward}
+    chains = {}
+    for (chain, layer), (ds, dc, ns_, nc) in tot.items():
+        print(f"{chain:10s} {layer:6s} {100 * ds / ns_:12.2f}% {100 * dc / nc:11.2f}%   ({ns_})")
+        out["layers"].append({"chain": chain, "layer": layer, "dead_steps": ds / ns_, "dead_chunks": dc / nc, "pairs": ns_})
+        c = chains.setdefault(chain, [0, 0])
+        w = 2 if layer == "W2,W3" else 1                      # one mask, two layers
+        c[0] += w * ds; c[1] += w * ns_
+    for chain, (ds, ns_) in chains.items():
+        print(f"{chain:10s} all    {100 * ds / ns_:12.2f}%")
+        out[f"{chain}_dead_steps"] = ds / ns_
+    for row in per_forward:
+        print(json.dumps(row))
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(out, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()

@@ -39,7 +39,8 @@ EXPORTS = ["ag_abi_version", "ag_ctx_create", "ag_ctx_destroy", "ag_last_error",
 AG_LOSS_MSE, AG_LOSS_CHAMFER, AG_LOSS_HAUSDORFF = 0, 1, 2
 
 OPTIONS = ["streams", "chunk", "latency", "ragged", "ell_graph", "self_dedupe", "repeat_sort", "edge_wgs", "edge_block_min",
-           "enc_persist", "stagger_us", "device_decode", "zigzag", "share_first", "share_prefix", "stream_min_rows", "pipeline_fork", "zero_skip"]
+           "enc_persist", "stagger_us", "device_decode", "zigzag", "share_first", "share_prefix", "stream_min_rows", "pipeline_fork", "zero_skip",
+           "edge_order", "ell_lds_words"]
 
 
 class AgDims(C.Structure):

@@ -31,6 +31,8 @@ const OptName kOptions[] = {
     {"share_prefix", "AG_SHARE_PREFIX", &Options::share_prefix, false, -1, 1},
     {"stream_min_rows", "AG_STREAM_MIN_ROWS", &Options::stream_min_rows, false, 0, 0x7fffffff},
     {"pipeline_fork", "AG_PIPELINE_FORK", &Options::pipeline_fork, false, 0, 1},
+    {"edge_order", "AG_EDGE_ORDER", &Options::edge_order, false, 0, 1},
+    {"ell_lds_words", "AG_ELL_LDS_WORDS", &Options::ell_lds_words, false, 0, 16384},
 };
 void options_from_env(Options& o) {   // values from the environment are clamped into the option's range
     for (const OptName& n : kOptions)
@@ -161,6 +163,7 @@ void carve_work(const ag_ctx* c, Slab& s, Work& w, int Bc, int N, int n_inst, in
         w.n_edges = s.take<int>(Bc);
         w.ns_edge = s.take<int>((size_t)Bc * edge_cap);
         w.n_ns = s.take<int>(Bc);
+        w.n_oo = s.take<int>(Bc);
         w.g.recv = w.recv; w.g.send = w.send; w.g.row_ptr = w.row_ptr; w.g.n_edges = w.n_edges;
     }
     if (roll) {

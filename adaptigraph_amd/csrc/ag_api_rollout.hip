@@ -380,6 +380,7 @@ int workspace_graph(RollCall& r, Work& w, int nb, hipStream_t s, GraphBufs& g) {
     g.wb3 = c->precision == 1 ? c->d_wb3 : nullptr;
     if (r.dedupe) {
         g.c_self = c->d_cself; g.ns_edge = w.ns_edge; g.n_ns = w.n_ns;
+        g.n_oo = r.ell_full && c->opt.edge_order ? w.n_oo : nullptr;
         g.self_row = (long)r.Ba * r.edge_cap;     // behind the last candidate's C rows of this workspace
         HIPCHK(c, hipMemcpyAsync(w.g.C + (size_t)g.self_row * NFP, c->d_cself, 2 * NFP * 4, hipMemcpyDeviceToDevice, s));
     }
@@ -401,6 +402,7 @@ EdgeArgs workspace_edge_args(const RollCall& r, const Work& w, int nb) {
     if (r.ell_full) {
         ea.ell_full = 1; ea.ell = w.send; ea.ell_stride = r.k + p->M; ea.ell_bstride = r.edge_cap;
         ea.ns_edge = w.ns_edge; ea.n_ns = w.n_ns;
+        ea.n_oo = r.c->opt.edge_order ? w.n_oo : nullptr; ea.lds_words = r.c->opt.ell_lds_words;
     }
     return ea;
 }

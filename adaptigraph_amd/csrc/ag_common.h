@@ -102,6 +102,13 @@ struct Options {
                               //                     zero in all 32 rows of a wavefront is branched over (ag_mlp.hip: mma_act).  Exact for
                               //                     finite weights; a weight upload that holds a non-finite value turns it off for that
                               //                     model (0 * inf must stay NaN), and so does a device-side upload, which no host code sees
+    int edge_order = 1;       // [AG_EDGE_ORDER]     order of the relation encoder's work list (k_ell_index): 0 = slot order (receiver-major),
+                              //                     1 = class-major - object-object slots by the signs and the dominant axis of
+                              //                     pos_r - pos_s (24 classes), then every slot with a tool at either end, slot order inside
+                              //                     a class.  The wavefronts of k_edge_enc then hold like edges and more of their k-steps are
+                              //                     all zero (zero_skip).  A C row does not depend on the lane that computes it: same bits
+    int ell_lds_words = 0;    // [AG_ELL_LDS_WORDS]  debug: LDS budget of k_ell_index's class bitmaps in 64-bit words (0 = the built-in
+                              //                     16384); below 25 bitmaps the classes fall back to (object-object, tool), then to one list
     int share_first = -1;     // [AG_SHARE_FIRST]    first forward of a dynamics() call: the relation encoder runs ONCE over the
                               //                     object-object edges of the start state's tool-free graph and every candidate reads
                               //                     those C rows (-1: batches of 8 candidates or more, 0 never, 1 whenever possible)
@@ -136,6 +143,9 @@ struct EdgeArgs {
     // the non-self-loop slot list (ns_edge, n_ns), n_edges, and applies the max_nR rule.
     int ell_full; int ell_stride; long ell_bstride;   // 0 / unset: ell_stride = min(topk,N), ell_bstride = N*ell_stride
     int* ns_edge; int* n_ns;
+    // Options::edge_order 1: ns_edge is written class-major (see there) and n_oo[b] = entries in front of the tool class (0 when the
+    // classes did not fit the LDS budget `lds_words` and the list stayed in slot order).  n_oo null: slot order, nothing written.
+    int* n_oo; int lds_words;
     int block_min_rows;         // Options::edge_block_min (-1: built-in threshold)
     const int* live;            // null, or device int: candidates [*live, B) of this launch have no forward left (device-planned
                                 // rollout, RollPlan): their workgroups exit and their graphs are presented as empty
@@ -234,6 +244,7 @@ struct GraphBufs {
     const float* c_self;                   // (2, NFP) or null
     long self_row;                         // row of C where c_self[0..1] were copied (k_mp reads them from there)
     const int* ns_edge; const int* n_ns;   // (B,edge_cap), (B,) or null
+    const int* n_oo;                       // (B,) or null: class-major list (Options::edge_order), entries [n_oo[b], n_ns[b]) are tool edges
     const float* wb3;                      // bf16x3 weight image: non-null selects the bf16x3 chains (ag_mlp.hip)
     const int* n_guard;                    // ag_forward: guarded per-candidate edge counts (k_edge_guard), else null
     // ---- ragged batches (masked rollouts, forward_dynamics.py:286-309: every candidate has its own number of valid

@@ -51,6 +51,7 @@ struct EdgeDev {
     int* ell;                            // (B, N, k) kept non-merged senders per row (top-k active only)
     int ell_full, ell_stride; long ell_bstride;   // see EdgeArgs
     int* ns_edge; int* n_ns;
+    int* n_oo; int n_cls;                // k_ell_index<true>: bitmaps (25, or 2), entries in front of the tool class; see EdgeArgs
     int* deg; int* slice_tot; int* cta_flag;
     int* recv; int* send; int* row_ptr; int* n_edges; int* overflow; int max_nR; int zero_on_overflow;
     int block_min_rows;                  // slices with at least this many rows take the 64-rows-per-wavefront path
@@ -724,6 +725,23 @@ __global__ __launch_bounds__(EW) void k_edge_emit(EdgeDev a) {
 // pass 2 gives every thread a contiguous run of those words: popcount, one block scan, and the set bits leave in slot order.
 // Same outputs bit for bit (recv per slot, ns list in slot order, pk, n_ns, n_edges, the share counters).
 constexpr int ELL_BITMAP_MAX_WORDS64 = 16384;              // 128 KB of dynamic LDS: 1,048,576 slots (N = 4096 rows of up to 256 slots; the builder's limit is topk <= 128, M <= 8)
+// Class-major list (CLS, Options::edge_order): the same scheme with n_cls bitmaps, one per class.  Pass 1 ballots a lane's slot into
+// the bitmap of its class; pass 2 scans the n_cls * nw words as one run - class 0's words, then class 1's, ... - so the list leaves
+// class by class, in slot order inside each.  No atomics, no floating-point ordering: a pure function of graph and positions.
+// The class of slot (receiver i, sender j): the LAST class if either end is a tool particle; else, of d = pos_i - pos_j at the
+// frame the builder read, (d.x < 0, d.y < 0, d.z < 0) x argmax(|d.x|, |d.y|, |d.z|) (ties to the lower axis; a NaN compares
+// false): 24 + 1 classes.  n_cls == 2 (the 25 bitmaps did not fit): object-object, tool.  The key steers only which lanes of
+// k_edge_enc share a wavefront - a C row is stored by slot and no result depends on it (tools/zero_skip_census.py restates it).
+constexpr int ELL_CLASSES = 25;
+__device__ __forceinline__ int edge_class(const float* __restrict__ p, int i, int j) {
+    const float dx = __fsub_rn(p[3 * i + 0], p[3 * j + 0]), dy = __fsub_rn(p[3 * i + 1], p[3 * j + 1]), dz = __fsub_rn(p[3 * i + 2], p[3 * j + 2]);
+    int ax = 0;
+    float m = fabsf(dx);
+    if (fabsf(dy) > m) { ax = 1; m = fabsf(dy); }
+    if (fabsf(dz) > m) ax = 2;
+    return ((dx < 0.0f ? 1 : 0) | (dy < 0.0f ? 2 : 0) | (dz < 0.0f ? 4 : 0)) * 3 + ax;
+}
+template <bool CLS>
 __global__ __launch_bounds__(EW) void k_ell_index(EdgeDev a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned long long* bits = reinterpret_cast<unsigned long long*>(smem);
@@ -731,7 +749,7 @@ __global__ __launch_bounds__(EW) void k_ell_index(EdgeDev a) {
     __shared__ int n_shared;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (a.live && b >= *a.live) {                           // no forward left: nothing for the relation encoder to do
-        if (tid == 0) { a.n_ns[b] = 0; a.n_edges[b] = 0; }
+        if (tid == 0) { a.n_ns[b] = 0; a.n_edges[b] = 0; if (a.n_oo) a.n_oo[b] = 0; }
         return;
     }
     if (tid == 0) n_shared = 0;
@@ -764,6 +782,9 @@ __global__ __launch_bounds__(EW) void k_ell_index(EdgeDev a) {
     const int stride = a.ell_stride;
     const int nslots = a.N * stride;
     const int nw = (nslots + 63) >> 6;                      // 64-slot words
+    const int K = CLS ? a.n_cls : 1;
+    const float* cpos = a.pos + (long)b * a.pos_bstride;
+    const uint8_t* ctool = a.tool + (long)b * a.N;
     // ---- pass 1: one slot per lane
     int shared = 0;
     constexpr int UN = 8;                                   // words per wavefront and trip: the loads of all eight are issued together
@@ -798,15 +819,27 @@ __global__ __launch_bounds__(EW) void k_ell_index(EdgeDev a) {
             pk[e] = v;
         }
         if (valid) recv[e] = i;
+        if (CLS) {
+            int cls = 0;
+            if (own) cls = (ctool[i] | ctool[j]) ? K - 1 : (K == 2 ? 0 : edge_class(cpos, i, j));
+            unsigned long long keep = 0;
+            for (int k = 0; k < K; ++k) {
+                const unsigned long long bal = __ballot(own && cls == k);
+                if (lane == k) keep = bal;
+            }
+            if (lane < K) bits[lane * nw + (e0 >> 6)] = keep;
+        } else {
         const unsigned long long bal = __ballot(own);
         if (lane == 0) bits[e0 >> 6] = bal;
+        }
       }
     }
     if (hide) for (int i = tid; i < a.N; i += EW) deg[i] = 0;
     __syncthreads();
     // ---- pass 2: contiguous words per thread, block scan of the popcounts, set bits out in slot order
-    const int per = (nw + EW - 1) / EW;
-    const int w0 = min(nw, tid * per), w1 = min(nw, w0 + per);
+    const int nwt = K * nw;                                 // the class bitmaps as one run of words
+    const int per = (nwt + EW - 1) / EW;
+    const int w0 = min(nwt, tid * per), w1 = min(nwt, w0 + per);
     int mine = 0;
     for (int w = w0; w < w1; ++w) mine += __popcll(bits[w]);
     int incl = mine;
@@ -821,12 +854,25 @@ __global__ __launch_bounds__(EW) void k_ell_index(EdgeDev a) {
 #pragma unroll
     for (int w = 0; w < EWAVES; ++w) { const int v = wave_tot[w]; before += w < wave ? v : 0; all += v; }
     int pos = before + incl - mine;
+    if (CLS) {
+        const int wt = (K - 1) * nw;                        // first word of the tool class
+        for (int w = w0; w < w1; ++w) {
+            if (w == wt) a.n_oo[b] = pos;                   // (exactly one thread's run holds word wt: nw > 0)
+            const int ws = w % nw;
+            unsigned long long m = bits[w];
+            while (m) {
+                ns[pos++] = (ws << 6) + __ffsll((long long)m) - 1;
+                m &= m - 1;
+            }
+        }
+    } else {
     for (int w = w0; w < w1; ++w) {
         unsigned long long m = bits[w];
         while (m) {
             ns[pos++] = (w << 6) + __ffsll((long long)m) - 1;
             m &= m - 1;
         }
+    }
     }
     if (pk && a.share_stats) {
 #pragma unroll
@@ -836,6 +882,7 @@ __global__ __launch_bounds__(EW) void k_ell_index(EdgeDev a) {
     }
     if (tid == EW - 1) {
         a.n_ns[b] = all;
+        if (!CLS && a.n_oo) a.n_oo[b] = 0;                  // slot order: no tool segment, every tile of k_edge_enc carries a full mask
         a.n_edges[b] = hide ? 0 : total;
         if (a.overflow && total > a.max_nR) atomicMax(a.overflow, total);
         if (pk && a.share_stats) {                           // integer counters: order-free
@@ -855,7 +902,7 @@ hipError_t launch_edge_build(const EdgeArgs& h, hipStream_t st, void (*mark)(voi
     a.ell_full = h.ell_full && a.topk_active;
     a.ell_stride = a.ell_full ? h.ell_stride : a.k;
     a.ell_bstride = a.ell_full ? h.ell_bstride : (long)h.N * a.k;
-    a.ns_edge = h.ns_edge; a.n_ns = h.n_ns;
+    a.ns_edge = h.ns_edge; a.n_ns = h.n_ns; a.n_oo = h.n_oo; a.n_cls = 1;
     a.recv = h.recv; a.send = h.send; a.row_ptr = h.row_ptr; a.n_edges = h.n_edges; a.overflow = h.overflow;
     a.max_nR = h.max_nR; a.zero_on_overflow = h.zero_on_overflow; a.live = h.live;
     a.send_pk = a.ell_full ? h.send_pk : nullptr; a.base_send = h.base_send; a.base_deg = h.base_deg; a.base_stride = h.base_stride;
@@ -874,7 +921,10 @@ hipError_t launch_edge_build(const EdgeArgs& h, hipStream_t st, void (*mark)(voi
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_edge_emit), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 160 * 1024 - 256);
         if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ell_index), hipFuncAttributeMaxDynamicSharedMemorySize,
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ell_index<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                160 * 1024 - 256);
+        if (e != hipSuccess) return e;
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ell_index<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 160 * 1024 - 256);
         if (e != hipSuccess) return e;
         if (dev_id < 64) attr_devices |= 1ull << dev_id;
@@ -886,7 +936,11 @@ hipError_t launch_edge_build(const EdgeArgs& h, hipStream_t st, void (*mark)(voi
     if (a.ell_full) {
         const long nw = ((long)h.N * a.ell_stride + 63) >> 6;
         if (nw > ELL_BITMAP_MAX_WORDS64) return hipErrorInvalidValue;     // (N <= 4096 and topk + M <= 112: never on this path)
-        hipLaunchKernelGGL(k_ell_index, dim3(h.B), dim3(EW), (size_t)nw * 8, st, a);
+        // class bitmaps inside the same 128 KB (or the debug budget): 25, else (object-object, tool), else the one list of slot order
+        const long budget = h.lds_words > 0 && h.lds_words < ELL_BITMAP_MAX_WORDS64 ? h.lds_words : ELL_BITMAP_MAX_WORDS64;
+        a.n_cls = !a.n_oo ? 1 : ELL_CLASSES * nw <= budget ? ELL_CLASSES : 2 * nw <= budget ? 2 : 1;
+        if (a.n_cls > 1) hipLaunchKernelGGL(k_ell_index<true>, dim3(h.B), dim3(EW), (size_t)a.n_cls * nw * 8, st, a);
+        else hipLaunchKernelGGL(k_ell_index<false>, dim3(h.B), dim3(EW), (size_t)nw * 8, st, a);
     }
     else hipLaunchKernelGGL(k_edge_emit, dim3(h.B * h.slices), dim3(EW), lds, st, a);
     if (mark) mark(mark_ctx, FAM_EDGE_EMIT, 1);

@@ -187,7 +187,7 @@ struct Work {
     RollBufs r{};
     int* ell; int* deg; int* slice_tot; int* cta_flag;
     int* recv; int* send; int* row_ptr; int* n_edges;
-    int* ns_edge; int* n_ns;
+    int* ns_edge; int* n_ns; int* n_oo;
     int* send_pk;                // first forward of a dynamics() call (GraphBufs::send_pk)
     int* rowlist; int* n_rows;   // ragged batches (GraphBufs::rowlist)
 };

@@ -58,13 +58,17 @@ constexpr int CHAIN_LDS_FLOATS = 2 * BUF_FLOATS + (WG / 64) * STG_FLOATS;
 
 struct Act { f32x16 t[5]; };
 // Zero skip (mma_act) per chain, fixed at build time.  The propagate chains (k_node_prop) have it: -4.7 % / -6.7 % per launch on the
-// flagship batch.  The relation-encoder chain does not: 8 % of its k-steps are dead there, but its wavefronts run MFMA-bound from
-// quarter barrier to quarter barrier, a quarter costs what its slowest wavefront costs, and the mask, branches and waits cost
-// 6 % where nothing is dead (measured: +1.7 % per launch, +0.8 % per rollout).  k_node_enc is built like the relation-encoder chain
-// and is not on the flagship path (the class table goes through the latency-mode chain); unmeasured, so it stays as it was.
-// docs/EXPERIMENTS.md, "Zero skip in the fp32 chains".  -DAG_ZS_EDGE=1 / -DAG_ZS_ENC=1 / -DAG_ZS_NODE=0: experiment builds.
+// flagship batch.  The relation-encoder chain has it per tile, on the class-major work list (Options::edge_order, k_ell_index): in
+// slot order 8 % of its k-steps are dead and the mask, branches and waits cost 6 % where nothing is dead (+1.7 % per launch); with
+// the wavefronts holding edges of one direction class 21 % are dead and the chain is 10 % faster per launch (1.489 -> 1.340 ms),
+// the rollout 4.2 %.  AG_ZS_EDGE: 0 = no skip (the chain's code is then the pre-skip one, instruction for instruction), 1 (shipped)
+// = the tiles that start among the object-object classes of a class-major list (GDev::n_oo), 2 = every tile (experiment build;
+// measured equal to 1).  k_node_enc is built like the relation-encoder chain and is not on the flagship path (the class table goes
+// through the latency-mode chain); unmeasured, so it stays as it was.
+// docs/EXPERIMENTS.md, "Zero skip in the fp32 chains" and "Class-major work list".  -DAG_ZS_EDGE=0|2 / -DAG_ZS_ENC=1 / -DAG_ZS_NODE=0:
+// experiment builds.
 #ifndef AG_ZS_EDGE
-#define AG_ZS_EDGE 0
+#define AG_ZS_EDGE 1
 #endif
 #ifndef AG_ZS_ENC
 #define AG_ZS_ENC 0
@@ -72,7 +76,7 @@ struct Act { f32x16 t[5]; };
 #ifndef AG_ZS_NODE
 #define AG_ZS_NODE 1
 #endif
-constexpr bool ZS_EDGE = AG_ZS_EDGE != 0, ZS_ENC = AG_ZS_ENC != 0, ZS_NODE = AG_ZS_NODE != 0;
+constexpr bool ZS_EDGE = AG_ZS_EDGE != 0, ZS_EDGE_ALL = AG_ZS_EDGE == 2, ZS_ENC = AG_ZS_ENC != 0, ZS_NODE = AG_ZS_NODE != 0;
 
 // ------------------------------------------------------------------------------------------------ staging
 // global -> LDS DMA (global_load_lds, 16 B per lane): NFLOATS (a multiple of 256) in 1-KB pieces, each wave-instruction
@@ -327,6 +331,7 @@ struct GDev {
     const float* c_eff; const float* c_P;
     long row0, nrows;          // k_node_enc: slice of rows to encode
     const int* ns_edge; const int* n_ns;   // k_edge_enc: non-self-loop edge list (null = every edge)
+    const int* n_oo;                       // k_edge_enc: class-major list, entries from n_oo[b] on are tool edges (null = slot order)
     const float* wb3;                      // bf16x3 weight image (null = exact fp32 mode)
     // message passing fused into the propagate chains (gather_agg): inputs of THIS round (Uin/Vin: the class table in the
     // first round of a rollout step, else what the previous round's chain wrote) - never the buffers this launch writes
@@ -625,6 +630,11 @@ __global__ __launch_bounds__(WG, 2) void k_edge_enc(GDev g) {
     const int e0 = (int)(blk / (unsigned)g.B) * WG_ROWS;
     const int ne = g.n_ns ? g.n_ns[b] : g.n_edges[b];       // rows to encode: all edges, or the non-self-loop ones
     if (e0 >= ne) continue;                                  // whole workgroup past this candidate's edges
+    // Zero skip per tile (AG_ZS_EDGE, top of the file).  Gated: only the tiles that start inside the object-object classes of a
+    // class-major list (GDev::n_oo; null = slot order: never) - a tile that starts at or past n_oo[b] holds tool edges only, whose
+    // wavefronts are mixed (7 % dead k-steps against 20 %): its mask is not built, every k-step counts as live.
+    int skip = 0;
+    if (ZS_EDGE) skip = g.zero_skip && (ZS_EDGE_ALL || (g.n_oo && e0 < g.n_oo[b])) ? 1 : 0;
 #ifdef AG_DIAG
     if (g.dbg && tid == 0) {
         g.dbg[blk * 4 + 0] = __builtin_amdgcn_s_memtime();
@@ -666,11 +676,13 @@ __global__ __launch_bounds__(WG, 2) void k_edge_enc(GDev g) {
     mma_feat<EDGE_L1_CHUNKS, (RD + 2) / 2>(lds + BUF_FLOATS, f, y.t, lane);     // RD inputs + bias: 9 (n_his 4) / 11 steps of 12
     __syncthreads();
     relu_one(y, lane);
-    layer160<Q_FLOATS, true, false, ZS_EDGE>(lds, wts + WL::E_L2, wts + WL::E_L3, y, x, tid, lane, live_of(y, g.zero_skip));
+    // (ZS_EDGE: one copy of the sweeps - a plain tile carries a full mask and pays the bit tests, not the ballots.  Two copies
+    // behind one branch were compiled and not run: 256 VGPRs and 152-192 B of scratch, docs/EXPERIMENTS.md)
+    layer160<Q_FLOATS, true, false, ZS_EDGE>(lds, wts + WL::E_L2, wts + WL::E_L3, y, x, tid, lane, live_of(y, skip));
     relu_one(x, lane);
-    layer160<Q_FLOATS, true, false, ZS_EDGE>(lds, wts + WL::E_L3, wts + WL::E_W1, x, y, tid, lane, live_of(x, g.zero_skip));
+    layer160<Q_FLOATS, true, false, ZS_EDGE>(lds, wts + WL::E_L3, wts + WL::E_W1, x, y, tid, lane, live_of(x, skip));
     relu_one(y, lane);
-    layer160<0, true, false, ZS_EDGE>(lds, wts + WL::E_W1, nullptr, y, x, tid, lane, live_of(y, g.zero_skip));
+    layer160<0, true, false, ZS_EDGE>(lds, wts + WL::E_W1, nullptr, y, x, tid, lane, live_of(y, skip));
     store_rows_t(x, g.C, (int)((long)b * g.c_cap + el), valid, stg, lane);
 #ifdef AG_DIAG
     if (g.dbg && tid == 0) {
@@ -1152,7 +1164,7 @@ static GDev to_dev(const float* w, const GraphBufs& g) {
     d.c_cap = g.c_cap; d.clamp = 0; d.pred_pos = nullptr; d.pred_motion = nullptr; d.n_tiles = 0;
     d.cls_on = g.cls_on; d.N_o = g.N_o; d.M = g.M; d.first_round = 0; d.vmask = g.vmask; d.c_eff = g.c_eff; d.c_P = g.c_P;
     d.row0 = 0; d.nrows = (long)g.B * g.N;
-    d.ns_edge = g.ns_edge; d.n_ns = g.n_ns;
+    d.ns_edge = g.ns_edge; d.n_ns = g.n_ns; d.n_oo = g.n_oo;
     d.wb3 = g.wb3;
     d.Uin = nullptr; d.Vin = nullptr; d.deg = g.deg; d.ell_stride = g.ell_stride; d.dedupe = g.c_self ? 1 : 0;
     d.self_row = (unsigned)g.self_row; d.n_guard = g.n_guard;

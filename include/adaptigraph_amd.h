@@ -175,7 +175,17 @@ int ag_ctx_set_chunk(ag_ctx* ctx, int32_t candidates_per_chunk);
  *                                         model that holds an inf or NaN weight, ag_ctx_load_weights_device / ag_adam_step always
  *                                         (no host code sees those values).  ag_ctx_get_option "zero_skip_active" (read-only) = 1
  *                                         when the option is on and the guard has not turned it off
- * Unknown names and values outside an option's range return AG_ERR_INVALID (ranges: stream_min_rows 0..INT32_MAX, pipeline_fork 0..1, streams 0..4, chunk 0..2^20, latency -1..1,
+ *   "edge_order"     [AG_EDGE_ORDER]      order of the relation encoder's work list on the rollout's slot-indexed graphs: 0 = slot
+ *                                         order (receiver-major); 1 (default) = class-major: the object-object slots by the sign bits
+ *                                         and the dominant axis of pos_r - pos_s at the current frame (24 classes), then every slot
+ *                                         with a tool particle at either end, slot order inside a class.  Wavefronts of the relation
+ *                                         encoder then hold like edges, more of their k-steps are all zero, and with "zero_skip" the
+ *                                         fp32 relation-encoder chain branches over them in the tiles of the object-object classes.
+ *                                         A C row is stored by slot and does not depend on the lane that computes it: same bits
+ *   "ell_lds_words"  [AG_ELL_LDS_WORDS]   debug: LDS budget, in 64-bit words, of the class bitmaps of "edge_order" 1 (0 = the
+ *                                         built-in 16384 = 128 KB).  A graph whose 25 bitmaps do not fit takes two classes
+ *                                         (object-object, tool), then the one list of slot order; tests reach the fallbacks with it
+ * Unknown names and values outside an option's range return AG_ERR_INVALID (ranges: edge_order 0..1, ell_lds_words 0..16384, stream_min_rows 0..INT32_MAX, pipeline_fork 0..1, streams 0..4, chunk 0..2^20, latency -1..1,
  * the 0/1 switches 0..1, edge_wgs 1..65536, edge_block_min -1..INT32_MAX, enc_persist 0..2^20, stagger_us 0..1000,
  * device_decode -1..1, share_first -1..1, share_prefix -1..1). */
 int ag_ctx_set_option(ag_ctx* ctx, const char* name, int32_t value);

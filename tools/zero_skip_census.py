@@ -15,7 +15,13 @@ Printed per layer: the share of (wavefront, k-step) pairs whose two features are
 MFMAs zero_skip leaves out - and the share of (wavefront, 4-step chunk) pairs that are dead as a whole (their weight-fragment
 reads go too).  Not modelled: the shared first forward (its object-object edges are encoded once per call, not per candidate).
 
-  python tools/zero_skip_census.py [--forwards 3] [--candidates 0,341,682,1023] [--json out.json]
+--order: the order of the relation encoder's work list (Options::edge_order, csrc/ag_edges.hip: k_ell_index).  `slot` is the
+receiver-major slot order; `tool-last` moves the edges with a tool at either end behind the object-object ones; `class` is the
+engine's class-major list: object-object edges by (d.x < 0, d.y < 0, d.z < 0) x argmax(|d.x|, |d.y|, |d.z|) of d = pos_r - pos_s
+at the current frame (ties to the lower axis, a NaN compares false), the tool class last, slot order inside a class
+(work_list_order below is the numpy restatement of that key).  The propagate chains do not depend on it.
+
+  python tools/zero_skip_census.py [--forwards 3] [--candidates 0,341,682,1023] [--order slot|tool-last|class] [--json out.json]
 """
 import argparse
 import json
@@ -58,7 +64,40 @@ def dead_share(act, first_row=0):
     return int((~live).sum()), int((~chunk_live).sum()), live.size, chunk_live.size
 
 
-def layers_of_forward(O, W, hist, attrs, recv, send, group, action, phys, pstep):
+N_CLASSES = 25
+
+
+def edge_classes(recv, send, pos, n_obj):
+    """class 0..24 of every edge (receiver, sender): k_ell_index's key, in fp32 like the kernel"""
+    pos = np.asarray(pos, F32)
+    d = pos[recv] - pos[send]
+    ad = np.abs(d)
+    ax = np.zeros(len(recv), np.int64)
+    m = ad[:, 0].copy()
+    up = ad[:, 1] > m
+    ax[up] = 1
+    m[up] = ad[up, 1]
+    ax[ad[:, 2] > m] = 2
+    cls = ((d[:, 0] < 0) * 1 + (d[:, 1] < 0) * 2 + (d[:, 2] < 0) * 4) * 3 + ax
+    cls[(recv >= n_obj) | (send >= n_obj)] = N_CLASSES - 1
+    return cls
+
+
+def work_list_order(recv, send, pos, n_obj, order):
+    """Permutation of the slot-order work list (the edges given, self-loops already left out): entry t of the engine's list is edge
+    perm[t].  Also returns the number of entries in front of the tool class (the whole list for `slot`)."""
+    n = len(recv)
+    if order == "slot":
+        return np.arange(n), n
+    assert order in ("tool-last", "class"), order
+    cls = edge_classes(recv, send, pos, n_obj)
+    tool = cls == N_CLASSES - 1
+    if order == "tool-last":
+        cls = tool.astype(np.int64)
+    return np.argsort(cls, kind="stable"), int((~tool).sum())
+
+
+def layers_of_forward(O, W, hist, attrs, recv, send, group, action, phys, pstep, order="slot", n_obj=None):
     """the hidden activations of one forward, as model_forward_single computes them; yields (chain, layer, rows x 150)"""
     n_his, N, _ = hist.shape
     res = hist[1:] - hist[:-1]
@@ -66,7 +105,8 @@ def layers_of_forward(O, W, hist, attrs, recv, send, group, action, phys, pstep)
     p_inputs = np.concatenate([attrs, phys[:, None], action], 1).astype(F32)
     gdiff = np.abs(group[recv] - group[send]).sum(1, keepdims=True)
     rel_inputs = np.concatenate([attrs[recv], attrs[send], gdiff, snt[recv] - snt[send]], 1).astype(F32)
-    ns = recv != send                                         # the relation encoder's work list
+    ns = np.flatnonzero(recv != send)                         # the relation encoder's work list
+    ns = ns[work_list_order(recv[ns], send[ns], hist[-1], N if n_obj is None else n_obj, order)[0]]
 
     def enc(x, pre):
         hs = []
@@ -98,6 +138,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--forwards", type=int, default=3)
     ap.add_argument("--candidates", default="0,341,682,1023")
+    ap.add_argument("--order", default="slot", choices=["slot", "tool-last", "class"])
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     import bench
@@ -131,15 +172,17 @@ def main():
             n_ns = int((rec["recv"] != rec["send"]).sum())
             n_tool = int(((rec["recv"] != rec["send"]) & ((rec["recv"] >= N_o) | (rec["send"] >= N_o))).sum())
             row = {"candidate": cand, "forward": k + 1, "edges": n_ns, "tool_edges": n_tool}
-            for chain, layer, act in layers_of_forward(O, W, hist, attrs, rec["recv"], rec["send"], group, action, phys, 3):
+            for chain, layer, act in layers_of_forward(O, W, hist, attrs, rec["recv"], rec["send"], group, action, phys, 3,
+                                                        args.order, N_o):
                 d = dead_share(act, 0 if chain == "edge" else cand * N)
                 key = (chain, layer)
                 tot[key] = tuple(x + y for x, y in zip(tot.get(key, (0, 0, 0, 0)), d))
                 row[f"{chain}.{layer}"] = round(d[0] / d[2], 4)
             per_forward.append(row)
-    print(f"zero-skip census: bench batch, candidates {picks}, forwards 1..{args.forwards} of look-ahead step 0")
+    print(f"zero-skip census: bench batch, candidates {picks}, forwards 1..{args.forwards} of look-ahead step 0, "
+          f"work list in {args.order} order")
     print(f"{'chain':10s} {'layer':6s} {'dead k-steps':>13s} {'dead chunks':>12s}   (wavefront x k-step pairs)")
-    out = {"candidates": picks, "forwards": args.forwards, "layers": [], "per_forward": per_forward}
+    out = {"candidates": picks, "forwards": args.forwards, "order": args.order, "layers": [], "per_forward": per_forward}
     chains = {}
     for (chain, layer), (ds, dc, ns_, nc) in tot.items():
         print(f"{chain:10s} {layer:6s} {100 * ds / ns_:12.2f}% {100 * dc / nc:11.2f}%   ({ns_})")

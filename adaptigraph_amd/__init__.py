@@ -50,6 +50,8 @@ from .rollout import rollout_eval, rollout_eval_step, surface_bounds, rollout_ev
 from .train_step import TrainStep
 from .set_losses import ChamferLoss, HausdorffLoss, LossSpec
 from .dataset import DeviceDynDataset, BatchDraws
+from . import perception
+from .perception import fps_cloud, construct_graph, state_cur_from_points
 
 __all__ = ["hw_queues", "Engine", "default_engine", "dynamics", "dynamics_masked", "dynamics_mixed", "rollout_work", "EdgeList", "construct_edges_from_states_batch", "construct_edges_from_states",
            "construct_edges_index", "construct_edges_with_backoff", "pad_torch", "truncate_graph", "DynamicsPredictor", "decode_action", "chamfer",
@@ -58,4 +60,4 @@ __all__ = ["hw_queues", "Engine", "default_engine", "dynamics", "dynamics_masked
            "dynamics_masked_diff", "chamfer_diff", "dynamics_error_grad", "optimize_grad", "TrainStep", "PhysParamFit",
            "optimize_grad_device", "dynamics_error_grad_device", "DeviceDynDataset", "BatchDraws", "construct_edges_graphs",
            "nonfixed_rule_graphs", "surface_rule_graphs", "BackoffPlan", "RuleConfig", "rule_attempt", "backoff_rounds", "attempt_with_backoff",
-           "ChamferLoss", "HausdorffLoss", "LossSpec"]
+           "ChamferLoss", "HausdorffLoss", "LossSpec", "perception", "fps_cloud", "construct_graph", "state_cur_from_points"]

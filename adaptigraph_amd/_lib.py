@@ -34,7 +34,7 @@ EXPORTS = ["ag_abi_version", "ag_ctx_create", "ag_ctx_destroy", "ag_last_error",
            "ag_ctx_load_weights_device", "ag_adam_step", "ag_train_step", "ag_ppm_grad_step", "ag_ppm_adam_step", "ag_train_step_part",
            "ag_fps_batch", "ag_dataset_assemble", "ag_build_edges_graphs", "ag_eval_step",
            "ag_edges_nonfixed_rule_graphs", "ag_edges_surface_rule_graphs",
-           "ag_set_loss", "ag_set_loss_backward", "ag_train_step_losses"]
+           "ag_set_loss", "ag_set_loss_backward", "ag_train_step_losses", "ag_fps_cloud"]
 
 AG_LOSS_MSE, AG_LOSS_CHAMFER, AG_LOSS_HAUSDORFF = 0, 1, 2
 
@@ -166,6 +166,7 @@ def load():
     lib.ag_mppi_update.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, vp]
     lib.ag_mppi_clip.argtypes = [vp, vp, vp, vp, vp, C.c_int64, vp]
     lib.ag_fps_batch.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp]
+    lib.ag_fps_cloud.argtypes = lib.ag_fps_batch.argtypes
     lib.ag_dataset_assemble.argtypes = [vp, vp, C.POINTER(AgDatasetBatch)]
     lib.ag_build_edges_graphs.argtypes = [vp, vp, vp, C.c_int64, vp, vp, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp]
     lib.ag_eval_step.argtypes = [vp, vp, C.POINTER(AgEvalStepArgs)]

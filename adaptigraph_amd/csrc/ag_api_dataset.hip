@@ -33,6 +33,31 @@ int ag_fps_batch(ag_ctx* c, void* stream, const float* d_pos, const int64_t* d_p
     return AG_OK;
 }
 
+int ag_fps_cloud(ag_ctx* c, void* stream, const float* d_pos, const int64_t* d_pt_off, const int64_t* d_npts, int32_t stride,
+                 const int32_t* d_fps_start, const float* d_fps_radius, const int32_t* d_rad_start, int32_t B, int32_t max_nobj,
+                 int32_t max_pts, int32_t* d_fps_idx, int32_t* d_n_obj) {
+    if (!c) return AG_ERR_INVALID;
+    if (!d_pos || !d_pt_off || !d_npts || !d_fps_start || !d_fps_radius || !d_rad_start || !d_fps_idx || !d_n_obj)
+        return fail(c, AG_ERR_INVALID, "ag_fps_cloud: null pointer");
+    if (B < 1 || stride < 1 || max_nobj < 1 || max_pts < 1)
+        return fail(c, AG_ERR_INVALID, "ag_fps_cloud: B=%d stride=%d max_nobj=%d max_pts=%d", B, stride, max_nobj, max_pts);
+    if ((size_t)max_pts > fps_cloud_max_points())
+        return fail(c, AG_ERR_UNSUPPORTED, "ag_fps_cloud: a cloud of %d points exceeds the limit %zu", max_pts, fps_cloud_max_points());
+    if (max_nobj > fps_max_nobj())
+        return fail(c, AG_ERR_UNSUPPORTED, "ag_fps_cloud: max_nobj=%d exceeds %d", max_nobj, fps_max_nobj());
+    SlotGuard call;
+    if (int rc = begin_call(c, stream, call)) return rc;
+    float* ws = nullptr;                 // running minima of the points behind the register-resident ones, per cloud
+    if (int rc = carve_slab(c, *call.sl, [&](Slab& s) { ws = s.take<float>(fps_cloud_ws_floats(B, max_pts)); })) return rc;
+    FpsArgs a{};
+    a.pos = d_pos; a.pt_off = reinterpret_cast<const long long*>(d_pt_off); a.npts = reinterpret_cast<const long long*>(d_npts);
+    a.stride = stride; a.fps_start = d_fps_start; a.fps_radius = d_fps_radius; a.rad_start = d_rad_start;
+    a.B = B; a.max_nobj = max_nobj; a.max_pts = max_pts; a.fps_idx = d_fps_idx; a.n_obj = d_n_obj;
+    Scoped p(c, FAM_FPS);
+    HIPCHK(c, launch_fps_cloud(a, ws, call.st));
+    return AG_OK;
+}
+
 int ag_dataset_assemble(ag_ctx* c, void* stream, const ag_dataset_batch* d) {
     if (!c) return AG_ERR_INVALID;
     if (!d) return fail(c, AG_ERR_INVALID, "ag_dataset_assemble: null batch");

@@ -171,6 +171,11 @@ struct FpsArgs {
 hipError_t launch_fps_batch(const FpsArgs& a, hipStream_t st);
 size_t fps_max_points();
 int fps_max_nobj();
+// the same on clouds beyond LDS (k_fps_cloud); ws: fps_cloud_ws_floats(B, max_pts) floats of the call's workspace
+hipError_t launch_fps_cloud(const FpsArgs& a, float* ws, hipStream_t st);
+size_t fps_cloud_max_points();
+size_t fps_cloud_switch_points();
+size_t fps_cloud_ws_floats(int B, int max_pts);
 // list of non-self-loop edges per candidate (self-loop dedupe, see GraphBufs)
 // one tool-attachment rule of the single-graph builder applied to a CSR edge list (ag_rules.hip)
 struct RuleArgs {

@@ -3,6 +3,7 @@
 //
 //   k_fps_batch         both farthest-point stages (dataset/graph.py:8-36) of B samples, one workgroup per sample
 //   k_dataset_assemble  every dense tensor of the batch, zero padding included, straight from the flat episode buffers
+//   k_fps_cloud         k_fps_batch's two stages for clouds beyond LDS (perception.py:259-315), the cloud read from global memory
 //
 // Indices and un-augmented tensors must equal the reference bit for bit, so the fp32 arithmetic is spelled out:
 //   stage 1 (dgl.geometry.farthest_point_sampler, restated from its CPU implementation - dgl is not available to check
@@ -49,16 +50,51 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
 // max of `mine` over the workgroup, in every thread.  `it` counts the reductions of the launch: consecutive ones use
 // alternate halves of wkey, so one barrier per reduction is enough (a thread can only overwrite a half after every thread
 // has passed the barrier of the reduction in between, i.e. has read it).
+// WAVES: wavefronts of the workgroup (wkey holds 2 * WAVES keys).
+template <int WAVES = FWAVES>
 __device__ __forceinline__ unsigned long long block_max_u64(unsigned long long mine, unsigned long long* wkey, int& it) {
     mine = wave_max_u64(mine);
-    unsigned long long* w = wkey + (it & 1) * FWAVES;
+    unsigned long long* w = wkey + (it & 1) * WAVES;
     if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = mine;
     __syncthreads();
     unsigned long long g = w[0];
 #pragma unroll
-    for (int k = 1; k < FWAVES; ++k) g = w[k] > g ? w[k] : g;
+    for (int k = 1; k < WAVES; ++k) g = w[k] > g ? w[k] : g;
     ++it;
     return g;
+}
+
+// Stage 2 (fps_rad_idx) on the n1 stage-1 points sx / sy / sz (LDS, selection order; sidx: their cloud indices), starting at
+// `cur`, by a workgroup of W threads that keeps PPT2 points each (W * PPT2 >= n1): writes the kept cloud indices to out[] in
+// selection order and returns their count, the same value in every thread.
+template <int W, int PPT2>
+__device__ __forceinline__ int fps_stage2(const float* sx, const float* sy, const float* sz, const int* sidx, int n1, float radius,
+                                          int cur, int* out, unsigned long long* wkey, int& it) {
+    const int tid = threadIdx.x;
+    float m2[PPT2];
+#pragma unroll
+    for (int u = 0; u < PPT2; ++u) m2[u] = __builtin_huge_valf();
+    int count = 0;
+    while (true) {
+        if (tid == 0) out[count] = sidx[cur];
+        ++count;
+        const float cx = sx[cur], cy = sy[cur], cz = sz[cur];
+        unsigned long long best = 0;
+#pragma unroll
+        for (int u = 0; u < PPT2; ++u) {
+            const int i = u * W + tid;
+            if (i < n1) {
+                const float d = __fsqrt_rn(fps_d2(sx[i], sy[i], sz[i], cx, cy, cz));
+                m2[u] = m2[u] > d ? d : m2[u];
+                const unsigned long long key = fps_key(m2[u], i);
+                best = key > best ? key : best;
+            }
+        }
+        const unsigned long long g = block_max_u64<W / 64>(best, wkey, it);           // the same value in every thread
+        if (!(__uint_as_float((unsigned)(g >> 32)) > radius) || count >= n1) break;
+        cur = (int)(0xffffffffu - (unsigned)(g & 0xffffffffull));
+    }
+    return count;
 }
 
 struct FpsDev {
@@ -121,30 +157,8 @@ __global__ __launch_bounds__(FW) void k_fps_batch(FpsDev a) {
     __syncthreads();
     // ---- stage 2 on the n1 selected points
     const float radius = a.fps_radius[b];
-    float m2[FPS_PPT2];
-#pragma unroll
-    for (int u = 0; u < FPS_PPT2; ++u) m2[u] = __builtin_huge_valf();
     cur = min(max(a.rad_start[b], 0), n1 - 1);
-    int count = 0;
-    while (true) {
-        if (tid == 0) out[count] = sidx[cur];
-        ++count;
-        const float cx = sx[cur], cy = sy[cur], cz = sz[cur];
-        unsigned long long best = 0;
-#pragma unroll
-        for (int u = 0; u < FPS_PPT2; ++u) {
-            const int i = u * FW + tid;
-            if (i < n1) {
-                const float d = __fsqrt_rn(fps_d2(sx[i], sy[i], sz[i], cx, cy, cz));
-                m2[u] = m2[u] > d ? d : m2[u];
-                const unsigned long long key = fps_key(m2[u], i);
-                best = key > best ? key : best;
-            }
-        }
-        const unsigned long long g = block_max_u64(best, wkey, it);                   // the same value in every thread
-        if (!(__uint_as_float((unsigned)(g >> 32)) > radius) || count >= n1) break;
-        cur = (int)(0xffffffffu - (unsigned)(g & 0xffffffffull));
-    }
+    const int count = fps_stage2<FW, FPS_PPT2>(sx, sy, sz, sidx, n1, radius, cur, out, wkey, it);
     for (int t = count + tid; t < a.max_nobj; t += FW) out[t] = -1;
     if (tid == 0) a.n_obj[b] = count;
 }
@@ -178,6 +192,116 @@ hipError_t launch_fps_batch(const FpsArgs& h, hipStream_t st) {
     if (ppt == 4) return launch_fps<4>(a, h.B, lds, st);
     if (ppt == 16) return launch_fps<16>(a, h.B, lds, st);
     return launch_fps<FPS_PPT_MAX>(a, h.B, lds, st);
+}
+
+// ---------------------------------------------------------------------------------------------- clouds beyond LDS
+// k_fps_cloud: the same two stages on clouds of up to 2^20 points (perception.py:259-315, the merged tabletop cloud), one
+// workgroup per cloud, the cloud read from global memory on every sweep.  Arithmetic, argmax order and outputs are k_fps_batch's.
+//   Workgroup: CW = 1024 threads, the largest there is.  One workgroup is all that works on a cloud (the argmax of every selected
+//   point is a rendezvous of everything that sweeps), so its 16 wavefronts - four per SIMD - are what hides the latency of the
+//   loads; that leaves 128 VGPRs per thread.
+//   Points: thread t owns the points u * CW + t, ascending in u, so "strictly greater" inside a thread keeps its lowest index and
+//   one packed key per thread goes into the reduction.  (The minima are never negative or NaN - a NaN distance loses "md > d" - so
+//   their bit patterns order as signed integers, -1 standing for "no point".)
+//   Coordinates: read as they lie, AoS, one 12-byte load per point.  A wavefront's load then covers 768 contiguous bytes and uses
+//   every byte of every line it fetches, like three SoA loads of 256 bytes would, with one instruction in place of three - a one-
+//   time SoA copy would buy nothing and cost 12 bytes of workspace per point.  (Reading x, y and z with three dword loads at a
+//   12-byte stride is what to avoid: each of them would touch all six lines.)
+//   Minima: those of the first CLOUD_S = CW * CLOUD_PPT points stay in registers (CLOUD_PPT per thread, in groups of CLOUD_GRP that
+//   a wave skips as a whole once past the cloud's end); those of the points behind live in the call's workspace, max_pts - CLOUD_S
+//   floats per cloud, read and written by their owner thread only (no barrier needed for them).  A cloud takes the workspace part
+//   of the sweep iff it has more than CLOUD_S points, whatever else is in the launch.
+// Bounded by: stage 1 makes min(max_nobj, n) - 1 sweeps of n points, stage 2 at most min(max_nobj, n) of as many points; every
+// load index is clamped below n.  No atomics, no flag, nothing waits for another workgroup.
+constexpr int CW = 1024;
+constexpr int CLOUD_PPT = 32;
+constexpr int CLOUD_GRP = 8;
+constexpr int CLOUD_S = CW * CLOUD_PPT;               // 32768 points with their minima in registers
+constexpr int CLOUD_MAX_POINTS = 1 << 20;
+static_assert(CW >= FPS_MAX_NOBJ && CLOUD_PPT % CLOUD_GRP == 0, "stage 2 keeps one point per thread");
+
+size_t fps_cloud_max_points() { return CLOUD_MAX_POINTS; }
+size_t fps_cloud_switch_points() { return CLOUD_S; }
+size_t fps_cloud_ws_floats(int B, int max_pts) { return max_pts > CLOUD_S ? (size_t)B * (size_t)(max_pts - CLOUD_S) : 0; }
+
+struct __attribute__((packed, aligned(4))) P3 { float x, y, z; };
+
+// one point of a sweep: its minimum against the centre, and the thread's running (bits, index) argmax
+__device__ __forceinline__ float cloud_visit(const P3* p, int i, int n, float md, float cx, float cy, float cz, int& bestb, int& besti) {
+    const P3 q = p[i < n ? i : n - 1];                 // branch-free: a point past the end reads the last one and is not counted
+    const float d = fps_d2(q.x, q.y, q.z, cx, cy, cz);
+    md = md > d ? d : md;
+    const int mb = i < n ? (int)__float_as_uint(md) : -1;
+    if (mb > bestb) { bestb = mb; besti = i; }
+    return md;
+}
+
+__global__ __launch_bounds__(CW) void k_fps_cloud(FpsDev a, float* ws) {
+    __shared__ unsigned long long wkey[2 * (CW / 64)];
+    __shared__ float sx[FPS_MAX_NOBJ], sy[FPS_MAX_NOBJ], sz[FPS_MAX_NOBJ];           // stage-1 points in selection order
+    __shared__ int sidx[FPS_MAX_NOBJ];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    int* out = a.fps_idx + (long)b * a.max_nobj;
+    const long long nraw = a.npts[(long)b * a.stride];
+    const int n = (int)(nraw < 0 ? 0 : nraw > (long long)a.max_pts ? (long long)a.max_pts : nraw);   // keeps ws inside its stride
+    if (n == 0) {
+        for (int t = tid; t < a.max_nobj; t += CW) out[t] = -1;
+        if (tid == 0) a.n_obj[b] = 0;
+        return;
+    }
+    const P3* p = reinterpret_cast<const P3*>(a.pos + a.pt_off[(long)b * a.stride] * 3);
+    float* wmd = ws + (long)b * (long)max(a.max_pts - CLOUD_S, 0);                    // minimum of point i >= CLOUD_S: wmd[i - CLOUD_S]
+    for (int i = CLOUD_S + tid; i < n; i += CW) wmd[i - CLOUD_S] = 1e10f;
+    int it = 0;
+    // ---- stage 1
+    const int n1 = min(a.max_nobj, n);
+    float md[CLOUD_PPT];
+#pragma unroll
+    for (int u = 0; u < CLOUD_PPT; ++u) md[u] = 1e10f;
+    int cur = min(max(a.fps_start[b], 0), n - 1);
+    for (int k = 0;; ++k) {
+        const P3 c = p[cur];                                                         // same address in every lane
+        if (tid == 0) { sidx[k] = cur; sx[k] = c.x; sy[k] = c.y; sz[k] = c.z; }
+        if (k + 1 >= n1) break;
+        int bestb = -1, besti = 0;
+#pragma unroll
+        for (int g = 0; g < CLOUD_PPT; g += CLOUD_GRP) {
+            if (g * CW < n) {                                                        // uniform over the workgroup
+#pragma unroll
+                for (int u = g; u < g + CLOUD_GRP; ++u) md[u] = cloud_visit(p, u * CW + tid, n, md[u], c.x, c.y, c.z, bestb, besti);
+            }
+        }
+        for (int base = CLOUD_S; base < n; base += 4 * CW) {                         // uniform trip count
+            float m[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) { const int i = base + u * CW + tid; m[u] = i < n ? wmd[i - CLOUD_S] : 1e10f; }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int i = base + u * CW + tid;
+                m[u] = cloud_visit(p, i, n, m[u], c.x, c.y, c.z, bestb, besti);
+                if (i < n) wmd[i - CLOUD_S] = m[u];
+            }
+        }
+        const unsigned long long key = bestb < 0 ? 0ull : fps_key(__uint_as_float((unsigned)bestb), besti);
+        const unsigned long long gk = block_max_u64<CW / 64>(key, wkey, it);
+        cur = (int)(0xffffffffu - (unsigned)(gk & 0xffffffffull));
+    }
+    __syncthreads();
+    // ---- stage 2 on the n1 selected points
+    const float radius = a.fps_radius[b];
+    cur = min(max(a.rad_start[b], 0), n1 - 1);
+    const int count = fps_stage2<CW, FPS_MAX_NOBJ / CW>(sx, sy, sz, sidx, n1, radius, cur, out, wkey, it);
+    for (int t = count + tid; t < a.max_nobj; t += CW) out[t] = -1;
+    if (tid == 0) a.n_obj[b] = count;
+}
+
+hipError_t launch_fps_cloud(const FpsArgs& h, float* ws, hipStream_t st) {
+    FpsDev a;
+    a.pos = h.pos; a.pt_off = h.pt_off; a.npts = h.npts; a.stride = h.stride;
+    a.fps_start = h.fps_start; a.fps_radius = h.fps_radius; a.rad_start = h.rad_start;
+    a.max_nobj = h.max_nobj; a.max_pts = h.max_pts; a.pad = 0; a.fps_idx = h.fps_idx; a.n_obj = h.n_obj;
+    hipLaunchKernelGGL(k_fps_cloud, dim3(h.B), dim3(CW), 0, st, a, ws);
+    return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------------- assembly

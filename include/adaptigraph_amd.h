@@ -624,6 +624,17 @@ int ag_fps_batch(ag_ctx* ctx, void* stream, const float* d_pos, const int64_t* d
                  const int32_t* d_fps_start, const float* d_fps_radius, const int32_t* d_rad_start, int32_t B, int32_t max_nobj,
                  int32_t max_pts, int32_t* d_fps_idx, int32_t* d_n_obj);
 
+/* ag_fps_batch for clouds that do not fit into LDS: the perceived tabletop cloud of perception.py:259-315 (construct_graph), one
+ * workgroup per cloud, any number of clouds per launch.  Arguments, both stages, their fp32 arithmetic, the tie rule, the clamping
+ * of the starts and the outputs are ag_fps_batch's: for every input that both entries accept the outputs are equal bit for bit (an
+ * empty cloud gives d_n_obj[b] = 0 and -1 throughout).  The cloud is read from global memory on every sweep; the running minima
+ * of a cloud's first 32768 points stay in registers, those of the points behind live in the call's workspace
+ * (B * (max_pts - 32768) floats, carved from the context: a second call of the same shape allocates nothing).
+ * Limits: 1 <= max_nobj <= 1024, 1 <= max_pts <= 1048576, else AG_ERR_UNSUPPORTED before anything is enqueued.  Enqueue only. */
+int ag_fps_cloud(ag_ctx* ctx, void* stream, const float* d_pos, const int64_t* d_pt_off, const int64_t* d_npts, int32_t stride,
+                 const int32_t* d_fps_start, const float* d_fps_radius, const int32_t* d_rad_start, int32_t B, int32_t max_nobj,
+                 int32_t max_pts, int32_t* d_fps_idx, int32_t* d_n_obj);
+
 /* One training batch (dataset.py:171-300), N = max_nobj + n_eef rows per sample.  T = n_his + n_future pair frames per sample: a
  * rest frame (store_rest_state with a short pair) is just frame index 0 in front. */
 typedef struct ag_dataset_batch {

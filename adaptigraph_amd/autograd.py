@@ -9,15 +9,37 @@ returns dLoss/daction and dLoss/dphys, the two data gradients the physics-parame
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
-from .context import ptr, current_stream
+from .context import ptr, current_stream, _vp_array
+from .marshal import ModelInputs
 
 
-def _vp_array(ts):
-    return (C.c_void_p * len(ts))(*[t.data_ptr() if t is not None else 0 for t in ts])
+def forward_call(eng, inp):
+    """ag_forward on a ModelInputs -> (pred_pos, pred_motion), both (B, n_p, 3)."""
+    dev = inp.state.device
+    pred_pos = torch.empty((inp.B, inp.n_p, 3), device=dev, dtype=torch.float32)
+    pred_motion = torch.empty((inp.B, inp.n_p, 3), device=dev, dtype=torch.float32)
+    eng.check(eng.lib.ag_forward(eng.ctx, current_stream(dev), *inp.c_args(), ptr(pred_pos), ptr(pred_motion)))
+    return pred_pos, pred_motion
+
+
+def _backward(ctx, g_pos, g_motion, inputs):
+    """ag_backward; inputs: ag_backward_inputs, which also returns the gradients toward action and phys where they are needed."""
+    state, attrs, action, phys, group, *params = ctx.saved_tensors
+    inp = ModelInputs(state, attrs, action, phys, group, ctx.edges, ctx.n_p)
+    eng, dev, need = ctx.eng, state.device, ctx.needs_input_grad
+    w_dev = [p.detach().to(device=dev, dtype=torch.float32).contiguous() for p in params]
+    g_w = [torch.empty_like(w) if n else None for w, n in zip(w_dev, need[8:])]
+    g_state = torch.empty_like(state) if need[3] else None
+    g_action = torch.empty_like(action) if inputs and need[5] else None
+    g_phys = torch.empty_like(phys) if inputs and need[6] else None
+    g_pos = g_pos.to(torch.float32).contiguous() if g_pos is not None else None
+    g_motion = g_motion.to(torch.float32).contiguous() if g_motion is not None else None
+    args = (eng.ctx, current_stream(dev), *inp.c_args(), _vp_array(w_dev), ptr(g_pos), ptr(g_motion), ptr(g_state), _vp_array(g_w))
+    eng.check(eng.lib.ag_backward_inputs(*args, ptr(g_phys), ptr(g_action)) if inputs else eng.lib.ag_backward(*args))
+    g_params = [g.to(p.device) if g is not None else None for g, p in zip(g_w, params)]
+    return (None, None, None, g_state, None, g_action, g_phys, None, *g_params)
 
 
 class DynamicsFunction(torch.autograd.Function):
@@ -28,37 +50,14 @@ class DynamicsFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, eng, edges, n_p, state, attrs, action, phys, group, *params):
-        dev = state.device
-        B, N = attrs.shape[0], attrs.shape[1]
-        n_inst = group.shape[2]
-        pred_pos = torch.empty((B, n_p, 3), device=dev, dtype=torch.float32)
-        pred_motion = torch.empty((B, n_p, 3), device=dev, dtype=torch.float32)
-        eng.check(eng.lib.ag_forward(eng.ctx, current_stream(dev), ptr(state), ptr(attrs), ptr(action), ptr(phys),
-                                     ptr(group), n_inst, ptr(edges.recv), ptr(edges.send), ptr(edges.row_ptr),
-                                     ptr(edges.n_edges), edges.edge_cap, B, N, n_p, ptr(pred_pos), ptr(pred_motion)))
+        out = forward_call(eng, ModelInputs(state, attrs, action, phys, group, edges, n_p))
         ctx.eng, ctx.edges, ctx.n_p = eng, edges, n_p
         ctx.save_for_backward(state, attrs, action, phys, group, *params)
-        return pred_pos, pred_motion
+        return out
 
     @staticmethod
     def backward(ctx, g_pos, g_motion):
-        state, attrs, action, phys, group, *params = ctx.saved_tensors
-        eng, edges, n_p = ctx.eng, ctx.edges, ctx.n_p
-        dev = state.device
-        B, N = attrs.shape[0], attrs.shape[1]
-        need_state = ctx.needs_input_grad[3]
-        need_w = ctx.needs_input_grad[8:]
-        w_dev = [p.detach().to(device=dev, dtype=torch.float32).contiguous() for p in params]
-        g_w = [torch.empty_like(w) if need else None for w, need in zip(w_dev, need_w)]
-        g_state = torch.empty_like(state) if need_state else None
-        g_pos = g_pos.to(torch.float32).contiguous() if g_pos is not None else None
-        g_motion = g_motion.to(torch.float32).contiguous() if g_motion is not None else None
-        eng.check(eng.lib.ag_backward(eng.ctx, current_stream(dev), ptr(state), ptr(attrs), ptr(action), ptr(phys),
-                                      ptr(group), group.shape[2], ptr(edges.recv), ptr(edges.send), ptr(edges.row_ptr),
-                                      ptr(edges.n_edges), edges.edge_cap, B, N, n_p, _vp_array(w_dev), ptr(g_pos),
-                                      ptr(g_motion), ptr(g_state), _vp_array(g_w)))
-        g_params = [g.to(p.device) if g is not None else None for g, p in zip(g_w, params)]
-        return (None, None, None, g_state, None, None, None, None, *g_params)
+        return _backward(ctx, g_pos, g_motion, inputs=False)
 
 
 class DynamicsDiffFunction(torch.autograd.Function):
@@ -70,22 +69,4 @@ class DynamicsDiffFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_pos, g_motion):
-        state, attrs, action, phys, group, *params = ctx.saved_tensors
-        eng, edges, n_p = ctx.eng, ctx.edges, ctx.n_p
-        dev = state.device
-        B, N = attrs.shape[0], attrs.shape[1]
-        need_state, need_action, need_phys = ctx.needs_input_grad[3], ctx.needs_input_grad[5], ctx.needs_input_grad[6]
-        need_w = ctx.needs_input_grad[8:]
-        w_dev = [p.detach().to(device=dev, dtype=torch.float32).contiguous() for p in params]
-        g_w = [torch.empty_like(w) if need else None for w, need in zip(w_dev, need_w)]
-        g_state = torch.empty_like(state) if need_state else None
-        g_action = torch.empty_like(action) if need_action else None
-        g_phys = torch.empty_like(phys) if need_phys else None
-        g_pos = g_pos.to(torch.float32).contiguous() if g_pos is not None else None
-        g_motion = g_motion.to(torch.float32).contiguous() if g_motion is not None else None
-        eng.check(eng.lib.ag_backward_inputs(eng.ctx, current_stream(dev), ptr(state), ptr(attrs), ptr(action), ptr(phys),
-                                             ptr(group), group.shape[2], ptr(edges.recv), ptr(edges.send), ptr(edges.row_ptr),
-                                             ptr(edges.n_edges), edges.edge_cap, B, N, n_p, _vp_array(w_dev), ptr(g_pos),
-                                             ptr(g_motion), ptr(g_state), _vp_array(g_w), ptr(g_phys), ptr(g_action)))
-        g_params = [g.to(p.device) if g is not None else None for g, p in zip(g_w, params)]
-        return (None, None, None, g_state, None, g_action, g_phys, None, *g_params)
+        return _backward(ctx, g_pos, g_motion, inputs=True)

@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import torch
 
@@ -25,6 +26,10 @@ def _require_gpu(device):
 
 def ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+def _vp_array(ts):
+    return (C.c_void_p * len(ts))(*[t.data_ptr() if t is not None else 0 for t in ts])
 
 
 def current_stream(device):
@@ -52,7 +57,6 @@ class Engine:
         self.pstep = pstep
         self._weights_key = None
         self.precision = "fp32"
-        import os
         if os.environ.get("AG_PRECISION", "fp32") != "fp32":
             self.set_precision(os.environ["AG_PRECISION"])
 

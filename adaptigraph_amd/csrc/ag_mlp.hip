@@ -1159,7 +1159,7 @@ __global__ __launch_bounds__(WGB, WGB_PER_CU) void k_node_prop_b3(GDev g) {
 static GDev to_dev(const float* w, const GraphBufs& g) {
     GDev d;
     d.w = w; d.node_in = g.node_in; d.feat12 = g.feat12; d.group = g.group; d.eff = g.eff; d.P = g.P; d.U = g.UV[1][0];
-    d.V = g.UV[1][1];; d.C = g.C; d.recv = g.recv; d.send = g.send; d.row_ptr = g.row_ptr;
+    d.V = g.UV[1][1]; d.C = g.C; d.recv = g.recv; d.send = g.send; d.row_ptr = g.row_ptr;
     d.n_edges = g.n_edges; d.B = g.B; d.N = g.N; d.n_p = g.n_p; d.n_inst = g.n_inst; d.edge_cap = g.edge_cap;
     d.c_cap = g.c_cap; d.clamp = 0; d.pred_pos = nullptr; d.pred_motion = nullptr; d.n_tiles = 0;
     d.cls_on = g.cls_on; d.N_o = g.N_o; d.M = g.M; d.first_round = 0; d.vmask = g.vmask; d.c_eff = g.c_eff; d.c_P = g.c_P;

@@ -55,11 +55,17 @@ def _tool_layout(decoded, theta, task_config):
     return xz, delta
 
 
-def _physics(ppm_optimizer, physics_param, N_o, dev):
+def _material(ppm_optimizer, physics_param):
+    """(the one material's name, the parameter dictionary in force: the optimizer's own unless the caller passes one)."""
     material_dims = ppm_optimizer.material_dims
-    physics_param = ppm_optimizer.physics_param if physics_param is None else physics_param
     assert len(material_dims) == 1          # the model asserts exactly one *_physics_param key (model.py:186-187)
     (name, _dim), = material_dims.items()
+    return name, ppm_optimizer.physics_param if physics_param is None else physics_param
+
+
+def _physics(ppm_optimizer, physics_param, N_o, dev):
+    """The rollout's physics parameter as (AgRolloutParams.physics_param, d_phys_vec): a scalar, or one value per object particle."""
+    name, physics_param = _material(ppm_optimizer, physics_param)
     if name not in physics_param:
         return 0.0, None                    # forward_dynamics.py:152-153 zeros
     v = physics_param[name].detach().to("cpu", torch.float32).reshape(-1)
@@ -69,6 +75,23 @@ def _physics(ppm_optimizer, physics_param, N_o, dev):
     return 0.0, v.to(dev).contiguous()
 
 
+def _rollout_params(task, ppm_optimizer, model, B, H, N_o, y_mode, phys_val):
+    """AgRolloutParams of a rollout of B candidates x H look-ahead steps over N_o object particles (forward_dynamics.py:16-21)."""
+    assert int(task["n_his"]) == model.n_his, "task_config['n_his'] (forward_dynamics.py:16) must be the model's n_his"
+    grip = bool(task["gripper_enable"])
+    return _lib.AgRolloutParams(B, H, N_o, ppm_optimizer.eef_num, int(task["topk"]), int(bool(task["connect_tools_all"])),
+                                int(task["max_nR"]), y_mode, float(ppm_optimizer.adj_thresh),
+                                float(0.01 * task["sim_real_ratio"]) if grip else 0.0, int(grip), phys_val)
+
+
+def _pusher_offsets(task, M):
+    """The tool points' offsets along the pusher, for the device-side action decode: 8 floats, the first and those past M zero."""
+    pts = task["pusher_points"]
+    if len(pts) != M or M not in (1, 5):
+        raise NotImplementedError("pusher not implemented")
+    return (C.c_float * 8)(*([0.0] + [float(pts[k][1]) * task["sim_real_ratio"] for k in range(1, M)] + [0.0] * (8 - M)))
+
+
 def _run(model, dev, task, ppm_optimizer, physics_param, B, H, N_o, y_mode, state0, obj_mask, xz, delta, repeat,
          sync=True, overflow_flag=None):
     if not isinstance(model, DynamicsPredictor):
@@ -76,13 +99,8 @@ def _run(model, dev, task, ppm_optimizer, physics_param, B, H, N_o, y_mode, stat
     eng = model.engine(dev)
     M = ppm_optimizer.eef_num
     assert xz.shape[2] == M
-    assert int(task["n_his"]) == model.n_his, "task_config['n_his'] (forward_dynamics.py:16) must be the model's n_his"
-    grip = bool(task["gripper_enable"])
-    phys_val, phys_vec = _physics(ppm_optimizer, physics_param, N_o, dev)
-    adj = ppm_optimizer.adj_thresh
-    p = _lib.AgRolloutParams(B, H, N_o, M, int(task["topk"]), int(bool(task["connect_tools_all"])),
-                             int(task["max_nR"]), y_mode, float(adj), float(0.01 * task["sim_real_ratio"]) if grip else 0.0,
-                             int(grip), phys_val)
+    p = _rollout_params(task, ppm_optimizer, model, B, H, N_o, y_mode, 0.0)
+    p.physics_param, phys_vec = _physics(ppm_optimizer, physics_param, N_o, dev)
     xz_d = xz.to(torch.float32).contiguous().to(dev)
     delta_d = delta.to(torch.float32).contiguous().to(dev)
     rep = repeat.to("cpu", torch.int32).contiguous()
@@ -111,18 +129,10 @@ def _run_device_actions(model, eng, dev, task, ppm_optimizer, physics_param, act
     """ag_rollout_actions: decode + launch plan on the device (see module docstring).  Returns (state_seqs, decoded), or None
     when a repeat count beyond `bound` was seen and `strict` is off (the caller then takes the host-decode path, which - like
     the reference, forward_dynamics.py:156 - accepts any action length)."""
-    assert int(task["n_his"]) == model.n_his, "task_config['n_his'] (forward_dynamics.py:16) must be the model's n_his"
-    B, H = action.shape[0], action.shape[1]
-    N_o, M = state0.shape[0], ppm_optimizer.eef_num
-    pts = task["pusher_points"]
-    if len(pts) != M or M not in (1, 5):
-        raise NotImplementedError("pusher not implemented")
-    grip = bool(task["gripper_enable"])
-    phys_val, phys_vec = _physics(ppm_optimizer, physics_param, N_o, dev)
-    p = _lib.AgRolloutParams(B, H, N_o, M, int(task["topk"]), int(bool(task["connect_tools_all"])), int(task["max_nR"]), 0,
-                             float(ppm_optimizer.adj_thresh), float(0.01 * task["sim_real_ratio"]) if grip else 0.0,
-                             int(grip), phys_val)
-    offs = (C.c_float * 8)(*([0.0] + [float(pts[k][1]) * task["sim_real_ratio"] for k in range(1, M)] + [0.0] * (8 - M)))
+    B, H, N_o = action.shape[0], action.shape[1], state0.shape[0]
+    p = _rollout_params(task, ppm_optimizer, model, B, H, N_o, 0, 0.0)
+    offs = _pusher_offsets(task, ppm_optimizer.eef_num)
+    p.physics_param, phys_vec = _physics(ppm_optimizer, physics_param, N_o, dev)
     act = action.detach().to(dev, torch.float32).contiguous()
     out = torch.empty((B, H, N_o, 3), device=dev, dtype=torch.float32)
     decoded = torch.empty((B, H, 4), device=dev, dtype=torch.float32)
@@ -169,18 +179,11 @@ def rollout_work(state, action, model, device, ppm_optimizer, physics_param=None
     if eng is None or bound is None or not (0 <= bound <= 1024) or ppm_optimizer.eef_num > 8 or eng.get_option("device_decode") == 0:
         _, repeat = decode_action(action.detach().to("cpu", torch.float32), push_length=task["push_length"])
         return repeat.clamp(min=0).sum(1).to(torch.int64).numpy()
-    assert int(task["n_his"]) == model.n_his
     state0 = state.detach().to(dev, torch.float32).contiguous()
-    N_o, M = state0.shape[0], ppm_optimizer.eef_num
-    pts = task["pusher_points"]
-    if len(pts) != M or M not in (1, 5):
-        raise NotImplementedError("pusher not implemented")
-    grip = bool(task["gripper_enable"])
-    phys_val, phys_vec = _physics(ppm_optimizer, physics_param, N_o, dev)
-    p = _lib.AgRolloutParams(B, H, N_o, M, int(task["topk"]), int(bool(task["connect_tools_all"])), int(task["max_nR"]), 0,
-                             float(ppm_optimizer.adj_thresh), float(0.01 * task["sim_real_ratio"]) if grip else 0.0,
-                             int(grip), phys_val)
-    offs = (C.c_float * 8)(*([0.0] + [float(pts[k][1]) * task["sim_real_ratio"] for k in range(1, M)] + [0.0] * (8 - M)))
+    N_o = state0.shape[0]
+    p = _rollout_params(task, ppm_optimizer, model, B, H, N_o, 0, 0.0)
+    offs = _pusher_offsets(task, ppm_optimizer.eef_num)
+    p.physics_param, phys_vec = _physics(ppm_optimizer, physics_param, N_o, dev)
     act = action.detach().to(dev, torch.float32).contiguous()
     work = np.zeros(B, np.int32)
     eng.check(eng.lib.ag_rollout_work(eng.ctx, current_stream(dev), C.byref(p), ptr(state0), ptr(act), float(task["push_length"]),
@@ -299,10 +302,7 @@ def dynamics_masked_diff(state_init, state_mask, action, model, device, ppm_opti
     tool_mask[:, N_o:] = True
     full_mask = torch.cat([mask, tool_mask[:, N_o:]], 1)
 
-    material_dims = ppm_optimizer.material_dims
-    physics_param = ppm_optimizer.physics_param if physics_param is None else physics_param
-    assert len(material_dims) == 1          # the model asserts exactly one *_physics_param key (model.py:186-187)
-    (name, _dim), = material_dims.items()
+    name, physics_param = _material(ppm_optimizer, physics_param)
     pp = physics_param[name].to(device=dev, dtype=torch.float32)                           # :337-339
     if pp.dim() == 1:
         pp = pp[None].expand(B, pp.numel())

@@ -12,9 +12,10 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from .autograd import DynamicsFunction, DynamicsDiffFunction
-from .context import Engine, ptr, current_stream, _require_gpu, STATE_DICT_ORDER
+from .autograd import DynamicsFunction, DynamicsDiffFunction, forward_call
+from .context import Engine, _require_gpu, STATE_DICT_ORDER
 from .graph import EdgeList
+from .marshal import ModelInputs
 
 
 def _mlp3(n_in, n_hidden, n_out):
@@ -146,28 +147,35 @@ class DynamicsPredictor(nn.Module):
         with torch.no_grad():
             return self._forward_nograd(state, attrs, Rr, Rs, p_instance, action, edges, kwargs)
 
-    def _inputs(self, dev, state, attrs, Rr, Rs, p_instance, action, edges, kwargs):
-        """Model inputs in the C-ABI's form (model.py:152-282 on the host side): physics parameter per particle, group."""
+    def _inputs(self, dev, state, attrs, Rr, Rs, p_instance, action, edges, kwargs, diff=False):
+        """ModelInputs from forward()'s arguments (model.py:152-282 on the host side): the physics parameter per particle, the
+        group matrix, dense Rr / Rs as an EdgeList, all fp32 and contiguous on `dev`.  diff: action and the physics parameter stay
+        under the caller's autograd ((B,1) expands through _ExpandRows); else they are data, like attrs, p_instance and the edges.
+        state follows the caller's autograd either way."""
         B, N = attrs.size(0), attrs.size(1)
         n_p, n_inst = p_instance.size(1), p_instance.size(2)
         n_s = N - n_p
-        physics_keys = [k for k in kwargs.keys() if k.endswith("_physics_param")]
-        assert len(physics_keys) == 1                                            # model.py:186-187
-        pp = kwargs[physics_keys[0]].to(device=dev, dtype=torch.float32)
-        if pp.size(-1) == 1:
-            pp = pp[:, None, :].repeat(1, n_p, 1)                                # model.py:191-197
-        else:
-            pp = pp.reshape(B, n_p, 1)                                           # model.py:204
-        phys = torch.cat([pp[..., 0], torch.zeros(B, n_s, device=dev)], 1).contiguous()   # model.py:206-207
-        assert action is not None                                                # model.py:222
-        group = torch.cat([p_instance.to(torch.float32), torch.zeros(B, n_s, n_inst, device=dev)], 1).contiguous()
-        if edges is None:
-            assert Rr is not None and Rs is not None
-            edges = EdgeList.from_dense(Rr, Rs)
+        with torch.set_grad_enabled(diff and torch.is_grad_enabled()):
+            physics_keys = [k for k in kwargs.keys() if k.endswith("_physics_param")]
+            assert len(physics_keys) == 1                                        # model.py:186-187
+            pp = kwargs[physics_keys[0]].to(device=dev, dtype=torch.float32)
+            if pp.size(-1) == 1:                                                 # model.py:191-197
+                pp = _ExpandRows.apply(pp.reshape(B, 1), n_p) if diff else pp.reshape(B, 1).repeat(1, n_p)
+            else:
+                pp = pp.reshape(B, n_p)                                          # model.py:204
+            phys = torch.cat([pp, torch.zeros(B, n_s, device=dev)], 1).contiguous()   # model.py:206-207
+            assert action is not None                                            # model.py:222
+            action = action.to(device=dev, dtype=torch.float32).contiguous()
+        with torch.no_grad():
+            group = torch.cat([p_instance.to(torch.float32), torch.zeros(B, n_s, n_inst, device=dev)], 1).contiguous()
+            if edges is None:
+                assert Rr is not None and Rs is not None
+                edges = EdgeList.from_dense(Rr, Rs)
+            attrs = attrs.to(torch.float32).contiguous()
         assert edges.N == N
-        attrs = attrs.to(torch.float32).contiguous()
-        action = action.to(torch.float32).contiguous()
-        return attrs, action, phys, group, edges, n_p
+        state = state.to(device=dev, dtype=torch.float32).contiguous()
+        assert state.shape == (B, self.n_his, N, 3)
+        return ModelInputs(state, attrs, action, phys, group, edges, n_p)
 
     def _forward_grad(self, state, attrs, Rr, Rs, p_instance, action, edges, params, kwargs):
         data = [("attrs", attrs), ("p_instance", p_instance), ("action", action), ("Rr", Rr), ("Rs", Rs)]
@@ -178,11 +186,8 @@ class DynamicsPredictor(nn.Module):
                                           "reach state and the parameters only)")
         dev = _require_gpu(state.device)
         eng = self.engine(dev)
-        with torch.no_grad():
-            attrs, action, phys, group, edges, n_p = self._inputs(dev, state, attrs, Rr, Rs, p_instance, action, edges, kwargs)
-        state = state.to(torch.float32).contiguous()
-        assert state.shape == (attrs.size(0), self.n_his, attrs.size(1), 3)
-        return DynamicsFunction.apply(eng, edges, n_p, state, attrs, action, phys, group, *params)
+        inp = self._inputs(dev, state, attrs, Rr, Rs, p_instance, action, edges, kwargs)
+        return DynamicsFunction.apply(eng, inp.edges, inp.n_p, inp.state, inp.attrs, inp.action, inp.phys, inp.group, *params)
 
     def forward_diff(self, state, attrs, Rr=None, Rs=None, p_instance=None, action=None, particle_den=None, obj_mask=None,
                      edges: EdgeList | None = None, **kwargs):
@@ -197,57 +202,10 @@ class DynamicsPredictor(nn.Module):
         params = self.ordered_parameters()
         dev = _require_gpu(state.device)
         eng = self.engine(dev)
-        B, N = attrs.size(0), attrs.size(1)
-        n_p, n_inst = p_instance.size(1), p_instance.size(2)
-        n_s = N - n_p
-        physics_keys = [k for k in kwargs.keys() if k.endswith("_physics_param")]
-        assert len(physics_keys) == 1                                            # model.py:186-187
-        pp = kwargs[physics_keys[0]].to(device=dev, dtype=torch.float32)
-        if pp.size(-1) == 1:
-            pp = _ExpandRows.apply(pp.reshape(B, 1), n_p)                        # model.py:191-197
-        else:
-            pp = pp.reshape(B, n_p)                                              # model.py:204
-        phys = torch.cat([pp, torch.zeros(B, n_s, device=dev)], 1).contiguous()  # model.py:206-207
-        assert action is not None                                                # model.py:222
-        with torch.no_grad():
-            group = torch.cat([p_instance.to(torch.float32), torch.zeros(B, n_s, n_inst, device=dev)], 1).contiguous()
-            if edges is None:
-                assert Rr is not None and Rs is not None
-                edges = EdgeList.from_dense(Rr, Rs)
-            attrs = attrs.to(torch.float32).contiguous()
-        assert edges.N == N
-        action = action.to(device=dev, dtype=torch.float32).contiguous()
-        state = state.to(torch.float32).contiguous()
-        assert state.shape == (B, self.n_his, N, 3)
-        return DynamicsDiffFunction.apply(eng, edges, n_p, state, attrs, action, phys, group, *params)
+        inp = self._inputs(dev, state, attrs, Rr, Rs, p_instance, action, edges, kwargs, diff=True)
+        return DynamicsDiffFunction.apply(eng, inp.edges, inp.n_p, inp.state, inp.attrs, inp.action, inp.phys, inp.group, *params)
 
     def _forward_nograd(self, state, attrs, Rr, Rs, p_instance, action, edges, kwargs):
         dev = _require_gpu(state.device)
         eng = self.engine(dev)
-        B, N = attrs.size(0), attrs.size(1)
-        n_p, n_inst = p_instance.size(1), p_instance.size(2)
-        n_s = N - n_p
-        physics_keys = [k for k in kwargs.keys() if k.endswith("_physics_param")]
-        assert len(physics_keys) == 1                                            # model.py:186-187
-        pp = kwargs[physics_keys[0]].to(device=dev, dtype=torch.float32)
-        if pp.size(-1) == 1:
-            pp = pp[:, None, :].repeat(1, n_p, 1)                                # model.py:191-197
-        else:
-            pp = pp.reshape(B, n_p, 1)                                           # model.py:204
-        phys = torch.cat([pp[..., 0], torch.zeros(B, n_s, device=dev)], 1).contiguous()   # model.py:206-207
-        assert action is not None                                                # model.py:222
-        group = torch.cat([p_instance.to(torch.float32), torch.zeros(B, n_s, n_inst, device=dev)], 1).contiguous()
-        if edges is None:
-            assert Rr is not None and Rs is not None
-            edges = EdgeList.from_dense(Rr, Rs)
-        assert edges.N == N
-        state = state.to(torch.float32).contiguous()
-        attrs = attrs.to(torch.float32).contiguous()
-        action = action.to(torch.float32).contiguous()
-        assert state.shape == (B, self.n_his, N, 3)
-        pred_pos = torch.empty((B, n_p, 3), device=dev, dtype=torch.float32)
-        pred_motion = torch.empty((B, n_p, 3), device=dev, dtype=torch.float32)
-        eng.check(eng.lib.ag_forward(eng.ctx, current_stream(dev), ptr(state), ptr(attrs), ptr(action), ptr(phys),
-                                     ptr(group), n_inst, ptr(edges.recv), ptr(edges.send), ptr(edges.row_ptr),
-                                     ptr(edges.n_edges), edges.edge_cap, B, N, n_p, ptr(pred_pos), ptr(pred_motion)))
-        return pred_pos, pred_motion
+        return forward_call(eng, self._inputs(dev, state, attrs, Rr, Rs, p_instance, action, edges, kwargs))

@@ -13,9 +13,8 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
-from .context import side_streams as _sweep_streams, ptr, current_stream, _require_gpu
-from .forward_dynamics import dynamics_masked, dynamics_masked_diff, _tool_layout
+from .context import side_streams as _sweep_streams, ptr, current_stream, _require_gpu, _vp_array
+from .forward_dynamics import dynamics_masked, dynamics_masked_diff, _tool_layout, _rollout_params
 from .model import DynamicsPredictor
 from .plan_utils import decode_action
 from .losses import mean_chamfer, chamfer_diff
@@ -267,7 +266,6 @@ class _DeviceProblem:
         self.w = [p.detach() for p in model.ordered_parameters()]
         for t in self.w:
             assert t.device == dev and t.dtype == torch.float32 and t.is_contiguous(), "model parameters must be fp32 on the device"
-        from .autograd import _vp_array
         self._w_arr = _vp_array(self.w)
         self.seqs = torch.empty((self.R, self.N_o, 3), device=dev, dtype=torch.float32)
         self.err = torch.empty((self.R,), device=dev, dtype=torch.float32)
@@ -279,14 +277,12 @@ class _DeviceProblem:
         """enqueue ag_ppm_grad_step on the current stream: phys (R,N_o) device fp32 -> self.seqs, self.err, self.grad"""
         ppm, task, dev = self.ppm, self.ppm.task_config, self.dev
         eng = ppm.model.engine(dev)
-        grip = bool(task["gripper_enable"])
         N = self.N_o + self.M
         k = min(N, int(task["topk"]))
         bound = N * (k + self.M) if k < N else N * N                              # the builder's structural bound
         edge_rows = int(self.edge_rows) if self.edge_rows is not None else bound
-        p = _lib.AgRolloutParams(self.R, 1, self.N_o, self.M, int(task["topk"]), int(bool(task["connect_tools_all"])),
-                                 int(self.max_nR), 1, float(ppm.adj_thresh), float(0.01 * task["sim_real_ratio"]) if grip else 0.0,
-                                 int(grip), 0.0)
+        p = _rollout_params(task, ppm, ppm.model, self.R, 1, self.N_o, 1, 0.0)
+        p.max_nR = int(self.max_nR)                                               # the attribute, which may have moved since
         eng.check(eng.lib.ag_ppm_grad_step(
             eng.ctx, current_stream(dev), C.byref(p), ptr(self.state0), ptr(self.obj_mask), ptr(self.xz), ptr(self.delta),
             C.c_void_p(self.h_repeat.ctypes.data), ptr(self.d_repeat), ptr(phys), ptr(self.obs), ptr(self.obs_mask), self.N_t,

@@ -246,8 +246,7 @@ def rollout_eval_batch(model, ds, idx, rollout_steps=100, draws=None, keep_pred=
     eng = model.engine(dev)
     N, No = ds.N, sp.max_nobj
     kw = {k: v for k, v in data.items() if k.endswith("_physics_param")}
-    attrs, action, phys, group, edges, _ = model._inputs(dev, data["state"], data["attrs"], None, None, data["p_instance"], data["action"],
-                                                         data["edges"], kw)
+    inp = model._inputs(dev, data["state"], data["attrs"], None, None, data["p_instance"], data["action"], data["edges"], kw)
     f32 = dict(dtype=torch.float32, device=dev)
     errors = torch.full((L_max, B), float("nan"), **f32)
     pred = torch.full((L_max if keep_pred else 1, B, No, 3), float("nan"), **f32)
@@ -270,8 +269,7 @@ def rollout_eval_batch(model, ds, idx, rollout_steps=100, draws=None, keep_pred=
     if per_graph or limit:
         _eval_per_graph(model, ds, eng, data, aux, dr, order, scheds, tab, errors, pred, kept, trails, keep_pred)
     else:
-        _eval_batched(ds, eng, data, aux, (attrs, action, phys, group, edges), lengths[order], tab, errors, pred, kept, trails, keep_pred,
-                      waits)
+        _eval_batched(ds, eng, data, aux, inp, lengths[order], tab, errors, pred, kept, trails, keep_pred, waits)
     # ---- back to the caller's order
     o = torch.from_numpy(order).to(dev)
     out_err = torch.empty_like(errors)
@@ -292,7 +290,7 @@ def rollout_eval_batch(model, ds, idx, rollout_steps=100, draws=None, keep_pred=
     return EvalResult(out_err, lengths, scheds, out_trails, out_pred, out_edges, waits[0])
 
 
-def _eval_batched(ds, eng, data, aux, inputs, len_s, tab, errors, pred, kept, trails, keep_pred, waits):
+def _eval_batched(ds, eng, data, aux, inp, len_s, tab, errors, pred, kept, trails, keep_pred, waits):
     """rollout_eval_batch's step loop, for every config that advances together.
     Per step: ag_eval_step - it writes the BASE next graphs at top-k into the second edge buffer -, then
     graph.attempt_with_backoff on the graphs that go on: ag_edges_nonfixed_rule_graphs and / or ag_edges_surface_rule_graphs
@@ -303,7 +301,7 @@ def _eval_batched(ds, eng, data, aux, inputs, len_s, tab, errors, pred, kept, tr
     max_nR - and ag_eval_step is told edge_rows = max_nR.  A config with neither rule keeps the max_nR-wide double buffer: no
     launch follows the step, the base graphs are the next step's graphs and the two buffers swap roles."""
     sp, dev, N, nh = ds.spec, ds.device, ds.N, ds.spec.n_his
-    attrs, action, phys, group, edges = inputs
+    attrs, action, phys, group, edges = inp.attrs, inp.action, inp.phys, inp.group, inp.edges
     L_max, B = errors.shape
     rule, cap = sp.connect_tool_all_non_fixed, max(1, sp.max_nR)
     cfg = ds._rule_config(sp.connect_tool_surface, 0)

@@ -23,8 +23,7 @@ import ctypes as C
 
 import torch
 
-from .autograd import _vp_array
-from .context import Engine, ptr, current_stream, _require_gpu
+from .context import Engine, ptr, current_stream, _require_gpu, _vp_array
 from .set_losses import LossSpec
 
 _ADAM_FIXED = {"amsgrad": False, "maximize": False}
@@ -190,11 +189,9 @@ class TrainStep:
         model, dev, eng = self.model, self.device, self.engine
         kw = {k: v for k, v in data.items() if k.endswith("_physics_param")}
         with torch.no_grad():
-            state = data["state"].to(device=dev, dtype=torch.float32).contiguous()
-            attrs, action, phys, group, edges, n_p = model._inputs(dev, state, data["attrs"], data.get("Rr"), data.get("Rs"),
-                                                                   data["p_instance"], data["action"], data.get("edges"), kw)
-            B, N = attrs.shape[:2]
-            assert state.shape == (B, model.n_his, N, 3)
+            inp = model._inputs(dev, data["state"], data["attrs"], data.get("Rr"), data.get("Rs"), data["p_instance"], data["action"],
+                                data.get("edges"), kw)
+            B, N, n_p, edges = inp.B, inp.N, inp.n_p, inp.edges
             nf = self.n_future
             fut = data["state_future"].to(device=dev, dtype=torch.float32)[:, :nf].contiguous()
             assert fut.shape == (B, nf, n_p, 3), tuple(fut.shape)
@@ -206,10 +203,9 @@ class TrainStep:
             if max_edges is None:
                 max_edges = int(edges.n_edges.max().item())                 # the one wait of the call
             pred = torch.empty((nf, B, n_p, 3), device=dev, dtype=torch.float32)
-        args = (eng.ctx, current_stream(dev), ptr(state), ptr(attrs), ptr(action), ptr(phys), ptr(group), group.shape[2],
-                ptr(edges.recv), ptr(edges.send), ptr(edges.row_ptr), ptr(edges.n_edges), edges.edge_cap, B, N, n_p, self._w_arr,
-                nf, ptr(fut), ptr(eef), ptr(act_f), int(self.store_rest_state), max(1, int(max_edges)), int(want_grad), self._g_arr,
-                ptr(self._loss), ptr(pred), ptr(self._status))
+        args = (eng.ctx, current_stream(dev), *inp.c_args(), self._w_arr, nf, ptr(fut), ptr(eef), ptr(act_f),
+                int(self.store_rest_state), max(1, int(max_edges)), int(want_grad), self._g_arr, ptr(self._loss), ptr(pred),
+                ptr(self._status))
         spec = () if self._spec is None else (C.byref(self._spec), ptr(self.last_loss_terms))
         if total is None:
             eng.check(eng.lib.ag_train_step_losses(*args, B, 0, *spec) if spec else eng.lib.ag_train_step(*args))

@@ -317,8 +317,8 @@ def test_eval_step_enqueues_and_the_rollout_waits_once_per_step(dev):
     aux, eng, sp = ds._last_build, model.engine(dev), ds.spec
     B, N = len(fx["samples"]), ds.N
     kw = {k: v for k, v in data.items() if k.endswith("_physics_param")}
-    attrs, action, phys, group, edges, _ = model._inputs(dev, data["state"], data["attrs"], None, None, data["p_instance"], data["action"],
-                                                         data["edges"], kw)
+    inp = model._inputs(dev, data["state"], data["attrs"], None, None, data["p_instance"], data["action"], data["edges"], kw)
+    attrs, action, phys, group, edges = inp.attrs, inp.action, inp.phys, inp.group, inp.edges
     tab = torch.tensor([[0, 0, ds.n_eef]] * B, dtype=torch.int64, device=dev)
     f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
     out = dict(pred=torch.empty((B, sp.max_nobj, 3), **f32), err=torch.empty((B,), **f32), state=torch.empty_like(data["state"]),

@@ -219,6 +219,53 @@ def test_forward_vs_oracle_pstep4(ag, dev):
     assert np.abs(mot.cpu().numpy() - want_mot).max() <= POS_TOL
 
 
+def test_forward_entries_agree_bitwise(ag, dev):
+    """forward() without and with autograd and forward_diff() marshal their inputs through one builder: the same bits from all
+    three, from dense Rr / Rs with a (B,1) parameter and from a pre-built EdgeList with the (B,n_p) parameter.  The smallest graph
+    with every case (tests/test_marshal.py): 5 object + 2 tool rows, 4 edges out of receiver order, a padding row, receivers of degree 0."""
+    from oracle import adaptigraph_oracle as O
+    rng = np.random.default_rng(12)
+    W = O.random_weights(12)
+    m = ag.DynamicsPredictor(*_cfg("rope", 3), dev)
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in W.items()})
+    B, n_p, N = 2, 5, 7
+    given = [[(5, 0), (1, 2), (5, 6), (0, 1)], [(6, 3), (2, 4), (2, 0), (3, 6)]]            # (receiver, sender)
+    Rr, Rs = torch.zeros((B, 5, N)), torch.zeros((B, 5, N))
+    for b, es in enumerate(given):
+        for row, (r, s) in zip((0, 1, 3, 4), es):                                           # row 2 stays zero: padding
+            Rr[b, row, r] = Rs[b, row, s] = 1
+    recv = np.array([[0, 1, 5, 5], [2, 2, 3, 6]], np.int32)                                 # the same edges, by receiver
+    send = np.array([[1, 2, 0, 6], [4, 0, 6, 3]], np.int32)
+    row_ptr = np.array([[0, 1, 2, 2, 2, 2, 4, 4], [0, 0, 0, 2, 3, 3, 3, 4]], np.int32)
+    t = lambda a: torch.from_numpy(a).to(dev)   # noqa: E731
+    el = ag.EdgeList(t(recv), t(send), t(row_ptr), torch.full((B,), 4, dtype=torch.int32, device=dev), N)
+    state = rng.normal(0, 0.3, (B, 4, N, 3)).astype(np.float32)
+    attrs = np.zeros((B, N, 2), np.float32)
+    attrs[:, :n_p, 0] = attrs[:, n_p:, 1] = 1
+    action = np.zeros((B, N, 3), np.float32)
+    action[:, n_p:] = rng.normal(0, 0.05, (B, N - n_p, 3))
+    p_inst = (rng.random((B, n_p, 3)) < 0.5).astype(np.float32)
+    phys = rng.uniform(0.1, 0.9, (B, 1)).astype(np.float32)
+    kw = dict(state=t(state), attrs=t(attrs), p_instance=t(p_inst), action=t(action))
+    forms = [dict(Rr=Rr.to(dev), Rs=Rs.to(dev), rope_physics_param=t(phys)),
+             dict(edges=el, rope_physics_param=t(np.repeat(phys, n_p, 1)))]
+    outs = []
+    for form in forms:
+        with torch.no_grad():
+            outs.append(m(**kw, **form))
+        m.train()
+        outs.append(m(**kw, **form))
+        assert outs[-1][0].requires_grad
+        m.eval()
+        outs.append(m.forward_diff(**dict(kw, action=t(action).requires_grad_(True)), **form))
+        assert outs[-1][0].requires_grad
+    for pos, mot in outs[1:]:
+        assert torch.equal(pos.detach(), outs[0][0]) and torch.equal(mot.detach(), outs[0][1])
+    want_pos, want_mot = O.model_forward(W, state, attrs, [(recv[b], send[b]) for b in range(B)], p_inst, action, phys, 3)
+    assert np.abs(outs[0][0].cpu().numpy() - want_pos).max() <= POS_TOL
+    assert np.abs(outs[0][1].cpu().numpy() - want_mot).max() <= POS_TOL
+
+
 # ------------------------------------------------------------------------------------------------- rollout
 @pytest.mark.parametrize("name,material", [("dyn_rope", "rope"), ("dyn_granular", "granular"), ("dyn_cloth", "cloth")])
 def test_dynamics_vs_reference_golden(ag, dev, name, material):

@@ -40,7 +40,7 @@ AG_LOSS_MSE, AG_LOSS_CHAMFER, AG_LOSS_HAUSDORFF = 0, 1, 2
 
 OPTIONS = ["streams", "chunk", "latency", "ragged", "ell_graph", "self_dedupe", "repeat_sort", "edge_wgs", "edge_block_min",
            "enc_persist", "stagger_us", "device_decode", "zigzag", "share_first", "share_prefix", "stream_min_rows", "pipeline_fork", "zero_skip",
-           "edge_order", "ell_lds_words"]
+           "edge_order", "ell_lds_words", "half_step"]
 
 
 class AgDims(C.Structure):

@@ -28,6 +28,7 @@ const OptName kOptions[] = {
     {"zigzag", "AG_ZIGZAG", &Options::zigzag, false, 0, 1},
     {"share_first", "AG_SHARE_FIRST", &Options::share_first, false, -1, 1},
     {"zero_skip", "AG_ZERO_SKIP", &Options::zero_skip, false, 0, 1},
+    {"half_step", "AG_HALF_STEP", &Options::half_step, false, 0, 1},
     {"share_prefix", "AG_SHARE_PREFIX", &Options::share_prefix, false, -1, 1},
     {"stream_min_rows", "AG_STREAM_MIN_ROWS", &Options::stream_min_rows, false, 0, 0x7fffffff},
     {"pipeline_fork", "AG_PIPELINE_FORK", &Options::pipeline_fork, false, 0, 1},
@@ -151,7 +152,7 @@ void carve_work(const ag_ctx* c, Slab& s, Work& w, int Bc, int N, int n_inst, in
     w.g.C = s.take<float>(((size_t)Bc * c_cap + 256) * NFP);   // + room for the two self-loop constant rows
     w.g.B = Bc; w.g.N = N; w.g.n_inst = n_inst; w.g.edge_cap = edge_cap; w.g.c_cap = c_cap; w.g.n_p = N_o;
     w.g.enc_persist = c->opt.enc_persist; w.g.stagger_us = c->opt.stagger_us; w.g.zigzag = c->opt.zigzag; w.g.diag = c->diag;
-    w.g.zero_skip = c->opt.zero_skip && c->w_finite;
+    w.g.zero_skip = c->opt.zero_skip && c->w_finite; w.g.half_step = w.g.zero_skip && c->opt.half_step;
     if (own_edges) {
         w.ell = s.take<int>(rows * (size_t)std::max(1, ell_stride));
         w.deg = s.take<int>(rows);

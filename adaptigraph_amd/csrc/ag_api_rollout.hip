@@ -433,7 +433,7 @@ int build_shared_base_graph(RollCall& r) {
     gb.node_in = b.node_in; gb.feat12 = b.feat; gb.group = b.group; gb.C = b.C; gb.recv = b.recv; gb.send = b.send;
     gb.n_edges = b.n_edges; gb.ns_edge = b.ns; gb.n_ns = b.n_ns; gb.B = 1; gb.N = p->N_o; gb.n_p = p->N_o; gb.n_inst = 1;
     gb.edge_cap = base_cap; gb.c_cap = base_cap; gb.n_his = r.n_his; gb.wb3 = c->precision == 1 ? c->d_wb3 : nullptr;
-    gb.diag = c->diag; gb.zero_skip = c->opt.zero_skip && c->w_finite;
+    gb.diag = c->diag; gb.zero_skip = c->opt.zero_skip && c->w_finite; gb.half_step = gb.zero_skip && c->opt.half_step;
     int rc = run_edge_chain(c, gb, st);
     if (rc) return rc;
     r.base_send = b.send; r.base_deg = b.deg; r.C_share = b.C; c->d_share_nns = b.n_ns;

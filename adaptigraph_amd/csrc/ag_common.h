@@ -102,6 +102,13 @@ struct Options {
                               //                     zero in all 32 rows of a wavefront is branched over (ag_mlp.hip: mma_act).  Exact for
                               //                     finite weights; a weight upload that holds a non-finite value turns it off for that
                               //                     model (0 * inf must stay NaN), and so does a device-side upload, which no host code sees
+    int half_step = 1;        // [AG_HALF_STEP]      where zero_skip runs: a k-step with exactly ONE of its two input features zero in all 32
+                              //                     rows takes 3 MFMAs instead of 5 - tiles (0,1) and (2,3) one two-block
+                              //                     v_mfma_f32_32x32x1_2b_f32 each over the live feature alone (ag_mlp.hip: mma_act).  Same
+                              //                     bits: the dropped term is fma(w, 0, acc) with finite w.  No effect where zero_skip is off.
+                              //                     0 does not bring back the 5-MFMA step: a step with both features live is two two-block
+                              //                     MFMAs per tile pair either way (same bits); only a build with -DAG_HS_EDGE=0
+                              //                     -DAG_HS_NODE=0 has the former code
     int edge_order = 1;       // [AG_EDGE_ORDER]     order of the relation encoder's work list (k_ell_index): 0 = slot order (receiver-major),
                               //                     1 = class-major - object-object slots by the signs and the dominant axis of
                               //                     pos_r - pos_s (24 classes), then every slot with a tool at either end, slot order inside
@@ -268,6 +275,7 @@ struct GraphBufs {
     int n_his;                             // 4 (0 = 4), or 5 on the forward path (feature rows then have pitch F15_PITCH)
     int enc_persist, stagger_us, zigzag;   // Options of the owning context
     int zero_skip;                         // Options::zero_skip, and the loaded weights are known to be finite (ag_ctx::w_finite)
+    int half_step;                         // Options::half_step, and zero_skip above is 1
     void* diag;                            // diagnostic build (-DAG_DIAG, ag_diag.hip) only: the context's probe state, else null
 };
 constexpr int B3_PHASE_BYTES = 2 * 5 * 3 * 64 * 16;   // 30,720

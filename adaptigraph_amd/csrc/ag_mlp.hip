@@ -33,6 +33,7 @@ void diag_node_end(void* diag, unsigned nwg, int round, hipStream_t st);
 #endif
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x32 __attribute__((ext_vector_type(32)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int WG = 256;                     // 4 wavefronts, one per SIMD; two workgroups share a CU
@@ -61,14 +62,14 @@ struct Act { f32x16 t[5]; };
 // flagship batch.  The relation-encoder chain has it per tile, on the class-major work list (Options::edge_order, k_ell_index): in
 // slot order 8 % of its k-steps are dead and the mask, branches and waits cost 6 % where nothing is dead (+1.7 % per launch); with
 // the wavefronts holding edges of one direction class 21 % are dead and the chain is 10 % faster per launch (1.489 -> 1.340 ms),
-// the rollout 4.2 %.  AG_ZS_EDGE: 0 = no skip (the chain's code is then the pre-skip one, instruction for instruction), 1 (shipped)
-// = the tiles that start among the object-object classes of a class-major list (GDev::n_oo), 2 = every tile (experiment build;
-// measured equal to 1).  k_node_enc is built like the relation-encoder chain and is not on the flagship path (the class table goes
+// the rollout 4.2 %.  AG_ZS_EDGE: 0 = no skip (the chain's code is then the pre-skip one, instruction for instruction), 1 = only the
+// tiles that start among the object-object classes of a class-major list (GDev::n_oo), 2 (shipped) = every tile: equal to 1 for the
+// plain skip, 1.1 % faster per launch with half-steps (the tool tiles are 28-48 % half-dead, docs/EXPERIMENTS.md).  k_node_enc is built like the relation-encoder chain and is not on the flagship path (the class table goes
 // through the latency-mode chain); unmeasured, so it stays as it was.
 // docs/EXPERIMENTS.md, "Zero skip in the fp32 chains" and "Class-major work list".  -DAG_ZS_EDGE=0|2 / -DAG_ZS_ENC=1 / -DAG_ZS_NODE=0:
 // experiment builds.
 #ifndef AG_ZS_EDGE
-#define AG_ZS_EDGE 1
+#define AG_ZS_EDGE 2
 #endif
 #ifndef AG_ZS_ENC
 #define AG_ZS_ENC 0
@@ -77,6 +78,15 @@ struct Act { f32x16 t[5]; };
 #define AG_ZS_NODE 1
 #endif
 constexpr bool ZS_EDGE = AG_ZS_EDGE != 0, ZS_EDGE_ALL = AG_ZS_EDGE == 2, ZS_ENC = AG_ZS_ENC != 0, ZS_NODE = AG_ZS_NODE != 0;
+// Half-steps (mma_act) per chain, fixed at build time like the skip they extend; 0 = the chain's code is the one without them,
+// instruction for instruction.  docs/EXPERIMENTS.md, "Half-dead k-steps at K = 1".  -DAG_HS_EDGE=0 / -DAG_HS_NODE=0: experiment builds.
+#ifndef AG_HS_EDGE
+#define AG_HS_EDGE 1
+#endif
+#ifndef AG_HS_NODE
+#define AG_HS_NODE 1
+#endif
+constexpr bool HS_EDGE = ZS_EDGE && AG_HS_EDGE != 0, HS_NODE = ZS_NODE && AG_HS_NODE != 0;
 
 // ------------------------------------------------------------------------------------------------ staging
 // global -> LDS DMA (global_load_lds, 16 B per lane): NFLOATS (a multiple of 256) in 1-KB pieces, each wave-instruction
@@ -110,9 +120,36 @@ __device__ __forceinline__ void dma_copy(float* lds_dst, const float* __restrict
 // two input features are exactly zero in all 32 rows of the wavefront adds 0*w + 0*w' to every accumulator - nothing, for
 // finite weights - so its MB MFMAs are branched over; a chunk of four such steps also leaves out its weight-fragment reads.
 // Only MFMAs and ds_reads sit under the branches: every DMA, barrier and store is executed by every wavefront as before.
-struct Live { unsigned m[3]; };                                   // bit s & 31 of m[s >> 5]: k-step s has a non-zero input
-template <int Q0, int Q1, int MB, bool SKIP>
-__device__ __forceinline__ void mma_act(const float* wl, const Act& in, f32x16* acc, int lane, const Live& lv) {
+//
+// Half-steps (Options::half_step, HS): a k-step carries feature `lo` on lanes 0-31 and `lo + 4` on lanes 32-63, and about half of all
+// steps have exactly ONE of the two all zero.  Such a step issues 3 MFMAs instead of 5: tiles (0,1) and (2,3) take one
+// v_mfma_f32_32x32x1_2b_f32 each - one k, two independent 32 x 32 blocks, block b = accumulator registers 16b .. 16b+15 with the
+// lane map of the 32x32x2 form, the same 16 passes - and tile 4 the ordinary MFMA (its dead half adds w * 0).  The A operand needs no
+// second weight image: a[2m][e] is [W(tile 2m, lo) | W(tile 2m, lo+4)] on its lane halves, and ONE v_permlane32_swap with
+// a[2m+1][e] leaves [W(2m, lo) | W(2m+1, lo)] in the first and [W(2m, lo+4) | W(2m+1, lo+4)] in the second register (in place: a
+// step's fragments are used by that step only).  The B operand is the step's own activation register, its live half broadcast to
+// both blocks by the MFMA's blgp modifier (1: lanes 0-31, 2: lanes 32-63).  Bits: an f32 MFMA is a k-ordered fmaf chain, so the full
+// step computes fma(w', x', fma(w, x, acc)) and the half-step the same with the fma whose x is zero left out - the identity for
+// finite w (and the same sign-of-an-exact-zero caveat on the seeded accumulator as the skip).  tools/probes/mfma_half_step.hip
+// checks the bits and times it: 0.67-0.69 of a full step.
+struct Live {
+    unsigned m[3];                                                // bit s & 31 of m[s >> 5]: k-step s has a non-zero input
+    unsigned lo[3], hi[3];                                        // HS only: ... on lanes 0-31 / on lanes 32-63 (m = lo | hi)
+};
+__device__ __forceinline__ f32x32 cat32(f32x16 a, f32x16 b) {
+    return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27,
+                                   28, 29, 30, 31);
+}
+__device__ __forceinline__ f32x16 lo16(f32x32 c) { return __builtin_shufflevector(c, c, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15); }
+__device__ __forceinline__ f32x16 hi16(f32x32 c) {
+    return __builtin_shufflevector(c, c, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31);
+}
+// HS: tiles (0,1) and (2,3) are accumulated in `pr`, 32 contiguous registers each, and acc[0..3] are not touched (layer160 moves
+// them in and out once per layer): with 16-register values on one path and 32-register ones on the other, the copies that join
+// them stay in the sweeps.
+template <int Q0, int Q1, int MB, bool SKIP, bool HS = false>
+__device__ __forceinline__ void mma_act(const float* wl, const Act& in, f32x16* acc, int lane, const Live& lv, f32x32* pr = nullptr) {
+    static_assert(!HS || (SKIP && MB == 5), "half-steps extend the skip of the 160-wide layers");
 #pragma unroll
     for (int q = Q0; q < Q1; ++q) {
         const unsigned nib = SKIP ? (lv.m[(4 * q) >> 5] >> ((4 * q) & 31)) & 15u : 15u;   // a chunk never straddles a word
@@ -133,7 +170,29 @@ __device__ __forceinline__ void mma_act(const float* wl, const Act& in, f32x16* 
                 const int t = s < 64 ? s / 16 : 4;
                 const int r = s < 64 ? s % 16 : s - 64;
                 const float b = in.t[t][r];
-                if (__builtin_expect((nib & (1u << e)) != 0u, 1)) {
+                if (HS) {
+                    // tiles (0,1) and (2,3): one two-block MFMA per live half, in K order (lo, then lo + 4: the fmaf chain of the
+                    // 32x32x2 form); tile 4: the ordinary MFMA, whose dead half adds w * 0.  Both live = 5 MFMAs' worth of passes.
+                    const bool l = (lv.lo[s >> 5] >> (s & 31)) & 1u, h = (lv.hi[s >> 5] >> (s & 31)) & 1u;
+                    if (__builtin_expect(l || h, 1)) {
+                        float w[2][2];
+#pragma unroll
+                        for (int m = 0; m < 2; ++m) {
+                            const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(a[2 * m][e]), __float_as_uint(a[2 * m + 1][e]),
+                                                                             false, false);
+                            w[m][0] = __uint_as_float(sw[0]); w[m][1] = __uint_as_float(sw[1]);
+                        }
+                        if (l) {
+#pragma unroll
+                            for (int m = 0; m < 2; ++m) pr[m] = __builtin_amdgcn_mfma_f32_32x32x1f32(w[m][0], b, pr[m], 0, 0, 1);
+                        }
+                        if (h) {
+#pragma unroll
+                            for (int m = 0; m < 2; ++m) pr[m] = __builtin_amdgcn_mfma_f32_32x32x1f32(w[m][1], b, pr[m], 0, 0, 2);
+                        }
+                        acc[4] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4][e], b, acc[4], 0, 0, 0);
+                    }
+                } else if (__builtin_expect((nib & (1u << e)) != 0u, 1)) {
 #pragma unroll
                     for (int mb = 0; mb < MB; ++mb)
                         acc[mb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mb][e], b, acc[mb], 0, 0, 0);
@@ -192,16 +251,31 @@ __device__ __forceinline__ void relu_one(Act& a, int lane) {   // ReLU, then for
 // Live mask of the 76 k-steps of `a` as the input of a 160-wide layer: step s (register (t, r), both lane halves = its two
 // features) is live iff any of the 64 lanes holds a non-zero.  NaN and inf count as non-zero.  Slot 150 is 1.0 after relu_one,
 // so its step (74) comes out live without being named here.  `on` == 0 (option off, or non-finite weights): every step live.
-__device__ __forceinline__ Live live_of(const Act& a, int on) {
-    Live lv = {{~0u, ~0u, ~0u}};
+// HS (half-steps, mma_act): also one mask per lane half - the two words of the same ballot.  `half` == 0 (Options::half_step off):
+// both say what `m` says, so that a step is full or skipped as without them.
+template <bool HS = false>
+__device__ __forceinline__ Live live_of(const Act& a, int on, int half = 0) {
+    Live lv = {{~0u, ~0u, ~0u}, {~0u, ~0u, ~0u}, {~0u, ~0u, ~0u}};
     if (on) {
-        lv.m[0] = lv.m[1] = lv.m[2] = 0u;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) lv.m[i] = lv.lo[i] = lv.hi[i] = 0u;
 #pragma unroll
         for (int s = 0; s < 4 * KCH; ++s) {
             const int t = s < 64 ? s / 16 : 4;
             const int r = s < 64 ? s % 16 : s - 64;
-            const bool any = __builtin_amdgcn_ballot_w64(a.t[t][r] != 0.0f) != 0;
+            const unsigned long long bal = __builtin_amdgcn_ballot_w64(a.t[t][r] != 0.0f);
+            const bool any = bal != 0;
             lv.m[s >> 5] |= any ? 1u << (s & 31) : 0u;
+            if (HS) {
+                unsigned bh = (unsigned)(bal >> 32);
+                asm("" : "+s"(bh));                                // (else the test becomes a 64-bit compare, which only the VALU has)
+                lv.lo[s >> 5] |= (unsigned)bal != 0u ? 1u << (s & 31) : 0u;
+                lv.hi[s >> 5] |= bh != 0u ? 1u << (s & 31) : 0u;
+            }
+        }
+        if (HS && !half) {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) lv.lo[i] = lv.hi[i] = lv.m[i];
         }
     }
     return lv;
@@ -293,24 +367,28 @@ __device__ __forceinline__ void store_rows_t(const Act& a, float* __restrict__ b
 // PRE: the caller has already issued the DMA of quarter 1 into buffer 1 (it did so BEFORE a burst of row stores: waits
 // count vector-memory operations in issue order, so a DMA issued behind the stores could not be awaited without them).
 // SKIP: consult `lv`, the live mask of `in` (zero skip, see mma_act); else every k-step is issued and `lv` is not read.
-template <int NEXT, bool ZERO = true, bool PRE = false, bool SKIP = false>
+// HS: half-steps on top of the skip (mma_act); `lv` then carries the masks of the two lane halves as well.
+template <int NEXT, bool ZERO = true, bool PRE = false, bool SKIP = false, bool HS = false>
 __device__ __forceinline__ void layer160(float* lds, const float* __restrict__ w, const float* __restrict__ next,
                                          const Act& in, Act& out, int tid, int lane, const Live& lv = Live()) {
     float* b0 = lds;
     float* b1 = lds + BUF_FLOATS;
     if (ZERO) zero(out);                                     // else: accumulate on top of what `out` holds
+    f32x32 pr[2];
+    if (HS) { pr[0] = cat32(out.t[0], out.t[1]); pr[1] = cat32(out.t[2], out.t[3]); }
     // every sweep runs with the NEXT quarter's DMA in flight into the other buffer (free since the last barrier)
     if (!PRE) dma_copy<Q_FLOATS>(b1, w + Q_FLOATS, tid);
-    mma_act<0, QCH, 5, SKIP>(b0, in, out.t, lane, lv);
+    mma_act<0, QCH, 5, SKIP, HS>(b0, in, out.t, lane, lv, pr);
     __syncthreads();
     dma_copy<Q_FLOATS>(b0, w + 2 * Q_FLOATS, tid);
-    mma_act<QCH, 2 * QCH, 5, SKIP>(b1, in, out.t, lane, lv);
+    mma_act<QCH, 2 * QCH, 5, SKIP, HS>(b1, in, out.t, lane, lv, pr);
     __syncthreads();
     dma_copy<Q3_FLOATS>(b1, w + 3 * Q_FLOATS, tid);
-    mma_act<2 * QCH, 3 * QCH, 5, SKIP>(b0, in, out.t, lane, lv);
+    mma_act<2 * QCH, 3 * QCH, 5, SKIP, HS>(b0, in, out.t, lane, lv, pr);
     __syncthreads();
     if (NEXT > 0) dma_copy<(NEXT > 0 ? NEXT : 256)>(b0, next, tid);
-    mma_act<3 * QCH, KCH, 5, SKIP>(b1, in, out.t, lane, lv);
+    mma_act<3 * QCH, KCH, 5, SKIP, HS>(b1, in, out.t, lane, lv, pr);
+    if (HS) { out.t[0] = lo16(pr[0]); out.t[1] = hi16(pr[0]); out.t[2] = lo16(pr[1]); out.t[3] = hi16(pr[1]); }
     if (NEXT > 0) __syncthreads();
 }
 
@@ -348,6 +426,7 @@ struct GDev {
     const float* C_share; unsigned share_kb;
     int f_pitch, cur_off;                     // feature-row pitch and offset of the current position in it (n_his 4: 12, 9)
     int zero_skip;                            // Options::zero_skip and finite weights: the 160-wide layers branch over all-zero k-steps
+    int half_step;                            // Options::half_step and zero_skip: a k-step with one all-zero feature takes 3 MFMAs (mma_act)
 #ifdef AG_DIAG
     unsigned long long* dbg;   // diagnostic build (ag_diag.hip) only: stamps per workgroup, never read by kernels
 #endif
@@ -630,9 +709,10 @@ __global__ __launch_bounds__(WG, 2) void k_edge_enc(GDev g) {
     const int e0 = (int)(blk / (unsigned)g.B) * WG_ROWS;
     const int ne = g.n_ns ? g.n_ns[b] : g.n_edges[b];       // rows to encode: all edges, or the non-self-loop ones
     if (e0 >= ne) continue;                                  // whole workgroup past this candidate's edges
-    // Zero skip per tile (AG_ZS_EDGE, top of the file).  Gated: only the tiles that start inside the object-object classes of a
-    // class-major list (GDev::n_oo; null = slot order: never) - a tile that starts at or past n_oo[b] holds tool edges only, whose
-    // wavefronts are mixed (7 % dead k-steps against 20 %): its mask is not built, every k-step counts as live.
+    // Zero skip per tile (AG_ZS_EDGE, top of the file).  Shipped (2): every tile builds its masks, whatever the order of the work
+    // list.  The gated build (1) does so only for the tiles that start inside the object-object classes of a class-major list
+    // (GDev::n_oo; null = slot order: never); a tile that starts at or past n_oo[b] holds tool edges only (7 % dead k-steps against
+    // 20 %, but 28-48 % half-dead), and there its mask is not built and every k-step counts as live on both halves.
     int skip = 0;
     if (ZS_EDGE) skip = g.zero_skip && (ZS_EDGE_ALL || (g.n_oo && e0 < g.n_oo[b])) ? 1 : 0;
 #ifdef AG_DIAG
@@ -676,13 +756,13 @@ __global__ __launch_bounds__(WG, 2) void k_edge_enc(GDev g) {
     mma_feat<EDGE_L1_CHUNKS, (RD + 2) / 2>(lds + BUF_FLOATS, f, y.t, lane);     // RD inputs + bias: 9 (n_his 4) / 11 steps of 12
     __syncthreads();
     relu_one(y, lane);
-    // (ZS_EDGE: one copy of the sweeps - a plain tile carries a full mask and pays the bit tests, not the ballots.  Two copies
+    // (ZS_EDGE: one copy of the sweeps - where `skip` is 0 a tile carries full masks and pays the bit tests, not the ballots.  Two copies
     // behind one branch were compiled and not run: 256 VGPRs and 152-192 B of scratch, docs/EXPERIMENTS.md)
-    layer160<Q_FLOATS, true, false, ZS_EDGE>(lds, wts + WL::E_L2, wts + WL::E_L3, y, x, tid, lane, live_of(y, skip));
+    layer160<Q_FLOATS, true, false, ZS_EDGE, HS_EDGE>(lds, wts + WL::E_L2, wts + WL::E_L3, y, x, tid, lane, live_of<HS_EDGE>(y, skip, g.half_step));
     relu_one(x, lane);
-    layer160<Q_FLOATS, true, false, ZS_EDGE>(lds, wts + WL::E_L3, wts + WL::E_W1, x, y, tid, lane, live_of(x, skip));
+    layer160<Q_FLOATS, true, false, ZS_EDGE, HS_EDGE>(lds, wts + WL::E_L3, wts + WL::E_W1, x, y, tid, lane, live_of<HS_EDGE>(x, skip, g.half_step));
     relu_one(y, lane);
-    layer160<0, true, false, ZS_EDGE>(lds, wts + WL::E_W1, nullptr, y, x, tid, lane, live_of(y, skip));
+    layer160<0, true, false, ZS_EDGE, HS_EDGE>(lds, wts + WL::E_W1, nullptr, y, x, tid, lane, live_of<HS_EDGE>(y, skip, g.half_step));
     store_rows_t(x, g.C, (int)((long)b * g.c_cap + el), valid, stg, lane);
 #ifdef AG_DIAG
     if (g.dbg && tid == 0) {
@@ -780,9 +860,10 @@ __global__ __launch_bounds__(WG, 2) void k_node_prop(GDev g) {
     __syncthreads();                                         // Wb quarter 0 is in buffer 0
     // (x = agg: sums of ReLU outputs.  The seeded accumulator is the one place where a skipped step can show: in the sign of an
     // exact zero, -0 + 0*w being +0.)
-    layer160<Q_FLOATS, false, false, ZS_NODE>(lds, g.w + WL::P_WB, g.w + (LAST ? WL::P_P0 : WL::N_W2), x, y, tid, lane, live_of(x, g.zero_skip));
+    layer160<Q_FLOATS, false, false, ZS_NODE, HS_NODE>(lds, g.w + WL::P_WB, g.w + (LAST ? WL::P_P0 : WL::N_W2), x, y, tid, lane,
+                                                       live_of<HS_NODE>(x, g.zero_skip, g.half_step));
     relu_one(y, lane);                                       // y = new particle effect (slot 150 forced to 1)
-    const Live lv = live_of(y, g.zero_skip);                 // the new effect feeds W2 and W3, or P0
+    const Live lv = live_of<HS_NODE>(y, g.zero_skip, g.half_step);   // the new effect feeds W2 and W3, or P0
 #ifdef AG_DIAG
     if (g.dbg && tid == 0) g.dbg[blockIdx.x * 4 + 2] = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -791,10 +872,10 @@ __global__ __launch_bounds__(WG, 2) void k_node_prop(GDev g) {
         // barrier leaves the stores in flight: they then have two quarter sweeps to drain instead of one
         dma_copy<Q_FLOATS>(lds + BUF_FLOATS, g.w + WL::N_W2 + Q_FLOATS, tid);
         store_rows_t(y, g.eff, (int)row, valid, stg, lane);
-        layer160<Q_FLOATS, true, true, ZS_NODE>(lds, g.w + WL::N_W2, g.w + WL::N_W3, y, x, tid, lane, lv);
+        layer160<Q_FLOATS, true, true, ZS_NODE, HS_NODE>(lds, g.w + WL::N_W2, g.w + WL::N_W3, y, x, tid, lane, lv);
         dma_copy<Q_FLOATS>(lds + BUF_FLOATS, g.w + WL::N_W3 + Q_FLOATS, tid);
         store_rows_t(x, g.U, (int)row, valid, stg, lane);
-        layer160<0, true, true, ZS_NODE>(lds, g.w + WL::N_W3, nullptr, y, x, tid, lane, lv);
+        layer160<0, true, true, ZS_NODE, HS_NODE>(lds, g.w + WL::N_W3, nullptr, y, x, tid, lane, lv);
         store_rows_t(x, g.V, (int)row, valid, stg, lane);
 #ifdef AG_DIAG
         if (g.dbg && tid == 0) {
@@ -803,9 +884,9 @@ __global__ __launch_bounds__(WG, 2) void k_node_prop(GDev g) {
         }
 #endif
     } else {
-        layer160<Q_FLOATS, true, false, ZS_NODE>(lds, g.w + WL::P_P0, g.w + WL::P_P1, y, x, tid, lane, lv);
+        layer160<Q_FLOATS, true, false, ZS_NODE, HS_NODE>(lds, g.w + WL::P_P0, g.w + WL::P_P1, y, x, tid, lane, lv);
         relu_one(x, lane);
-        layer160<OUT3_FLOATS, true, false, ZS_NODE>(lds, g.w + WL::P_P1, g.w + WL::P_P2, x, y, tid, lane, live_of(x, g.zero_skip));
+        layer160<OUT3_FLOATS, true, false, ZS_NODE, HS_NODE>(lds, g.w + WL::P_P1, g.w + WL::P_P2, x, y, tid, lane, live_of<HS_NODE>(x, g.zero_skip, g.half_step));
         relu_one(y, lane);
         f32x16 m[1];
 #pragma unroll
@@ -1171,7 +1252,7 @@ static GDev to_dev(const float* w, const GraphBufs& g) {
     d.rowlist = g.rowlist; d.n_rows = g.n_rows;
     d.C_share = nullptr; d.share_kb = 0;
     d.f_pitch = feat_pitch(g.n_his); d.cur_off = g.n_his == 5 ? 12 : 9;
-    d.zero_skip = g.zero_skip;
+    d.zero_skip = g.zero_skip; d.half_step = g.half_step;
     // Options::stagger_us: offset between the two workgroups of a CU in the fused propagate chains.  Off by default: it removes
     // the "both computing / both gathering" states (probe: 8 % -> 0 % of CU time) but the kernel time moves by <= 1 %
     // either way (two streams: 169 vs 171 ms per rollout with 30 us; four streams: 484.9 vs 482.9 ms per rollout without)

@@ -175,12 +175,18 @@ int ag_ctx_set_chunk(ag_ctx* ctx, int32_t candidates_per_chunk);
  *                                         model that holds an inf or NaN weight, ag_ctx_load_weights_device / ag_adam_step always
  *                                         (no host code sees those values).  ag_ctx_get_option "zero_skip_active" (read-only) = 1
  *                                         when the option is on and the guard has not turned it off
+ *   "half_step"      [AG_HALF_STEP]       1 (default): where "zero_skip" is active, a k-step with exactly one of its two input features
+ *                                         zero in all 32 rows of a wavefront issues 3 MFMAs instead of 5 (two two-block
+ *                                         v_mfma_f32_32x32x1_2b_f32 over the live feature, one ordinary MFMA).  Same bits; no effect
+ *                                         where "zero_skip_active" is 0.  0 does not restore the 5-MFMA step: a step with
+ *                                         both features live stays two two-block MFMAs per tile pair (same bits); only a build
+ *                                         with -DAG_HS_EDGE=0 -DAG_HS_NODE=0 has the former code
  *   "edge_order"     [AG_EDGE_ORDER]      order of the relation encoder's work list on the rollout's slot-indexed graphs: 0 = slot
  *                                         order (receiver-major); 1 (default) = class-major: the object-object slots by the sign bits
  *                                         and the dominant axis of pos_r - pos_s at the current frame (24 classes), then every slot
  *                                         with a tool particle at either end, slot order inside a class.  Wavefronts of the relation
  *                                         encoder then hold like edges, more of their k-steps are all zero, and with "zero_skip" the
- *                                         fp32 relation-encoder chain branches over them in the tiles of the object-object classes.
+ *                                         fp32 relation-encoder chain branches over them (in every tile, also with order 0).
  *                                         A C row is stored by slot and does not depend on the lane that computes it: same bits
  *   "ell_lds_words"  [AG_ELL_LDS_WORDS]   debug: LDS budget, in 64-bit words, of the class bitmaps of "edge_order" 1 (0 = the
  *                                         built-in 16384 = 128 KB).  A graph whose 25 bitmaps do not fit takes two classes

@@ -21,6 +21,13 @@ engine's class-major list: object-object edges by (d.x < 0, d.y < 0, d.z < 0) x 
 at the current frame (ties to the lower axis, a NaN compares false), the tool class last, slot order inside a class
 (work_list_order below is the numpy restatement of that key).  The propagate chains do not depend on it.
 
+Behind that output (its format is a prefix of this tool's output) comes the census for Options::half_step: a k-step with exactly ONE
+of its two features zero in all rows of the wavefront takes 3 MFMAs (192 issue cycles) instead of 5 (320).  Per layer the shares of
+(wavefront, k-step) pairs that are dead / half-dead / live - for the relation encoder also over the tiles (128 rows) that start among
+the object-object classes and over the others, which is the gate of the engine's skip - and the mean MFMA issue cycles per k-step
+they stand for, with the skip alone and with half-steps.  The quarter barriers are modelled as the slowest of a workgroup's four
+wavefronts per quarter (k-steps 0-19, 20-39, 40-59, 60-75).
+
   python tools/zero_skip_census.py [--forwards 3] [--candidates 0,341,682,1023] [--order slot|tool-last|class] [--json out.json]
 """
 import argparse
@@ -62,6 +69,43 @@ def dead_share(act, first_row=0):
     np.logical_or.at(live, wave, step_live_row)
     chunk_live = live.reshape(n_wave, NSTEP // 4, 4).any(2)
     return int((~live).sum()), int((~chunk_live).sum()), live.size, chunk_live.size
+
+
+CYC_FULL, CYC_HALF = 320, 192                                 # 5 MFMAs of 64 cycles; 2 two-block MFMAs + 1
+
+
+def step_shares(act, first_row=0, tile_mask=None):
+    """act as for dead_share -> (dead, half-dead, live, wavefront x k-step pairs, issue cycles today, issue cycles with half-steps,
+    the same two with every quarter of a 4-wavefront workgroup taking as long as its slowest wavefront).  tile_mask(first row of
+    a 128-row tile) -> bool selects the tiles that are counted (None: all)."""
+    rows = act.shape[0]
+    a = np.zeros((rows, 160), bool)
+    a[:, :150] = act != 0
+    a[:, 150] = True
+    wave = (first_row + np.arange(rows)) // 32
+    wave -= wave[0]
+    n_wave = int(wave[-1]) + 1
+    lo = np.zeros((n_wave, NSTEP), bool)
+    hi = np.zeros((n_wave, NSTEP), bool)
+    np.logical_or.at(lo, wave, a[:, LO])
+    np.logical_or.at(hi, wave, a[:, LO + 4])
+    keep = np.ones(n_wave, bool)
+    if tile_mask is not None:
+        keep = np.asarray([bool(tile_mask((w // 4) * 128)) for w in range(n_wave)])
+    lo, hi = lo[keep], hi[keep]
+    n_live = lo.astype(int) + hi
+    dead, half, live = int((n_live == 0).sum()), int((n_live == 1).sum()), int((n_live == 2).sum())
+    cyc_now = np.where(n_live == 0, 0, CYC_FULL)
+    cyc_hs = np.where(n_live == 0, 0, np.where(n_live == 1, CYC_HALF, CYC_FULL))
+    bar = [0, 0]
+    wg = np.flatnonzero(keep) // 4
+    for i, cyc in enumerate((cyc_now, cyc_hs)):
+        for q0, q1 in ((0, 20), (20, 40), (40, 60), (60, 76)):
+            per_wave = cyc[:, q0:q1].sum(1)
+            for g in np.unique(wg):
+                sel = per_wave[wg == g]
+                bar[i] += int(sel.max()) * len(sel)
+    return dead, half, live, lo.size, int(cyc_now.sum()), int(cyc_hs.sum()), bar[0], bar[1]
 
 
 N_CLASSES = 25
@@ -162,6 +206,7 @@ def main():
     group = np.zeros((N, 1), F32); group[:N_o] = 1
     phys = np.zeros(N, F32); phys[:N_o] = 0.5
     tot = {}
+    half = {}
     per_forward = []
     for ci, (cand, recs) in enumerate(zip(picks, trace)):
         action = np.zeros((N, 3), F32); action[N_o:] = delta[ci, 0]
@@ -178,6 +223,15 @@ def main():
                 key = (chain, layer)
                 tot[key] = tuple(x + y for x, y in zip(tot.get(key, (0, 0, 0, 0)), d))
                 row[f"{chain}.{layer}"] = round(d[0] / d[2], 4)
+                scopes = [("all tiles", None)]
+                if chain == "edge":
+                    ns_i = np.flatnonzero(rec["recv"] != rec["send"])
+                    n_oo = work_list_order(rec["recv"][ns_i], rec["send"][ns_i], hist[-1], N_o, args.order)[1]
+                    scopes += [("object-object tiles", lambda e0: e0 < n_oo), ("tool tiles", lambda e0: e0 >= n_oo)]
+                for scope, mask in scopes:
+                    h = step_shares(act, 0 if chain == "edge" else cand * N, mask)
+                    hk = (chain, layer, scope)
+                    half[hk] = tuple(x + y for x, y in zip(half.get(hk, (0,) * 8), h))
             per_forward.append(row)
     print(f"zero-skip census: bench batch, candidates {picks}, forwards 1..{args.forwards} of look-ahead step 0, "
           f"work list in {args.order} order")
@@ -195,6 +249,19 @@ def main():
         out[f"{chain}_dead_steps"] = ds / ns_
     for row in per_forward:
         print(json.dumps(row))
+    print("half-step census: share of (wavefront, k-step) pairs, and mean MFMA issue cycles per k-step "
+          f"(dead 0, half-dead {CYC_FULL} today / {CYC_HALF} as a half-step, live {CYC_FULL})")
+    print(f"{'chain':10s} {'layer':6s} {'tiles':20s} {'dead':>7s} {'half':>7s} {'live':>7s} {'cyc now':>8s} {'cyc half':>9s} "
+          f"{'now, barriers':>14s} {'half, barriers':>15s}")
+    out["half_step"] = []
+    for (chain, layer, scope), (de, ha, li, n, c0, c1, b0, b1) in half.items():
+        if n == 0:
+            continue
+        print(f"{chain:10s} {layer:6s} {scope:20s} {100 * de / n:6.2f}% {100 * ha / n:6.2f}% {100 * li / n:6.2f}% {c0 / n:8.1f} {c1 / n:9.1f} "
+              f"{b0 / n:14.1f} {b1 / n:15.1f}")
+        out["half_step"].append({"chain": chain, "layer": layer, "tiles": scope, "dead": de / n, "half": ha / n, "live": li / n,
+                                 "pairs": n, "cycles_now": c0 / n, "cycles_half_step": c1 / n, "cycles_now_barriers": b0 / n,
+                                 "cycles_half_step_barriers": b1 / n})
     if args.json:
         with open(args.json, "w") as f:
             json.dump(out, f, indent=1)

@@ -36,7 +36,8 @@ EXPORTS = ["ag_abi_version", "ag_ctx_create", "ag_ctx_destroy", "ag_last_error",
            "ag_edges_nonfixed_rule_graphs", "ag_edges_surface_rule_graphs",
            "ag_set_loss", "ag_set_loss_backward", "ag_train_step_losses", "ag_fps_cloud"]
 
-AG_LOSS_MSE, AG_LOSS_CHAMFER, AG_LOSS_HAUSDORFF = 0, 1, 2
+AG_LOSS_MSE, AG_LOSS_CHAMFER, AG_LOSS_HAUSDORFF, AG_LOSS_EMD = 0, 1, 2, 3
+EMD_MAX_MATCH = 512             # min(N, M) the Earth-mover loss serves (ag_common.h)
 
 OPTIONS = ["streams", "chunk", "latency", "ragged", "ell_graph", "self_dedupe", "repeat_sort", "edge_wgs", "edge_block_min",
            "enc_persist", "stagger_us", "device_decode", "zigzag", "share_first", "share_prefix", "stream_min_rows", "pipeline_fork", "zero_skip",

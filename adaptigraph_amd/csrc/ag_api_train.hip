@@ -50,6 +50,8 @@ int train_step_impl(ag_ctx* c, void* stream, const float* d_state, const float* 
                     float* d_loss_terms);
 int set_loss_call(ag_ctx* c, void* stream, const float* d_x, const float* d_y, int B, int N, int M, int B_total, int kind,
                   float* d_out, int32_t* d_work, const float* d_grad_out, float* d_grad_x, bool backward);
+int emd_loss_call(ag_ctx* c, void* stream, const float* d_x, const float* d_y, int B, int N, int M, int B_total, float* d_out,
+                  int32_t* d_work, const float* d_grad_out, float* d_grad_x, bool backward);
 
 }  // namespace
 
@@ -183,12 +185,13 @@ int ag_train_step_losses(ag_ctx* c, void* stream, const float* d_state, const fl
     if (!c) return AG_ERR_INVALID;
     if (!spec) return fail(c, AG_ERR_INVALID, "ag_train_step_losses: null loss spec");
     if (spec->n_terms < 1 || spec->n_terms > 4) return fail(c, AG_ERR_INVALID, "ag_train_step_losses: %d loss terms (1..4)", spec->n_terms);
-    bool set_term = false;
+    bool set_term = false, emd_term = false;
     for (int k = 0; k < spec->n_terms; ++k) {
-        if (spec->kind[k] < AG_LOSS_MSE || spec->kind[k] > AG_LOSS_HAUSDORFF)
+        if (spec->kind[k] < AG_LOSS_MSE || spec->kind[k] > AG_LOSS_EMD)
             return fail(c, AG_ERR_INVALID, "ag_train_step_losses: term %d has unknown kind %d", k, spec->kind[k]);
         if (!std::isfinite(spec->weight[k])) return fail(c, AG_ERR_INVALID, "ag_train_step_losses: term %d has a non-finite weight", k);
-        set_term = set_term || spec->kind[k] != AG_LOSS_MSE;
+        set_term = set_term || spec->kind[k] == AG_LOSS_CHAMFER || spec->kind[k] == AG_LOSS_HAUSDORFF;
+        emd_term = emd_term || spec->kind[k] == AG_LOSS_EMD;
         if (spec->kind[k] == AG_LOSS_HAUSDORFF && (B_total != B || accumulate != 0))
             return fail(c, AG_ERR_UNSUPPORTED, "ag_train_step_losses: a Hausdorff term is a max over the whole batch and does not split "
                         "into parts (B=%d, B_total=%d, accumulate=%d)", B, B_total, accumulate);
@@ -198,6 +201,9 @@ int ag_train_step_losses(ag_ctx* c, void* stream, const float* d_state, const fl
     if (set_term && n_p >= 1 && 2 * (size_t)n_p > chamfer_max_points())
         return fail(c, AG_ERR_UNSUPPORTED, "ag_train_step_losses: 2 * n_p = %d exceeds the set-loss LDS tile (%zu points)", 2 * n_p,
                     chamfer_max_points());
+    if (emd_term && n_p >= 1 && (2 * (size_t)n_p > emd_max_points() || n_p > EMD_MAX_MATCH))
+        return fail(c, AG_ERR_UNSUPPORTED, "ag_train_step_losses: an Earth-mover term serves n_p <= %d and 2 * n_p <= %zu (the LDS tile), "
+                    "got n_p = %d", EMD_MAX_MATCH, emd_max_points(), n_p);
     return train_step_impl(c, stream, d_state, d_attrs, d_action, d_phys, d_group, n_inst, d_recv, d_send, d_row_ptr, d_n_edges,
                            edge_cap, B, N, n_p, d_w, n_future, d_state_future, d_eef_future, d_action_future, store_rest_state,
                            edge_rows, want_grad, d_grad_w, d_loss, d_pred, d_status, B_total, accumulate, spec, d_loss_terms);
@@ -262,17 +268,26 @@ int train_step_impl(ag_ctx* c, void* stream, const float* d_state, const float* 
     float* S = nullptr; float* A = nullptr; float* P = nullptr; float* motion = nullptr; double* part = nullptr;
     float* dpos = nullptr; float* D[2] = {nullptr, nullptr};
     // a loss list: which kernels a step needs, the weights per kind (terms of one kind share their passes)
-    bool has_mse = false, has_set = false;
-    double w_mse = 0.0; float w_ch = 0.f, w_hd = 0.f;
+    bool has_mse = false, has_set = false, has_emd = false;
+    double w_mse = 0.0; float w_ch = 0.f, w_hd = 0.f, w_em = 0.f;
     for (int k = 0; spec && k < spec->n_terms; ++k) {
         if (spec->kind[k] == AG_LOSS_MSE) { has_mse = true; w_mse += (double)spec->weight[k]; }
+        else if (spec->kind[k] == AG_LOSS_EMD) { has_emd = true; w_em += spec->weight[k]; }
         else { has_set = true; (spec->kind[k] == AG_LOSS_CHAMFER ? w_ch : w_hd) += spec->weight[k]; }
     }
     SetLossDev sd{};                                             // the set terms' clouds: prediction against state_future[:, fi]
     sd.x_bstride = (long)n_p * 3; sd.y_bstride = (long)n_future * n_p * 3; sd.B = B; sd.N = n_p; sd.M = n_p;
     int* nn_all = nullptr; int* win_all = nullptr; float* terms = d_loss_terms;
+    EmdDev ed{};                                                 // the Earth-mover term: the same clouds
+    ed.x_bstride = sd.x_bstride; ed.y_bstride = sd.y_bstride; ed.B = B; ed.N = n_p; ed.M = n_p;
+    int* match_all = nullptr; int* emd_status_all = nullptr;
     rc = carve_slab(c, *sl, [&](Slab& s) {
         f.carve(c, s);
+        if (has_emd) {
+            match_all = s.take<int>((size_t)n_future * B * n_p);     // every step's match table and status words wait for the backward
+            emd_status_all = s.take<int>((size_t)n_future * B);
+            ed.part = s.take<double>((size_t)B);
+        }
         if (has_set) {
             nn_all = s.take<int>((size_t)n_future * B * 2 * n_p);    // every step's arg-min tables and winners wait for the backward
             win_all = s.take<int>((size_t)n_future * 4);
@@ -317,6 +332,12 @@ int train_step_impl(ag_ctx* c, void* stream, const float* d_state, const float* 
                 HIPCHK(c, launch_set_nn(sd, st));
                 fl.set_part = sd.part; fl.set_idx = sd.pidx; fl.win = win_all + 4 * fi;
             }
+            if (has_emd) {
+                ed.x = pred; ed.y = d_state_future + (size_t)fi * n_p * 3;
+                ed.match = match_all + (size_t)fi * B * n_p; ed.status = emd_status_all + (size_t)fi * B;
+                HIPCHK(c, launch_emd_assign(ed, st));
+                fl.emd_part = ed.part;
+            }
             HIPCHK(c, launch_step_loss_final(fl, st));
         }
         if (fi + 1 < n_future)
@@ -345,6 +366,13 @@ int train_step_impl(ag_ctx* c, void* stream, const float* d_state, const float* 
                 sg.w_chamfer = w_ch; sg.w_hausdorff = w_hd; sg.B_total = B_total; sg.win = win_all + 4 * fi; sg.gx = dpos; sg.add = 1;
                 HIPCHK(c, launch_set_grad(sd, sg, st));
             }
+            if (has_emd) {                                          // after the other set terms, on the same stream: one writer at a time
+                ed.x = P + (size_t)fi * n_pred; ed.y = d_state_future + (size_t)fi * n_p * 3;
+                ed.match = match_all + (size_t)fi * B * n_p; ed.status = emd_status_all + (size_t)fi * B;
+                SetGradDev sg{};
+                sg.w_emd = w_em; sg.B_total = B_total; sg.gx = dpos; sg.add = 1;
+                HIPCHK(c, launch_emd_grad(ed, sg, st));
+            }
         }
         t.state = state_of(fi); t.action = action_of(fi);
         t.dstate = fi > 0 ? D[0] : nullptr;                          // step 0's input is data
@@ -357,6 +385,45 @@ int train_step_impl(ag_ctx* c, void* stream, const float* d_state, const float* 
     return AG_OK;
 }
 
+// set_loss_call for AG_LOSS_EMD (the arguments are checked there): the assignment solve and the finaliser, then - backward - the
+// gradient.  d_work (B*(N+M) + 4 int32, optional): the (B,N) match table, then B status words.  A backward that is given them
+// does not solve again (the gradient kernel clamps what it reads from the table).
+int emd_loss_call(ag_ctx* c, void* stream, const float* d_x, const float* d_y, int B, int N, int M, int B_total, float* d_out,
+                  int32_t* d_work, const float* d_grad_out, float* d_grad_x, bool backward) {
+    if ((size_t)N + (size_t)M > emd_max_points())
+        return fail(c, AG_ERR_UNSUPPORTED, "ag_set_loss: N+M=%d exceeds the Earth-mover LDS tile (%zu points)", N + M, emd_max_points());
+    if (std::min(N, M) > EMD_MAX_MATCH)
+        return fail(c, AG_ERR_UNSUPPORTED, "ag_set_loss: the Earth-mover loss matches min(N, M) = %d pairs, at most %d are served",
+                    std::min(N, M), EMD_MAX_MATCH);
+    SlotGuard call;
+    int rc = begin_call(c, stream, call);
+    if (rc) return rc;
+    hipStream_t st = call.st; CallSlot* sl = call.sl;
+    EmdDev ed{};
+    ed.x = d_x; ed.y = d_y; ed.x_bstride = (long)N * 3; ed.y_bstride = (long)M * 3; ed.B = B; ed.N = N; ed.M = M;
+    const bool given = backward && d_work;                       // the forward's table: no solve of our own
+    float* val = nullptr;
+    rc = carve_slab(c, *sl, [&](Slab& s) {
+        ed.match = d_work ? d_work : s.take<int>((size_t)B * N);
+        ed.status = d_work ? d_work + (size_t)B * N : s.take<int>((size_t)B);
+        if (!given) ed.part = s.take<double>((size_t)B);
+        val = d_out ? d_out : s.take<float>(1);
+    });
+    if (rc) return rc;
+    Scoped pr(c, FAM_COST);
+    if (!given) {
+        HIPCHK(c, launch_emd_assign(ed, st));
+        SetLossDev sd{};
+        sd.B = B; sd.N = N; sd.M = M;
+        HIPCHK(c, launch_set_final(sd, ed.part, B_total, AG_LOSS_EMD, val, nullptr, st));
+    }
+    if (!backward) return AG_OK;
+    SetGradDev sg{};
+    sg.gout = d_grad_out; sg.w_emd = 1.f; sg.B_total = B_total; sg.gx = d_grad_x; sg.add = 0;
+    HIPCHK(c, launch_emd_grad(ed, sg, st));
+    return AG_OK;
+}
+
 // ag_set_loss (backward false) and ag_set_loss_backward: the nearest-neighbour pass and the finaliser, then - backward - the
 // gradient.  d_work (B*(N+M) + 4 int32, optional): the arg-min tables and the Hausdorff winners.  The forward leaves them there;
 // a backward that is given them skips its own pass (the gradient kernel clamps what it reads from a table, so a stale buffer
@@ -366,7 +433,9 @@ int set_loss_call(ag_ctx* c, void* stream, const float* d_x, const float* d_y, i
     if (!c) return AG_ERR_INVALID;
     if (!d_x || !d_y || (!backward && !d_out)) return fail(c, AG_ERR_INVALID, "ag_set_loss: null pointer");
     if (B < 1 || N < 1 || M < 1 || B_total < B) return fail(c, AG_ERR_INVALID, "ag_set_loss: bad sizes B=%d N=%d M=%d B_total=%d", B, N, M, B_total);
-    if (kind != AG_LOSS_CHAMFER && kind != AG_LOSS_HAUSDORFF) return fail(c, AG_ERR_INVALID, "ag_set_loss: kind %d is no set loss", kind);
+    if (kind != AG_LOSS_CHAMFER && kind != AG_LOSS_HAUSDORFF && kind != AG_LOSS_EMD)
+        return fail(c, AG_ERR_INVALID, "ag_set_loss: kind %d is no set loss", kind);
+    if (kind == AG_LOSS_EMD) return emd_loss_call(c, stream, d_x, d_y, B, N, M, B_total, d_out, d_work, d_grad_out, d_grad_x, backward);
     if (kind == AG_LOSS_HAUSDORFF && B_total != B)
         return fail(c, AG_ERR_UNSUPPORTED, "ag_set_loss: the Hausdorff loss is a max over the whole batch and does not split into parts");
     if ((size_t)N + (size_t)M > chamfer_max_points())
@@ -390,7 +459,7 @@ int set_loss_call(ag_ctx* c, void* stream, const float* d_x, const float* d_y, i
     Scoped pr(c, FAM_COST);
     if (!given) {
         HIPCHK(c, launch_set_nn(sd, st));
-        HIPCHK(c, launch_set_final(sd, B_total, kind, val, win, st));
+        HIPCHK(c, launch_set_final(sd, nullptr, B_total, kind, val, win, st));
     }
     if (!backward) return AG_OK;
     SetGradDev sg{};

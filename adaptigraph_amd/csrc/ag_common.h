@@ -455,9 +455,24 @@ hipError_t launch_mse_part(const float* pred, const float* fut, int B, int n_p, 
 hipError_t launch_pred_grad_scaled(const float* pred, const float* fut, const float* dnext, int B, int N, int n_p, int n_his,
                                    int n_future, int fi, float mse_scale, float* dpos, hipStream_t st);
 
-// ---- set losses of the training side (ag_setloss.hip; ag_set_loss, ag_set_loss_backward, ag_train_step_losses): Chamfer and
-// Hausdorff over a batch of cloud pairs, reference src/dynamics/gnn/loss.py.  Kinds as AG_LOSS_* of the C-ABI.
-constexpr int SET_LOSS_MSE = 0, SET_LOSS_CHAMFER = 1, SET_LOSS_HAUSDORFF = 2;
+// ---- set losses of the training side (ag_setloss.hip, ag_emd.hip; ag_set_loss, ag_set_loss_backward, ag_train_step_losses):
+// Chamfer, Hausdorff and Earth-mover over a batch of cloud pairs, reference src/dynamics/gnn/loss.py.  Kinds as AG_LOSS_* of the
+// C-ABI.
+constexpr int SET_LOSS_MSE = 0, SET_LOSS_CHAMFER = 1, SET_LOSS_HAUSDORFF = 2, SET_LOSS_EMD = 3;
+// what the set-loss kernels of both files share: the fp32 distance, every operation rounded on its own
+__device__ __forceinline__ float set_dist(float ax, float ay, float az, float bx, float by, float bz) {
+    const float dx = __fsub_rn(ax, bx), dy = __fsub_rn(ay, by), dz = __fsub_rn(az, bz);
+    return __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
+}
+// g += s * d||x_i - y_j|| / dx_i; zero at zero distance
+__device__ __forceinline__ void set_pull(const float* xi, const float* yj, float s, float (&g)[3]) {
+    const float dx = __fsub_rn(xi[0], yj[0]), dy = __fsub_rn(xi[1], yj[1]), dz = __fsub_rn(xi[2], yj[2]);
+    const float dist = __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
+    if (!(dist > 0.f)) return;
+    const float q = s / dist;
+    g[0] += dx * q; g[1] += dy * q; g[2] += dz * q;
+}
+__device__ __forceinline__ int clampi(int v, int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }   // a table is never trusted as an address
 struct SetLossDev {
     const float* x; const float* y;     // graph b's clouds start at x + b * x_bstride (N,3) and y + b * y_bstride (M,3)
     long x_bstride, y_bstride;
@@ -468,14 +483,16 @@ struct SetLossDev {
 struct SetGradDev {
     const float* gout;                  // device scalar dLoss/dout, or null (= 1)
     float w_chamfer, w_hausdorff;       // the terms' weights (0: term absent)
-    int B_total;                        // rows of the whole optimiser step: the Chamfer means' denominator
+    float w_emd;                        // the Earth-mover term's weight (k_emd_grad; k_set_grad does not read it)
+    int B_total;                        // rows of the whole optimiser step: the means' denominator
     const int* win;                     // the finaliser's Hausdorff winners {b, i, b, j} (read only with w_hausdorff != 0)
     float* gx; int add;                 // (B,N,3): overwritten, or added to (every element has one writer)
 };
 struct StepLossDev {                    // closes step fi of a chained training step with a loss list
     int n_terms, kind[4]; float weight[4];
     const double* mse_part; int n_mse_part; long mse_n;   // k_mse_part's partial sums and B_total * n_p * 3; null: no MSE term
-    const double* set_part; const int* set_idx;           // k_set_nn's partials; null: no set term
+    const double* set_part; const int* set_idx;           // k_set_nn's partials; null: no Chamfer / Hausdorff term
+    const double* emd_part;                               // k_emd_assign's partials (B); null: no Earth-mover term
     int B, n_p, B_total, fi, n_future, accumulate;
     float* loss; float* terms;          // (n_future + 1), (n_future, n_terms)
     int* win;                           // 4 ints of this step
@@ -483,9 +500,25 @@ struct StepLossDev {                    // closes step fi of a chained training 
 size_t set_loss_part_doubles(int B);
 size_t set_loss_part_ints(int B);
 hipError_t launch_set_nn(const SetLossDev& a, hipStream_t st);
-hipError_t launch_set_final(const SetLossDev& a, int B_total, int kind, float* out, int* win, hipStream_t st);
+// kind SET_LOSS_EMD reads emd_part (B doubles of k_emd_assign) and neither a.part, a.pidx nor win
+hipError_t launch_set_final(const SetLossDev& a, const double* emd_part, int B_total, int kind, float* out, int* win, hipStream_t st);
 hipError_t launch_step_loss_final(const StepLossDev& a, hipStream_t st);
 hipError_t launch_set_grad(const SetLossDev& a, const SetGradDev& g, hipStream_t st);
+
+// Earth-mover loss (ag_emd.hip; reference loss.py:25-60): the exact one-to-one matching of min(N, M) pairs per graph.
+constexpr int EMD_MAX_MATCH = 512;      // K = min(N, M) served: the serial search steps of one graph are at most K (K + 1) / 2
+constexpr int EMD_OK = 0, EMD_NONFINITE = 1, EMD_EXHAUSTED = 2;   // status word of a graph
+struct EmdDev {
+    const float* x; const float* y;     // as SetLossDev
+    long x_bstride, y_bstride;
+    int B, N, M;                        // N + M <= emd_max_points(), min(N, M) <= EMD_MAX_MATCH
+    int* match;                         // (B, N): the y index matched to x_i, or -1
+    int* status;                        // (B): EMD_*
+    double* part;                       // (B): sum of the matched fp32 distances in ascending i; NaN for a failed graph
+};
+size_t emd_max_points();                // N + M that fits the LDS tile with the solver's arrays beside the clouds
+hipError_t launch_emd_assign(const EmdDev& a, hipStream_t st);
+hipError_t launch_emd_grad(const EmdDev& a, const SetGradDev& g, hipStream_t st);
 
 // ---- device-resident physics-parameter fit (ag_ppm.hip; ag_ppm_grad_step, ag_ppm_adam_step): the glue of the masked rollout
 // (forward_dynamics.py:209-399) around the forwards and the backward chunks, and the per-start reduction + Adam.  Rows [0,L) of a

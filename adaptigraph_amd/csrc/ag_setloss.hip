@@ -10,6 +10,7 @@
 //                hausdorff = max x-side + max y-side with the winning (b, i) and (b, j), lowest (b, index) among equals.
 //                k_set_final is the standalone form; k_step_loss_final also closes a training step's loss (MSE partials of
 //                k_mse_part, the per-term table, the weighted fp32 sum in list order, train.py:100-102).
+//                The Earth-mover term (ag_emd.hip) joins both finalisers: the mean of its matched distances.
 //   k_set_grad   one workgroup per graph, the y arg-min table in LDS: the thread of x_i takes its own nearest y, then walks the
 //                table for the j whose arg-min is i, in ascending j.  Hausdorff: only the two winning pairs.  The norm's gradient
 //                at zero distance is zero (torch).  Every x_i has one writer: no atomics, repeated runs give the same bits.
@@ -21,10 +22,6 @@ namespace ag {
 namespace {
 constexpr int ST = 256;
 
-__device__ __forceinline__ float set_dist(float ax, float ay, float az, float bx, float by, float bz) {
-    const float dx = __fsub_rn(ax, bx), dy = __fsub_rn(ay, by), dz = __fsub_rn(az, bz);
-    return __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
-}
 // nearest point of the other cloud (SoA in LDS, on points, stride opad): lowest index of the smallest distance; a NaN distance
 // is taken at its first occurrence and kept
 __device__ __forceinline__ float set_nearest(const float* os, int opad, int on, float qx, float qy, float qz, int& arg) {
@@ -123,8 +120,18 @@ __device__ inline void set_reduce(const double* part, const int* pidx, int B, in
     hausdorff = mx + my;
 }
 
-__global__ void k_set_final(const double* part, const int* pidx, int B, int N, int M, int B_total, int kind, float* out, int* win_out) {
+// the Earth-mover term: the B partials of k_emd_assign in index order, over the B_total * K matched pairs of the whole batch
+// (torch.mean over the (B, K) matched norms, loss.py:54).  A failed graph's partial is NaN, and so is the term
+__device__ inline double emd_reduce(const double* part, int B, int K, int B_total) {
+    double s = 0.0;
+    for (int b = 0; b < B; ++b) s += part[b];
+    return s / ((double)B_total * K);
+}
+
+__global__ void k_set_final(const double* part, const int* pidx, const double* emd_part, int B, int N, int M, int B_total, int kind,
+                            float* out, int* win_out) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if (kind == SET_LOSS_EMD) { out[0] = (float)emd_reduce(emd_part, B, N < M ? N : M, B_total); return; }
     double ch, hd; int win[4];
     set_reduce(part, pidx, B, N, M, B_total, ch, hd, win);
     out[0] = (float)(kind == SET_LOSS_CHAMFER ? ch : hd);
@@ -133,7 +140,7 @@ __global__ void k_set_final(const double* part, const int* pidx, int B, int N, i
 
 __global__ void k_step_loss_final(StepLossDev a) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    double mse = 0.0, ch = 0.0, hd = 0.0;
+    double mse = 0.0, ch = 0.0, hd = 0.0, em = 0.0;
     if (a.mse_part) {
         for (int k = 0; k < a.n_mse_part; ++k) mse += a.mse_part[k];
         mse = mse / (double)a.mse_n;
@@ -143,11 +150,12 @@ __global__ void k_step_loss_final(StepLossDev a) {
         set_reduce(a.set_part, a.set_idx, a.B, a.n_p, a.n_p, a.B_total, ch, hd, win);
         for (int k = 0; k < 4; ++k) a.win[k] = win[k];
     }
+    if (a.emd_part) em = emd_reduce(a.emd_part, a.B, a.n_p, a.B_total);
     // every term is this call's share of a mean (or, Hausdorff, the whole batch's max: never in parts); an earlier part's share
     // joins in fp64 before the one rounding.  The step's loss is then the fp32 sum of weight * term in list order
     float l = 0.f;
     for (int k = 0; k < a.n_terms; ++k) {
-        double v = a.kind[k] == SET_LOSS_MSE ? mse : a.kind[k] == SET_LOSS_CHAMFER ? ch : hd;
+        double v = a.kind[k] == SET_LOSS_MSE ? mse : a.kind[k] == SET_LOSS_CHAMFER ? ch : a.kind[k] == SET_LOSS_HAUSDORFF ? hd : em;
         float* t = a.terms + (long)a.fi * a.n_terms + k;
         if (a.accumulate) v += (double)*t;
         *t = (float)v;
@@ -160,16 +168,6 @@ __global__ void k_step_loss_final(StepLossDev a) {
         a.loss[a.n_future] = s;
     }
 }
-
-// g += s * d||x_i - y_j|| / dx_i; zero at zero distance
-__device__ __forceinline__ void set_pull(const float* xi, const float* yj, float s, float (&g)[3]) {
-    const float dx = __fsub_rn(xi[0], yj[0]), dy = __fsub_rn(xi[1], yj[1]), dz = __fsub_rn(xi[2], yj[2]);
-    const float dist = __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
-    if (!(dist > 0.f)) return;
-    const float q = s / dist;
-    g[0] += dx * q; g[1] += dy * q; g[2] += dz * q;
-}
-__device__ __forceinline__ int clampi(int v, int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }   // a table is never trusted as an address
 
 __global__ __launch_bounds__(ST) void k_set_grad(SetLossDev a, SetGradDev g) {
     extern __shared__ int tab[];     // [M] arg-min of every y_j
@@ -222,8 +220,8 @@ hipError_t launch_set_nn(const SetLossDev& a, hipStream_t st) {
     hipLaunchKernelGGL(k_set_nn, dim3(a.B), dim3(ST), lds, st, a);
     return hipGetLastError();
 }
-hipError_t launch_set_final(const SetLossDev& a, int B_total, int kind, float* out, int* win, hipStream_t st) {
-    hipLaunchKernelGGL(k_set_final, dim3(1), dim3(64), 0, st, (const double*)a.part, (const int*)a.pidx, a.B, a.N, a.M, B_total, kind,
+hipError_t launch_set_final(const SetLossDev& a, const double* emd_part, int B_total, int kind, float* out, int* win, hipStream_t st) {
+    hipLaunchKernelGGL(k_set_final, dim3(1), dim3(64), 0, st, (const double*)a.part, (const int*)a.pidx, emd_part, a.B, a.N, a.M, B_total, kind,
                        out, win);
     return hipGetLastError();
 }

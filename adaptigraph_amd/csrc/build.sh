@@ -12,7 +12,7 @@ FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -Wall -Wno-u
 # per-file extras: the fused MLP chains are scheduled for ILP (hipcc's default strategy leaves ~0.9 % on k_edge_enc and
 # ~0.5 % on k_node_prop: A/B on the same box); scheduling only, results are bit-identical
 declare -A PERFILE=( [ag_mlp]="-mllvm -amdgpu-sched-strategy=max-ilp" )
-SRCS="ag_edges ag_rules ag_mlp ag_lat ag_graph ag_cost ag_setloss ag_mppi ag_train ag_optim ag_ppm ag_dataset ag_eval ag_api ag_api_edges ag_api_rollout ag_api_train ag_api_dataset ag_api_eval"
+SRCS="ag_edges ag_rules ag_mlp ag_lat ag_graph ag_cost ag_setloss ag_emd ag_mppi ag_train ag_optim ag_ppm ag_dataset ag_eval ag_api ag_api_edges ag_api_rollout ag_api_train ag_api_dataset ag_api_eval"
 build_variant() {   # $1 = object dir, $2 = extra flags, $3 = output, $4 = extra sources
   mkdir -p "$1"
   local objs=""

@@ -15,7 +15,8 @@ loss_part, exactly); the shares are summed on the device in call order and Adam 
 losses=[(term, weight), ...] replaces the hard-wired MSE by the reference's loss list (train.py:65, 100-102): "mse", "chamfer"
 and "hausdorff" (or torch.nn.MSELoss, ChamferLoss, HausdorffLoss instances; set_losses.py), up to four terms, run by
 ag_train_step_losses inside the same device-resident step.  Chamfer is a batch mean like MSE and splits into parts the same way;
-Hausdorff is a batch max and is refused with accumulate, step_parts or a group.
+Hausdorff is a batch max and is refused with accumulate, step_parts or a group.  An EarthMoverLoss() instance (set_losses.py) adds
+the Earth-mover term: its assignment is solved on the device inside the step, and being a mean it splits into parts as well.
 """
 from __future__ import annotations
 
@@ -129,7 +130,7 @@ class TrainStep:
 
     losses: None (MSE x 1, the step as it always was, through ag_train_step / ag_train_step_part) or the reference's loss list
     [(term, weight), ...] of up to four terms, a term being "mse", "chamfer", "hausdorff" or an instance of torch.nn.MSELoss,
-    ChamferLoss, HausdorffLoss (LossSpec checks it on the host).  step, evaluate, accumulate, apply and step_parts then run
+    ChamferLoss, HausdorffLoss, EarthMoverLoss (LossSpec checks it on the host).  step, evaluate, accumulate, apply and step_parts then run
     ag_train_step_losses; .last_loss_terms holds every step's terms before weighting, (n_future, n_terms) on the device.  A
     Hausdorff term is a max over the whole batch: accumulate, step_parts and group= raise ValueError with one."""
 

@@ -559,6 +559,7 @@ int ag_train_step_part(ag_ctx* ctx, void* stream, const float* d_state, const fl
 #define AG_LOSS_MSE 0
 #define AG_LOSS_CHAMFER 1
 #define AG_LOSS_HAUSDORFF 2
+#define AG_LOSS_EMD 3
 typedef struct ag_loss_spec {
     int32_t n_terms;            /* 1..4 */
     int32_t kind[4];            /* AG_LOSS_* */
@@ -576,7 +577,19 @@ typedef struct ag_loss_spec {
  * ag_cost_chamfer (<= ~13k points), else AG_ERR_UNSUPPORTED before anything is enqueued.  No masks: every row counts, as in the
  * reference's training losses.
  * d_work: NULL, or B*(N+M) + 4 int32 that receive the arg-min tables (per graph: nearest y of every x, then nearest x of every
- * y) and the Hausdorff winners {b, i, b, j}.  Enqueue only. */
+ * y) and the Hausdorff winners {b, i, b, j}.  Enqueue only.
+ *   AG_LOSS_EMD        sum_b sum_{(i,j) in A_b} d(b,i,j) / (B_total * K), K = min(N, M)    (loss.py:25-60; splits into parts through
+ *                      B_total as Chamfer does)
+ * A_b is the one-to-one matching of K pairs of graph b with the smallest sum of distances - the linear assignment problem on the
+ * fp32 distances, solved exactly on the device in fp64 (shortest augmenting paths with dual variables), one workgroup per graph;
+ * the smaller cloud is the row side, x when N == M.  Tie rule of the search: among equal path costs a free column wins, then the
+ * lowest column index (the optimum of generic clouds is unique and does not depend on it).  Limits, AG_ERR_UNSUPPORTED before
+ * anything is enqueued: K <= 512, and N + M must fit the solver's LDS tile (<= ~4k points).  A graph with a non-finite coordinate
+ * is not solved: it is marked failed and makes the loss NaN; ag_set_loss_backward then writes NaN into its rows.  (The reference
+ * prints a message and reuses the previous graph's indices there; that is not reproduced.)
+ * d_work for AG_LOSS_EMD: the same B*(N+M) + 4 int32, holding first the (B, N) match table - entry (b, i) is the y index matched
+ * to x_i of graph b, or -1 (N > M: N - M rows stay unmatched; a failed graph: every row) - then B status words (0 solved, 1
+ * non-finite input, 2 a loop bound ran out). */
 int ag_set_loss(ag_ctx* ctx, void* stream, const float* d_x, const float* d_y, int32_t B, int32_t N, int32_t M, int32_t B_total,
                 int32_t kind, float* d_out, int32_t* d_work);
 
@@ -584,7 +597,9 @@ int ag_set_loss(ag_ctx* ctx, void* stream, const float* d_x, const float* d_y, i
  * d_grad_x (B,N,3), fully written.  Each min routes to its arg-min, the norm has zero gradient at zero distance, Hausdorff
  * reaches only its two winning pairs.  The label is data: no gradient toward y.  d_work: NULL (the nearest-neighbour pass runs
  * again), or the buffer an ag_set_loss call on the same inputs and kind filled (its tables are used; indices are clamped before
- * they address anything).  No atomics: repeated calls give the same bits.  Enqueue only. */
+ * they address anything).  No atomics: repeated calls give the same bits.  Enqueue only.
+ * AG_LOSS_EMD: d_grad_x[b,i] = d_grad_out[0] / (B_total * K) * (x_i - y_j) / d(b,i,j) for the matched pair (i, j), zero for an
+ * unmatched x_i and at zero distance, NaN in every row of a failed graph. */
 int ag_set_loss_backward(ag_ctx* ctx, void* stream, const float* d_x, const float* d_y, int32_t B, int32_t N, int32_t M,
                          int32_t B_total, int32_t kind, const float* d_grad_out, float* d_grad_x, const int32_t* d_work);
 
@@ -597,7 +612,8 @@ int ag_set_loss_backward(ag_ctx* ctx, void* stream, const float* d_x, const floa
  *   d_loss_terms  NULL, or (n_future, n_terms) floats: every step's terms before weighting.  Required when accumulate != 0:
  *                 the parts' running sums live there, each part's share joining in fp64 before the one rounding.
  * B_total and accumulate act on MSE and Chamfer terms as in ag_train_step_part (both are means over the batch: a part's share
- * is B / B_total).  A Hausdorff term with B_total != B or accumulate != 0 returns AG_ERR_UNSUPPORTED; an unknown kind, a
+ * is B / B_total), and on an Earth-mover term (AG_LOSS_EMD, a mean over the B_total * n_p matched pairs; n_p <= 512 and 2 * n_p
+ * within its LDS tile, else AG_ERR_UNSUPPORTED).  A Hausdorff term with B_total != B or accumulate != 0 returns AG_ERR_UNSUPPORTED; an unknown kind, a
  * non-finite weight or n_terms outside 1..4 AG_ERR_INVALID; 2 * n_p beyond the LDS tile with a set term AG_ERR_UNSUPPORTED - all
  * before anything is enqueued.  spec = {1, {AG_LOSS_MSE}, {1}} gives ag_train_step_part's bits; ag_train_step and
  * ag_train_step_part themselves are unchanged and never run this path.  Enqueue only. */

@@ -60,6 +60,28 @@ struct WeightLayout {
     static constexpr int TOTAL = P_P2 + OUT3_FLOATS;
 };
 
+// ---- build switches of the fp32 chains (ag_mlp.hip, where they are described: "Zero skip" and "Half-steps").  They sit here because
+// the weight packer (ag_optim.hip) has to agree with the chains on them: a chain built with half-steps reads its 160-wide layers
+// from a PAIRED image (pack_elem_f32), a chain built without reads the plain one.  -DAG_ZS_EDGE=0|2 / -DAG_ZS_ENC=1 / -DAG_ZS_NODE=0 /
+// -DAG_HS_EDGE=0 / -DAG_HS_NODE=0: experiment builds (tools/build_experiment.sh hands the flags to every source file).
+#ifndef AG_ZS_EDGE
+#define AG_ZS_EDGE 2
+#endif
+#ifndef AG_ZS_ENC
+#define AG_ZS_ENC 0
+#endif
+#ifndef AG_ZS_NODE
+#define AG_ZS_NODE 1
+#endif
+#ifndef AG_HS_EDGE
+#define AG_HS_EDGE 1
+#endif
+#ifndef AG_HS_NODE
+#define AG_HS_NODE 1
+#endif
+constexpr bool ZS_EDGE = AG_ZS_EDGE != 0, ZS_EDGE_ALL = AG_ZS_EDGE == 2, ZS_ENC = AG_ZS_ENC != 0, ZS_NODE = AG_ZS_NODE != 0;
+constexpr bool HS_EDGE = ZS_EDGE && AG_HS_EDGE != 0, HS_NODE = ZS_NODE && AG_HS_NODE != 0;
+
 // ---- kernel families (profiling ids) ------------------------------------------------------------------
 enum Family { FAM_EDGE_COUNT = 0, FAM_EDGE_EMIT, FAM_PREP, FAM_NODE_ENC, FAM_EDGE_ENC, FAM_MP, FAM_NODE_PROP,
               FAM_NODE_FINAL, FAM_ROLL_INIT, FAM_ROLL_UPDATE, FAM_COST, FAM_FPS, FAM_ASSEMBLE, FAM_RULE, FAM_SURFACE, FAM_COUNT };

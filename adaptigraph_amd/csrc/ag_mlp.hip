@@ -67,26 +67,10 @@ struct Act { f32x16 t[5]; };
 // plain skip, 1.1 % faster per launch with half-steps (the tool tiles are 28-48 % half-dead, docs/EXPERIMENTS.md).  k_node_enc is built like the relation-encoder chain and is not on the flagship path (the class table goes
 // through the latency-mode chain); unmeasured, so it stays as it was.
 // docs/EXPERIMENTS.md, "Zero skip in the fp32 chains" and "Class-major work list".  -DAG_ZS_EDGE=0|2 / -DAG_ZS_ENC=1 / -DAG_ZS_NODE=0:
-// experiment builds.
-#ifndef AG_ZS_EDGE
-#define AG_ZS_EDGE 2
-#endif
-#ifndef AG_ZS_ENC
-#define AG_ZS_ENC 0
-#endif
-#ifndef AG_ZS_NODE
-#define AG_ZS_NODE 1
-#endif
-constexpr bool ZS_EDGE = AG_ZS_EDGE != 0, ZS_EDGE_ALL = AG_ZS_EDGE == 2, ZS_ENC = AG_ZS_ENC != 0, ZS_NODE = AG_ZS_NODE != 0;
+// experiment builds.  The switches themselves (ZS_EDGE, ZS_EDGE_ALL, ZS_ENC, ZS_NODE) are defined in ag_common.h.
 // Half-steps (mma_act) per chain, fixed at build time like the skip they extend; 0 = the chain's code is the one without them,
-// instruction for instruction.  docs/EXPERIMENTS.md, "Half-dead k-steps at K = 1".  -DAG_HS_EDGE=0 / -DAG_HS_NODE=0: experiment builds.
-#ifndef AG_HS_EDGE
-#define AG_HS_EDGE 1
-#endif
-#ifndef AG_HS_NODE
-#define AG_HS_NODE 1
-#endif
-constexpr bool HS_EDGE = ZS_EDGE && AG_HS_EDGE != 0, HS_NODE = ZS_NODE && AG_HS_NODE != 0;
+// instruction for instruction, and its layers are packed unpaired.  docs/EXPERIMENTS.md, "Half-dead k-steps at K = 1" and "Paired
+// weight image".  -DAG_HS_EDGE=0 / -DAG_HS_NODE=0: experiment builds (HS_EDGE, HS_NODE: ag_common.h, shared with the weight packer).
 
 // ------------------------------------------------------------------------------------------------ staging
 // global -> LDS DMA (global_load_lds, 16 B per lane): NFLOATS (a multiple of 256) in 1-KB pieces, each wave-instruction
@@ -124,14 +108,18 @@ __device__ __forceinline__ void dma_copy(float* lds_dst, const float* __restrict
 // Half-steps (Options::half_step, HS): a k-step carries feature `lo` on lanes 0-31 and `lo + 4` on lanes 32-63, and about half of all
 // steps have exactly ONE of the two all zero.  Such a step issues 3 MFMAs instead of 5: tiles (0,1) and (2,3) take one
 // v_mfma_f32_32x32x1_2b_f32 each - one k, two independent 32 x 32 blocks, block b = accumulator registers 16b .. 16b+15 with the
-// lane map of the 32x32x2 form, the same 16 passes - and tile 4 the ordinary MFMA (its dead half adds w * 0).  The A operand needs no
-// second weight image: a[2m][e] is [W(tile 2m, lo) | W(tile 2m, lo+4)] on its lane halves, and ONE v_permlane32_swap with
-// a[2m+1][e] leaves [W(2m, lo) | W(2m+1, lo)] in the first and [W(2m, lo+4) | W(2m+1, lo+4)] in the second register (in place: a
-// step's fragments are used by that step only).  The B operand is the step's own activation register, its live half broadcast to
-// both blocks by the MFMA's blgp modifier (1: lanes 0-31, 2: lanes 32-63).  Bits: an f32 MFMA is a k-ordered fmaf chain, so the full
-// step computes fma(w', x', fma(w, x, acc)) and the half-step the same with the fma whose x is zero left out - the identity for
+// lane map of the 32x32x2 form, the same 16 passes - and tile 4 the ordinary MFMA (its dead half adds w * 0).  The A operand of the
+// two-block form is [W(tile 2m, k) | W(tile 2m+1, k)] on the lane halves, where the 32x32x2 form wants [W(tile, lo) | W(tile, lo+4)].
+// Every step of an HS chain that issues anything issues the two-block form on tiles 0-3 (a fully live step as 2 x 2 of them in K
+// order), so the layers such a chain reads are PACKED that way (ag_optim.hip, pack_elem_f32: m-blocks 2m and 2m+1 of a paired
+// block hold [W(2m, lo) | W(2m+1, lo)] and [W(2m, lo+4) | W(2m+1, lo+4)]; m-block 4 is unchanged) and a[2m][e], a[2m+1][e] are the
+// operands as they come from LDS.  (The first version packed every layer for the 32x32x2 form and made these with one
+// v_permlane32_swap per tile pair at the head of every live step: 456 swaps per tile in k_edge_enc, VALU work in front of the MFMAs
+// that wait for it.  docs/EXPERIMENTS.md, "Paired weight image".)  The B operand is the step's own activation register, its live half
+// broadcast to both blocks by the MFMA's blgp modifier (1: lanes 0-31, 2: lanes 32-63).  Bits: an f32 MFMA is a k-ordered fmaf
+// chain, so the full step computes fma(w', x', fma(w, x, acc)) and the half-step the same with the fma whose x is zero left out - the identity for
 // finite w (and the same sign-of-an-exact-zero caveat on the seeded accumulator as the skip).  tools/probes/mfma_half_step.hip
-// checks the bits and times it: 0.67-0.69 of a full step.
+// checks the bits and times it: 0.57-0.60 of a full step from paired fragments (0.67-0.69 with the swaps).
 struct Live {
     unsigned m[3];                                                // bit s & 31 of m[s >> 5]: k-step s has a non-zero input
     unsigned lo[3], hi[3];                                        // HS only: ... on lanes 0-31 / on lanes 32-63 (m = lo | hi)
@@ -149,7 +137,8 @@ __device__ __forceinline__ f32x16 hi16(f32x32 c) {
 // them stay in the sweeps.
 template <int Q0, int Q1, int MB, bool SKIP, bool HS = false>
 __device__ __forceinline__ void mma_act(const float* wl, const Act& in, f32x16* acc, int lane, const Live& lv, f32x32* pr = nullptr) {
-    static_assert(!HS || (SKIP && MB == 5), "half-steps extend the skip of the 160-wide layers");
+    // HS without SKIP: every step in the two-block form - how a chain without a skip reads a paired layer (k_node_enc)
+    static_assert(!HS || MB == 5, "the two-block form is that of the 160-wide layers");
 #pragma unroll
     for (int q = Q0; q < Q1; ++q) {
         const unsigned nib = SKIP ? (lv.m[(4 * q) >> 5] >> ((4 * q) & 31)) & 15u : 15u;   // a chunk never straddles a word
@@ -173,22 +162,16 @@ __device__ __forceinline__ void mma_act(const float* wl, const Act& in, f32x16* 
                 if (HS) {
                     // tiles (0,1) and (2,3): one two-block MFMA per live half, in K order (lo, then lo + 4: the fmaf chain of the
                     // 32x32x2 form); tile 4: the ordinary MFMA, whose dead half adds w * 0.  Both live = 5 MFMAs' worth of passes.
-                    const bool l = (lv.lo[s >> 5] >> (s & 31)) & 1u, h = (lv.hi[s >> 5] >> (s & 31)) & 1u;
+                    const bool l = !SKIP || ((lv.lo[s >> 5] >> (s & 31)) & 1u), h = !SKIP || ((lv.hi[s >> 5] >> (s & 31)) & 1u);
                     if (__builtin_expect(l || h, 1)) {
-                        float w[2][2];
-#pragma unroll
-                        for (int m = 0; m < 2; ++m) {
-                            const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(a[2 * m][e]), __float_as_uint(a[2 * m + 1][e]),
-                                                                             false, false);
-                            w[m][0] = __uint_as_float(sw[0]); w[m][1] = __uint_as_float(sw[1]);
-                        }
+                        // paired image: a[2m][e] = [W(2m, lo) | W(2m+1, lo)], a[2m+1][e] = [W(2m, lo+4) | W(2m+1, lo+4)]
                         if (l) {
 #pragma unroll
-                            for (int m = 0; m < 2; ++m) pr[m] = __builtin_amdgcn_mfma_f32_32x32x1f32(w[m][0], b, pr[m], 0, 0, 1);
+                            for (int m = 0; m < 2; ++m) pr[m] = __builtin_amdgcn_mfma_f32_32x32x1f32(a[2 * m][e], b, pr[m], 0, 0, 1);
                         }
                         if (h) {
 #pragma unroll
-                            for (int m = 0; m < 2; ++m) pr[m] = __builtin_amdgcn_mfma_f32_32x32x1f32(w[m][1], b, pr[m], 0, 0, 2);
+                            for (int m = 0; m < 2; ++m) pr[m] = __builtin_amdgcn_mfma_f32_32x32x1f32(a[2 * m + 1][e], b, pr[m], 0, 0, 2);
                         }
                         acc[4] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4][e], b, acc[4], 0, 0, 0);
                     }
@@ -803,13 +786,16 @@ __global__ __launch_bounds__(WG, 2) void k_node_enc(GDev g) {
     relu_one(x, lane);
     layer160<Q_FLOATS, true, false, ZS_ENC>(lds, g.w + WL::N_L3, g.w + WL::N_WA, x, y, tid, lane, live_of(x, g.zero_skip));
     relu_one(y, lane);                                       // y = p_enc (slot 150 = 1 for the bias of Wa)
-    const Live lv = live_of(y, g.zero_skip);                 // p_enc feeds Wa, W2 and W3
+    // W2 and W3 are the propagate chains' layers as well: with half-steps there (HS_NODE) the two blocks are packed paired, and this
+    // chain reads them in the two-block form too, every step (or every live one) on both halves: the same fmaf chain as the five
+    // 32x32x2 MFMAs, bit for bit (tools/probes/mfma_half_step.hip, part 3).  No swap back, and no second copy of the two blocks.
+    const Live lv = live_of<HS_NODE>(y, g.zero_skip);        // p_enc feeds Wa, W2 and W3 (half = 0: both halves say what `m` says)
     store_rows_t(y, g.eff, (int)row, valid, stg, lane);
     layer160<Q_FLOATS, true, false, ZS_ENC>(lds, g.w + WL::N_WA, g.w + WL::N_W2, y, x, tid, lane, lv);
     store_rows_t(x, g.P, (int)row, valid, stg, lane);
-    layer160<Q_FLOATS, true, false, ZS_ENC>(lds, g.w + WL::N_W2, g.w + WL::N_W3, y, x, tid, lane, lv);
+    layer160<Q_FLOATS, true, false, ZS_ENC, HS_NODE>(lds, g.w + WL::N_W2, g.w + WL::N_W3, y, x, tid, lane, lv);
     store_rows_t(x, g.U, (int)row, valid, stg, lane);
-    layer160<0, true, false, ZS_ENC>(lds, g.w + WL::N_W3, nullptr, y, x, tid, lane, lv);
+    layer160<0, true, false, ZS_ENC, HS_NODE>(lds, g.w + WL::N_W3, nullptr, y, x, tid, lane, lv);
     store_rows_t(x, g.V, (int)row, valid, stg, lane);
 }
 

@@ -18,28 +18,31 @@ namespace {
 
 // kind: 0 hidden layer (152 input slots, bias in slot ONE_F), 1 first layer of an encoder (inputs then the bias), 2 the 3-output head
 // in: -1 = the model's rel_dim (5 + 3 n_his); chunks: k-chunks of a first layer in the fp32 / latency image
-struct PackBlock { int w, b, ld, col0, out, in, kind, off, b3_phase, lat, chunks, lat_chunks; };
+// pair (kind 0, fp32 image only): the block's readers are half-step chains (ag_mlp.hip, mma_act), which issue the two-block MFMA on
+// tile pairs (0,1) and (2,3): m-blocks 2m and 2m+1 then hold the A operands of that form (pack_elem_f32).  It follows the build
+// switches of the chains: with half-steps compiled out of a chain its blocks are packed plain and its code is the one before them.
+struct PackBlock { int w, b, ld, col0, out, in, kind, off, b3_phase, lat, chunks, lat_chunks, pair; };
 using WL = WeightLayout;
 constexpr int kNumBlocks = 14;
 constexpr PackBlock kPackBlocks[kNumBlocks] = {
-    // tensor, bias, ld, col0, out, in, kind, fp32 offset, bf16x3 phase (WLB in ag_mlp.hip), latency slot (ag_lat.hip), chunks
-    {0, 1, IN_DIM, 0, NF, IN_DIM, 1, WL::N_L1, 16, 10, NODE_L1_CHUNKS, 1},   // particle encoder
-    {2, 3, NF, 0, NF, NF, 0, WL::N_L2, 17, 11, 0, 0},
-    {4, 5, NF, 0, NF, NF, 0, WL::N_L3, 22, 12, 0, 0},
-    {6, 7, -1, 0, NF, -1, 1, WL::E_L1, 0, 0, EDGE_L1_CHUNKS, 2},             // relation encoder
-    {8, 9, NF, 0, NF, NF, 0, WL::E_L2, 1, 1, 0, 0},
-    {10, 11, NF, 0, NF, NF, 0, WL::E_L3, 6, 2, 0, 0},
-    {12, 13, 2 * NF, 0, NF, NF, 0, WL::N_WA, 27, 13, 0, 0},                  // particle propagator W_pp = [Wa | Wb], bias with Wa
-    {12, -1, 2 * NF, NF, NF, NF, 0, WL::P_WB, 42, 4, 0, 0},
-    {14, 15, 3 * NF, 0, NF, NF, 0, WL::E_W1, 11, 3, 0, 0},                   // relation propagator W_rp = [W1 | W2 | W3], bias with W1
-    {14, -1, 3 * NF, NF, NF, NF, 0, WL::N_W2, 32, 5, 0, 0},
-    {14, -1, 3 * NF, 2 * NF, NF, NF, 0, WL::N_W3, 37, 6, 0, 0},
-    {16, 17, NF, 0, NF, NF, 0, WL::P_P0, 47, 7, 0, 0},                       // predictor
-    {18, 19, NF, 0, NF, NF, 0, WL::P_P1, 52, 8, 0, 0},
-    {20, 21, NF, 0, 3, NF, 2, WL::P_P2, 57, 9, 0, 0},
+    // tensor, bias, ld, col0, out, in, kind, fp32 offset, bf16x3 phase (WLB in ag_mlp.hip), latency slot (ag_lat.hip), chunks, pair
+    {0, 1, IN_DIM, 0, NF, IN_DIM, 1, WL::N_L1, 16, 10, NODE_L1_CHUNKS, 1, 0},   // particle encoder
+    {2, 3, NF, 0, NF, NF, 0, WL::N_L2, 17, 11, 0, 0, 0},
+    {4, 5, NF, 0, NF, NF, 0, WL::N_L3, 22, 12, 0, 0, 0},
+    {6, 7, -1, 0, NF, -1, 1, WL::E_L1, 0, 0, EDGE_L1_CHUNKS, 2, 0},             // relation encoder
+    {8, 9, NF, 0, NF, NF, 0, WL::E_L2, 1, 1, 0, 0, HS_EDGE},
+    {10, 11, NF, 0, NF, NF, 0, WL::E_L3, 6, 2, 0, 0, HS_EDGE},
+    {12, 13, 2 * NF, 0, NF, NF, 0, WL::N_WA, 27, 13, 0, 0, 0},                  // particle propagator W_pp = [Wa | Wb], bias with Wa
+    {12, -1, 2 * NF, NF, NF, NF, 0, WL::P_WB, 42, 4, 0, 0, HS_NODE},
+    {14, 15, 3 * NF, 0, NF, NF, 0, WL::E_W1, 11, 3, 0, 0, HS_EDGE},             // relation propagator W_rp = [W1 | W2 | W3], bias with W1
+    {14, -1, 3 * NF, NF, NF, NF, 0, WL::N_W2, 32, 5, 0, 0, HS_NODE},
+    {14, -1, 3 * NF, 2 * NF, NF, NF, 0, WL::N_W3, 37, 6, 0, 0, HS_NODE},
+    {16, 17, NF, 0, NF, NF, 0, WL::P_P0, 47, 7, 0, 0, HS_NODE},                 // predictor
+    {18, 19, NF, 0, NF, NF, 0, WL::P_P1, 52, 8, 0, 0, HS_NODE},
+    {20, 21, NF, 0, 3, NF, 2, WL::P_P2, 57, 9, 0, 0, 0},
 };
 
-struct PackSrc { const float* W; const float* bias; int ld, col0, out, in, kind; };
+struct PackSrc { const float* W; const float* bias; int ld, col0, out, in, kind, pair; };
 
 __host__ __device__ inline float pack_src_at(const PackSrc& s, int m, int k) {   // hidden layer / head: weight, bias in slot ONE_F, zero padding
     if (m < 0 || m >= s.out || k < 0) return 0.f;
@@ -54,6 +57,9 @@ __host__ __device__ inline float pack_first_at(const PackSrc& s, int m, int k) {
 
 // ---- MFMA A-operand image of v_mfma_f32_32x32x2_f32: [chunk q][m-block][lane][4 steps]; lane l supplies out-feature
 // 32*mb + (l&31) for input slot k(s, l>>5).  See ag_mlp.hip header.
+// Paired block (PackBlock::pair): m-blocks 2m + i, m in {0, 1}, are the A operands of v_mfma_f32_32x32x1_2b_f32 instead - lane l
+// supplies out-feature 32*(2m + (l>>5)) + (l&31), tile 2m on lanes 0-31 and tile 2m+1 on lanes 32-63, for the ONE input slot
+// k(s, i): i = 0 the feature the step carries on lanes 0-31, i = 1 the one on lanes 32-63.  M-block 4 is as in a plain block.
 __host__ __device__ inline int slot_of(int s, int h) {
     const int t = s < 64 ? s / 16 : 4, r = s < 64 ? s % 16 : s - 64;
     return 32 * t + (r & 3) + 8 * (r >> 2) + 4 * h;
@@ -64,6 +70,7 @@ template <int KIND>
 __host__ __device__ inline float pack_elem_f32(const PackSrc& s, int q, int mb, int lane, int e) {
     const int m = 32 * mb + (lane & 31);
     if (KIND == 1) return pack_first_at(s, m, 2 * (4 * q + e) + (lane >> 5));
+    if (KIND == 0 && s.pair && mb < 4) return pack_src_at(s, 32 * ((mb & ~1) + (lane >> 5)) + (lane & 31), slot_of(4 * q + e, mb & 1));
     return pack_src_at(s, m, slot_of(4 * q + e, lane >> 5));
 }
 
@@ -131,7 +138,7 @@ __host__ __device__ inline PackSrc pack_src(const PackBlock& b, const float* con
     PackSrc s;
     s.W = t[b.w]; s.bias = b.b >= 0 ? t[b.b] : nullptr;
     s.ld = b.ld < 0 ? rel_dim : b.ld; s.in = b.in < 0 ? rel_dim : b.in;
-    s.col0 = b.col0; s.out = b.out; s.kind = b.kind;
+    s.col0 = b.col0; s.out = b.out; s.kind = b.kind; s.pair = b.pair;
     return s;
 }
 

@@ -3,7 +3,7 @@
 
   headline   python tools/zero_skip_ab.py bench --libs parent=PATH,change=PATH [--runs 3] --out profiles/zero_skip_ab.json
              runs `bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline` per library in turn (ADAPTIGRAPH_AMD_LIB) and
-             keeps every run's ms per step
+             keeps every run's ms per step and reward_sha256
   kernels    python tools/zero_skip_ab.py kernels --libs ... --weights bench|all_live [--runs 3] --out ...
              the bench's cloth batch on ONE stream with share_first off (every k_edge_enc launch a full 128-candidate one),
              HIP events around every launch of the three chain kernels: ms per launch, per run.  --weights all_live sets every
@@ -100,7 +100,8 @@ def main():
                                 path, name, 600)
                 line = [ln for ln in txt.splitlines() if ln.startswith("{")][-1]
                 d = json.loads(line)
-                rec = {"lib": name, "run": i, "ms_per_step": d["ms_per_step"], "rollout_steps_per_s": d["value"]}
+                rec = {"lib": name, "run": i, "ms_per_step": d["ms_per_step"], "rollout_steps_per_s": d["value"],
+                       "reward_sha256": d.get("reward_sha256")}
             else:
                 txt = run_child([sys.executable, os.path.abspath(__file__), "one", "--weights", args.weights, "--passes", str(args.passes)],
                                 path, name, 600)

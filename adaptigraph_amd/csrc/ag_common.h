@@ -486,11 +486,12 @@ __device__ __forceinline__ float set_dist(float ax, float ay, float az, float bx
     const float dx = __fsub_rn(ax, bx), dy = __fsub_rn(ay, by), dz = __fsub_rn(az, bz);
     return __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
 }
-// g += s * d||x_i - y_j|| / dx_i; zero at zero distance
+// g += s * d||x_i - y_j|| / dx_i; zero at zero distance and at no other: a NaN distance gives a NaN row, as torch's norm does
+// (the test was !(dist > 0), which a NaN passes: the row of a diverged point came out as 0, the one number that hides it)
 __device__ __forceinline__ void set_pull(const float* xi, const float* yj, float s, float (&g)[3]) {
     const float dx = __fsub_rn(xi[0], yj[0]), dy = __fsub_rn(xi[1], yj[1]), dz = __fsub_rn(xi[2], yj[2]);
     const float dist = __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
-    if (!(dist > 0.f)) return;
+    if (dist == 0.f) return;
     const float q = s / dist;
     g[0] += dx * q; g[1] += dy * q; g[2] += dz * q;
 }

@@ -14,7 +14,12 @@
 //   k_set_grad   one workgroup per graph, the y arg-min table in LDS: the thread of x_i takes its own nearest y, then walks the
 //                table for the j whose arg-min is i, in ascending j.  Hausdorff: only the two winning pairs.  The norm's gradient
 //                at zero distance is zero (torch).  Every x_i has one writer: no atomics, repeated runs give the same bits.
-// A NaN distance wins a min and a max, as in torch.min / torch.max, so a diverged prediction gives a NaN loss.
+// A NaN distance wins a min and a max, as in torch.min / torch.max, so a diverged prediction gives a NaN loss; its pull is NaN too
+// (set_pull, ag_common.h), so the gradient row of a NaN point is NaN and the rows of graphs without one keep their bits.
+// Equal maxima: the Hausdorff winner is the lowest (b, index), and k_set_grad gives that one pair the whole weight.  torch.max()
+// over the batch splits its gradient evenly among equal maxima instead (each of k tied rows gets 1/k).  Values and arg-min tables
+// are torch's either way; the gradients differ only at exact ties, which need duplicated points.  Kept: one winner per side is
+// what lets the backward read four ints instead of searching for ties (tests/test_set_loss_edges.py has the difference on record).
 #include "ag_common.h"
 
 namespace ag {

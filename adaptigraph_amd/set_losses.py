@@ -8,6 +8,12 @@ and label (B,M,3) on the GPU; each returns a 0-d device tensor and is a torch.au
 ag_set_loss_backward: no (B,N,M,3) tensor is ever formed.  The gradient goes toward pred only - the label is data, and a label
 that requires grad raises NotImplementedError.  Every row counts (no masks), as in the reference's training losses.  TrainStep
 takes the same terms by name (losses=[("mse", 1), ("chamfer", 0.5)]) and runs them inside the device-resident step.
+  * ties: the arg-min is the lowest index of the smallest distance and the Hausdorff winner the lowest (b, index) of the largest
+    minimum, which are torch.min(dim)'s and torch.max()'s values and indices.  One gradient differs from the reference's autograd:
+    torch.max() over the batch splits its gradient evenly among EQUAL maxima, HausdorffLoss gives the whole weight to the one
+    winning pair per side.  Only exact ties - duplicated points - show it; the tied rows together carry the same pull.
+  * non-finite input: a NaN distance wins a min and a max, so the loss is NaN (inf for an infinite coordinate), the gradient row
+    of a NaN point is NaN, and the rows of graphs without a non-finite coordinate keep the bits of a clean run.
 
 EarthMoverLoss (loss.py:25-60) is the third: the mean distance over the one-to-one matching of K = min(N, M) pairs per graph with
 the smallest sum of distances.  The reference solves that assignment on the host (scipy.optimize.linear_sum_assignment per graph,

@@ -37,6 +37,7 @@ EXPORTS = ["ag_abi_version", "ag_ctx_create", "ag_ctx_destroy", "ag_last_error",
            "ag_set_loss", "ag_set_loss_backward", "ag_train_step_losses", "ag_fps_cloud"]
 
 AG_LOSS_MSE, AG_LOSS_CHAMFER, AG_LOSS_HAUSDORFF, AG_LOSS_EMD = 0, 1, 2, 3
+AG_LOSS_ROWS = 16                       # flag on a set kind: each graph's real rows (adaptigraph_amd.h, ag_set_loss)
 EMD_MAX_MATCH = 512             # min(N, M) the Earth-mover loss serves (ag_common.h)
 
 OPTIONS = ["streams", "chunk", "latency", "ragged", "ell_graph", "self_dedupe", "repeat_sort", "edge_wgs", "edge_block_min",

@@ -51,7 +51,7 @@ int train_step_impl(ag_ctx* c, void* stream, const float* d_state, const float* 
 int set_loss_call(ag_ctx* c, void* stream, const float* d_x, const float* d_y, int B, int N, int M, int B_total, int kind,
                   float* d_out, int32_t* d_work, const float* d_grad_out, float* d_grad_x, bool backward);
 int emd_loss_call(ag_ctx* c, void* stream, const float* d_x, const float* d_y, int B, int N, int M, int B_total, float* d_out,
-                  int32_t* d_work, const float* d_grad_out, float* d_grad_x, bool backward);
+                  int32_t* d_work, const float* d_grad_out, float* d_grad_x, bool backward, const SetRows& rows);
 
 }  // namespace
 
@@ -186,13 +186,22 @@ int ag_train_step_losses(ag_ctx* c, void* stream, const float* d_state, const fl
     if (!spec) return fail(c, AG_ERR_INVALID, "ag_train_step_losses: null loss spec");
     if (spec->n_terms < 1 || spec->n_terms > 4) return fail(c, AG_ERR_INVALID, "ag_train_step_losses: %d loss terms (1..4)", spec->n_terms);
     bool set_term = false, emd_term = false;
+    int set_rows = -1, emd_rows = -1;                            // the flag of the terms that share a pass: -1 none yet
     for (int k = 0; k < spec->n_terms; ++k) {
-        if (spec->kind[k] < AG_LOSS_MSE || spec->kind[k] > AG_LOSS_EMD)
+        const int kind = spec->kind[k] & ~AG_LOSS_ROWS, rows = (spec->kind[k] & AG_LOSS_ROWS) ? 1 : 0;
+        if (spec->kind[k] < 0 || kind < AG_LOSS_MSE || kind > AG_LOSS_EMD || (rows && kind == AG_LOSS_MSE))
             return fail(c, AG_ERR_INVALID, "ag_train_step_losses: term %d has unknown kind %d", k, spec->kind[k]);
         if (!std::isfinite(spec->weight[k])) return fail(c, AG_ERR_INVALID, "ag_train_step_losses: term %d has a non-finite weight", k);
-        set_term = set_term || spec->kind[k] == AG_LOSS_CHAMFER || spec->kind[k] == AG_LOSS_HAUSDORFF;
-        emd_term = emd_term || spec->kind[k] == AG_LOSS_EMD;
-        if (spec->kind[k] == AG_LOSS_HAUSDORFF && (B_total != B || accumulate != 0))
+        set_term = set_term || kind == AG_LOSS_CHAMFER || kind == AG_LOSS_HAUSDORFF;
+        emd_term = emd_term || kind == AG_LOSS_EMD;
+        if (kind != AG_LOSS_MSE) {
+            int& seen = kind == AG_LOSS_EMD ? emd_rows : set_rows;
+            if (seen >= 0 && seen != rows)
+                return fail(c, AG_ERR_INVALID, "ag_train_step_losses: term %d: terms that share a pass (Chamfer and Hausdorff; Earth-mover) "
+                            "must agree on AG_LOSS_ROWS", k);
+            seen = rows;
+        }
+        if (kind == AG_LOSS_HAUSDORFF && (B_total != B || accumulate != 0))
             return fail(c, AG_ERR_UNSUPPORTED, "ag_train_step_losses: a Hausdorff term is a max over the whole batch and does not split "
                         "into parts (B=%d, B_total=%d, accumulate=%d)", B, B_total, accumulate);
     }
@@ -270,11 +279,15 @@ int train_step_impl(ag_ctx* c, void* stream, const float* d_state, const float* 
     // a loss list: which kernels a step needs, the weights per kind (terms of one kind share their passes)
     bool has_mse = false, has_set = false, has_emd = false;
     double w_mse = 0.0; float w_ch = 0.f, w_hd = 0.f, w_em = 0.f;
+    bool set_rows = false, emd_rows = false;                     // AG_LOSS_ROWS: one flag per pass (checked by the caller)
     for (int k = 0; spec && k < spec->n_terms; ++k) {
-        if (spec->kind[k] == AG_LOSS_MSE) { has_mse = true; w_mse += (double)spec->weight[k]; }
-        else if (spec->kind[k] == AG_LOSS_EMD) { has_emd = true; w_em += spec->weight[k]; }
-        else { has_set = true; (spec->kind[k] == AG_LOSS_CHAMFER ? w_ch : w_hd) += spec->weight[k]; }
+        const int kind = spec->kind[k] & ~AG_LOSS_ROWS;
+        const bool rows = (spec->kind[k] & AG_LOSS_ROWS) != 0;
+        if (kind == AG_LOSS_MSE) { has_mse = true; w_mse += (double)spec->weight[k]; }
+        else if (kind == AG_LOSS_EMD) { has_emd = true; emd_rows = rows; w_em += spec->weight[k]; }
+        else { has_set = true; set_rows = rows; (kind == AG_LOSS_CHAMFER ? w_ch : w_hd) += spec->weight[k]; }
     }
+    int* live = nullptr;                                         // (B) live prefix of every graph, from d_attrs (k_prefix_rows)
     SetLossDev sd{};                                             // the set terms' clouds: prediction against state_future[:, fi]
     sd.x_bstride = (long)n_p * 3; sd.y_bstride = (long)n_future * n_p * 3; sd.B = B; sd.N = n_p; sd.M = n_p;
     int* nn_all = nullptr; int* win_all = nullptr; float* terms = d_loss_terms;
@@ -293,6 +306,7 @@ int train_step_impl(ag_ctx* c, void* stream, const float* d_state, const float* 
             win_all = s.take<int>((size_t)n_future * 4);
             sd.part = s.take<double>(set_loss_part_doubles(B)); sd.pidx = s.take<int>(set_loss_part_ints(B));
         }
+        if (set_rows || emd_rows) live = s.take<int>((size_t)B);
         if (spec && !d_loss_terms) terms = s.take<float>((size_t)n_future * spec->n_terms);
         S = s.take<float>((size_t)(n_future - 1) * n_state);     // model inputs of steps 1.. (step 0: the caller's)
         A = s.take<float>((size_t)(n_future - 1) * n_act);
@@ -307,6 +321,11 @@ int train_step_impl(ag_ctx* c, void* stream, const float* d_state, const float* 
     });
     if (rc) return rc;
     HIPCHK(c, launch_edge_guard(d_n_edges, B, cap, f.n_eff, d_status, st));
+    // the prediction's and the label's real rows are the graph's live prefix: the same count on both sides
+    if (live) HIPCHK(c, launch_prefix_rows(d_attrs, B, N, n_p, live, st));
+    const SetRows no_rows{nullptr, nullptr}, live_rows{live, live};
+    const SetRows& srows = set_rows ? live_rows : no_rows;
+    const SetRows& erows = emd_rows ? live_rows : no_rows;
     auto state_of = [&](int fi) { return fi == 0 ? d_state : S + (size_t)(fi - 1) * n_state; };
     auto action_of = [&](int fi) { return fi == 0 ? d_action : A + (size_t)(fi - 1) * n_act; };
     // ---- train.py:94-119: n_future chained forwards, MSE of each prediction, the next model input from it
@@ -329,13 +348,13 @@ int train_step_impl(ag_ctx* c, void* stream, const float* d_state, const float* 
             }
             if (has_set) {
                 sd.x = pred; sd.y = d_state_future + (size_t)fi * n_p * 3; sd.nn = nn_all + (size_t)fi * B * 2 * n_p;
-                HIPCHK(c, launch_set_nn(sd, st));
+                HIPCHK(c, launch_set_nn(sd, srows, st));
                 fl.set_part = sd.part; fl.set_idx = sd.pidx; fl.win = win_all + 4 * fi;
             }
             if (has_emd) {
                 ed.x = pred; ed.y = d_state_future + (size_t)fi * n_p * 3;
                 ed.match = match_all + (size_t)fi * B * n_p; ed.status = emd_status_all + (size_t)fi * B;
-                HIPCHK(c, launch_emd_assign(ed, st));
+                HIPCHK(c, launch_emd_assign(ed, erows, st));
                 fl.emd_part = ed.part;
             }
             HIPCHK(c, launch_step_loss_final(fl, st));
@@ -364,14 +383,14 @@ int train_step_impl(ag_ctx* c, void* stream, const float* d_state, const float* 
                 sd.x = P + (size_t)fi * n_pred; sd.y = d_state_future + (size_t)fi * n_p * 3; sd.nn = nn_all + (size_t)fi * B * 2 * n_p;
                 SetGradDev sg{};
                 sg.w_chamfer = w_ch; sg.w_hausdorff = w_hd; sg.B_total = B_total; sg.win = win_all + 4 * fi; sg.gx = dpos; sg.add = 1;
-                HIPCHK(c, launch_set_grad(sd, sg, st));
+                HIPCHK(c, launch_set_grad(sd, srows, sg, st));
             }
             if (has_emd) {                                          // after the other set terms, on the same stream: one writer at a time
                 ed.x = P + (size_t)fi * n_pred; ed.y = d_state_future + (size_t)fi * n_p * 3;
                 ed.match = match_all + (size_t)fi * B * n_p; ed.status = emd_status_all + (size_t)fi * B;
                 SetGradDev sg{};
                 sg.w_emd = w_em; sg.B_total = B_total; sg.gx = dpos; sg.add = 1;
-                HIPCHK(c, launch_emd_grad(ed, sg, st));
+                HIPCHK(c, launch_emd_grad(ed, erows, sg, st));
             }
         }
         t.state = state_of(fi); t.action = action_of(fi);
@@ -387,9 +406,10 @@ int train_step_impl(ag_ctx* c, void* stream, const float* d_state, const float* 
 
 // set_loss_call for AG_LOSS_EMD (the arguments are checked there): the assignment solve and the finaliser, then - backward - the
 // gradient.  d_work (B*(N+M) + 4 int32, optional): the (B,N) match table, then B status words.  A backward that is given them
-// does not solve again (the gradient kernel clamps what it reads from the table).
+// does not solve again (the gradient kernel clamps what it reads from the table).  rows: the counts of a flagged kind (both
+// null otherwise), which live behind those words in d_work - required then.
 int emd_loss_call(ag_ctx* c, void* stream, const float* d_x, const float* d_y, int B, int N, int M, int B_total, float* d_out,
-                  int32_t* d_work, const float* d_grad_out, float* d_grad_x, bool backward) {
+                  int32_t* d_work, const float* d_grad_out, float* d_grad_x, bool backward, const SetRows& rows) {
     if ((size_t)N + (size_t)M > emd_max_points())
         return fail(c, AG_ERR_UNSUPPORTED, "ag_set_loss: N+M=%d exceeds the Earth-mover LDS tile (%zu points)", N + M, emd_max_points());
     if (std::min(N, M) > EMD_MAX_MATCH)
@@ -412,30 +432,40 @@ int emd_loss_call(ag_ctx* c, void* stream, const float* d_x, const float* d_y, i
     if (rc) return rc;
     Scoped pr(c, FAM_COST);
     if (!given) {
-        HIPCHK(c, launch_emd_assign(ed, st));
+        HIPCHK(c, launch_emd_assign(ed, rows, st));
         SetLossDev sd{};
         sd.B = B; sd.N = N; sd.M = M;
-        HIPCHK(c, launch_set_final(sd, ed.part, B_total, AG_LOSS_EMD, val, nullptr, st));
+        HIPCHK(c, launch_set_final(sd, ed.part, B_total, AG_LOSS_EMD | (rows.nx ? AG_LOSS_ROWS : 0), val, nullptr, st));
     }
     if (!backward) return AG_OK;
     SetGradDev sg{};
     sg.gout = d_grad_out; sg.w_emd = 1.f; sg.B_total = B_total; sg.gx = d_grad_x; sg.add = 0;
-    HIPCHK(c, launch_emd_grad(ed, sg, st));
+    HIPCHK(c, launch_emd_grad(ed, rows, sg, st));
     return AG_OK;
 }
 
 // ag_set_loss (backward false) and ag_set_loss_backward: the nearest-neighbour pass and the finaliser, then - backward - the
 // gradient.  d_work (B*(N+M) + 4 int32, optional): the arg-min tables and the Hausdorff winners.  The forward leaves them there;
 // a backward that is given them skips its own pass (the gradient kernel clamps what it reads from a table, so a stale buffer
-// gives a wrong gradient, never a wild read).
+// gives a wrong gradient, never a wild read).  kind | AG_LOSS_ROWS: d_work is required and 2 B words longer, nx[B] then ny[B], inputs
+// (counts are clamped by the kernels that read them).
 int set_loss_call(ag_ctx* c, void* stream, const float* d_x, const float* d_y, int B, int N, int M, int B_total, int kind,
                   float* d_out, int32_t* d_work, const float* d_grad_out, float* d_grad_x, bool backward) {
     if (!c) return AG_ERR_INVALID;
     if (!d_x || !d_y || (!backward && !d_out)) return fail(c, AG_ERR_INVALID, "ag_set_loss: null pointer");
     if (B < 1 || N < 1 || M < 1 || B_total < B) return fail(c, AG_ERR_INVALID, "ag_set_loss: bad sizes B=%d N=%d M=%d B_total=%d", B, N, M, B_total);
+    const bool flagged = kind >= 0 && (kind & AG_LOSS_ROWS) != 0;
+    const int full_kind = kind;
+    if (flagged) kind &= ~AG_LOSS_ROWS;
     if (kind != AG_LOSS_CHAMFER && kind != AG_LOSS_HAUSDORFF && kind != AG_LOSS_EMD)
-        return fail(c, AG_ERR_INVALID, "ag_set_loss: kind %d is no set loss", kind);
-    if (kind == AG_LOSS_EMD) return emd_loss_call(c, stream, d_x, d_y, B, N, M, B_total, d_out, d_work, d_grad_out, d_grad_x, backward);
+        return fail(c, AG_ERR_INVALID, "ag_set_loss: kind %d is no set loss", full_kind);
+    if (flagged && !d_work)
+        return fail(c, AG_ERR_INVALID, "ag_set_loss: AG_LOSS_ROWS needs d_work: the counts nx[B], ny[B] are its last 2 B words");
+    // AG_LOSS_ROWS: the counts follow the B*(N+M) + 4 words every kind has; the kernels clamp them where they read them
+    const size_t n_tab = (size_t)B * ((size_t)N + M) + 4;
+    const SetRows rows{flagged ? d_work + n_tab : nullptr, flagged ? d_work + n_tab + B : nullptr};
+    if (kind == AG_LOSS_EMD)
+        return emd_loss_call(c, stream, d_x, d_y, B, N, M, B_total, d_out, d_work, d_grad_out, d_grad_x, backward, rows);
     if (kind == AG_LOSS_HAUSDORFF && B_total != B)
         return fail(c, AG_ERR_UNSUPPORTED, "ag_set_loss: the Hausdorff loss is a max over the whole batch and does not split into parts");
     if ((size_t)N + (size_t)M > chamfer_max_points())
@@ -458,14 +488,14 @@ int set_loss_call(ag_ctx* c, void* stream, const float* d_x, const float* d_y, i
     if (rc) return rc;
     Scoped pr(c, FAM_COST);
     if (!given) {
-        HIPCHK(c, launch_set_nn(sd, st));
-        HIPCHK(c, launch_set_final(sd, nullptr, B_total, kind, val, win, st));
+        HIPCHK(c, launch_set_nn(sd, rows, st));
+        HIPCHK(c, launch_set_final(sd, nullptr, B_total, full_kind, val, win, st));
     }
     if (!backward) return AG_OK;
     SetGradDev sg{};
     sg.gout = d_grad_out; sg.B_total = B_total; sg.win = win; sg.gx = d_grad_x; sg.add = 0;
     (kind == AG_LOSS_CHAMFER ? sg.w_chamfer : sg.w_hausdorff) = 1.f;
-    HIPCHK(c, launch_set_grad(sd, sg, st));
+    HIPCHK(c, launch_set_grad(sd, rows, sg, st));
     return AG_OK;
 }
 

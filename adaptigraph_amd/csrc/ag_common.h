@@ -481,6 +481,20 @@ hipError_t launch_pred_grad_scaled(const float* pred, const float* fut, const fl
 // Chamfer, Hausdorff and Earth-mover over a batch of cloud pairs, reference src/dynamics/gnn/loss.py.  Kinds as AG_LOSS_* of the
 // C-ABI.
 constexpr int SET_LOSS_MSE = 0, SET_LOSS_CHAMFER = 1, SET_LOSS_HAUSDORFF = 2, SET_LOSS_EMD = 3;
+// AG_LOSS_ROWS, or-ed onto a set kind: every graph's real rows are a prefix, x[b, :nx[b]] and y[b, :ny[b]]; the rows behind the
+// counts are never read.  A graph with an empty side is wholly empty.  The kernels are templates on the flag: ROWS = false is the
+// code of the plain kinds, the same arithmetic in the same order.
+constexpr int SET_LOSS_ROWS = 16;
+struct SetRows {                        // both null: the plain kinds
+    const int* nx; const int* ny;       // (B) each, as the caller gave them: clamped into [0, N] / [0, M] where they are read
+};
+// a count clamped into [0, n], before it bounds a loop or addresses anything
+__device__ __forceinline__ int clamp_count(int v, int n) { return v < 0 ? 0 : (v > n ? n : v); }
+// graph b's real rows (nx, ny) under ROWS: the clamped counts, both 0 when either side is empty
+__device__ __forceinline__ void set_rows_of(const SetRows& r, int b, int N, int M, int& nx, int& ny) {
+    nx = clamp_count(r.nx[b], N); ny = clamp_count(r.ny[b], M);
+    if (nx == 0 || ny == 0) nx = ny = 0;
+}
 // what the set-loss kernels of both files share: the fp32 distance, every operation rounded on its own
 __device__ __forceinline__ float set_dist(float ax, float ay, float az, float bx, float by, float bz) {
     const float dx = __fsub_rn(ax, bx), dy = __fsub_rn(ay, by), dz = __fsub_rn(az, bz);
@@ -522,11 +536,14 @@ struct StepLossDev {                    // closes step fi of a chained training 
 };
 size_t set_loss_part_doubles(int B);
 size_t set_loss_part_ints(int B);
-hipError_t launch_set_nn(const SetLossDev& a, hipStream_t st);
-// kind SET_LOSS_EMD reads emd_part (B doubles of k_emd_assign) and neither a.part, a.pidx nor win
+// rows.nx non-null: the ROWS instance of the kernel; the partials are then per-graph means, the arg-min entries of padding rows 0
+hipError_t launch_set_nn(const SetLossDev& a, const SetRows& rows, hipStream_t st);
+// kind SET_LOSS_EMD reads emd_part (B doubles of k_emd_assign) and neither a.part, a.pidx nor win; kind may carry SET_LOSS_ROWS
 hipError_t launch_set_final(const SetLossDev& a, const double* emd_part, int B_total, int kind, float* out, int* win, hipStream_t st);
-hipError_t launch_step_loss_final(const StepLossDev& a, hipStream_t st);
-hipError_t launch_set_grad(const SetLossDev& a, const SetGradDev& g, hipStream_t st);
+hipError_t launch_step_loss_final(const StepLossDev& a, hipStream_t st);   // a.kind[] may carry SET_LOSS_ROWS
+hipError_t launch_set_grad(const SetLossDev& a, const SetRows& rows, const SetGradDev& g, hipStream_t st);
+// n[b] = the first i < n_p with attrs[b, i, 0] <= 0, or n_p: the live prefix of a padded training batch (attrs (B, N, 2))
+hipError_t launch_prefix_rows(const float* attrs, int B, int N, int n_p, int* n, hipStream_t st);
 
 // Earth-mover loss (ag_emd.hip; reference loss.py:25-60): the exact one-to-one matching of min(N, M) pairs per graph.
 constexpr int EMD_MAX_MATCH = 512;      // K = min(N, M) served: the serial search steps of one graph are at most K (K + 1) / 2
@@ -540,8 +557,8 @@ struct EmdDev {
     double* part;                       // (B): sum of the matched fp32 distances in ascending i; NaN for a failed graph
 };
 size_t emd_max_points();                // N + M that fits the LDS tile with the solver's arrays beside the clouds
-hipError_t launch_emd_assign(const EmdDev& a, hipStream_t st);
-hipError_t launch_emd_grad(const EmdDev& a, const SetGradDev& g, hipStream_t st);
+hipError_t launch_emd_assign(const EmdDev& a, const SetRows& rows, hipStream_t st);
+hipError_t launch_emd_grad(const EmdDev& a, const SetRows& rows, const SetGradDev& g, hipStream_t st);
 
 // ---- device-resident physics-parameter fit (ag_ppm.hip; ag_ppm_grad_step, ag_ppm_adam_step): the glue of the masked rollout
 // (forward_dynamics.py:209-399) around the forwards and the backward chunks, and the per-start reduction + Adam.  Rows [0,L) of a

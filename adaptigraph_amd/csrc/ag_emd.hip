@@ -23,6 +23,8 @@
 //   finaliser    k_set_final / k_step_loss_final (ag_setloss.hip): the B partials in index order in fp64, / (B_total K), one rounding.
 //   k_emd_grad   g_x[b,i] = s (x_i - y_match(i)) / dist with s = g_out w / (B_total K); zero at zero distance and for an unmatched
 //                x_i (N > M only).  One writer per element: overwrites, or adds to the chain's dLoss/dpred.
+// REAL ROWS (AG_LOSS_ROWS, template <bool ROWS>): the matching runs over the prefixes x[b, :nx_b], y[b, :ny_b] with K_b = min(nx_b,
+// ny_b) pairs, the loss is the mean over graphs of sum_b matched / K_b, the gradient scale g_out w / (B_total K_b); see k_emd_assign.
 #include "ag_common.h"
 
 namespace ag {
@@ -63,30 +65,44 @@ __device__ __forceinline__ void block_argmin_f64(double& v, int& k, double (*sh)
 // path[L] scanned[L]  = 24 K + 40 L bytes
 __host__ __device__ inline size_t emd_lds_bytes(int K, int L) { return (size_t)24 * K + (size_t)40 * L; }
 
-template <int NT>
-__global__ __launch_bounds__(NT) void k_emd_assign(EmdDev a) {
+// ROWS: the graph's clouds are the prefixes x[b, :nx], y[b, :ny] (set_rows_of).  K, L and the row side come from these clamped
+// counts, before any loop is entered, so every loop below keeps its bound; the LDS arrays are carved for the padded sizes
+// (Kp = min(N, M) >= K, Lp = max(N, M) >= L).  An empty graph is solved by nothing: match -1, partial 0, status EMD_OK.  Padding
+// rows are never read; their match entries are -1; the partial is the graph's own mean, sum of matched / K.
+template <int NT, bool ROWS>
+__global__ __launch_bounds__(NT) void k_emd_assign(EmdDev a, SetRows rw) {
     extern __shared__ __attribute__((aligned(16))) unsigned char emd_sm[];
     __shared__ double sh[2][NT / 64];
     __shared__ int shk[2][NT / 64];
     __shared__ int s_fail;
     const int b = blockIdx.x, tid = threadIdx.x;
     const int N = a.N, M = a.M;
-    const bool xrows = N <= M;                                  // the smaller cloud is the row side, x when N == M
-    const int K = xrows ? N : M, L = xrows ? M : N;
+    int nx = N, ny = M;
+    if constexpr (ROWS) set_rows_of(rw, b, N, M, nx, ny);
+    int* match = a.match + (long)b * N;
+    if constexpr (ROWS) {
+        if (nx == 0) {                                          // uniform: an empty graph adds 0 and matches nothing
+            for (int i = tid; i < N; i += NT) match[i] = -1;
+            if (tid == 0) { a.part[b] = 0.0; a.status[b] = EMD_OK; }
+            return;
+        }
+    }
+    const bool xrows = nx <= ny;                                // the smaller cloud is the row side, x when N == M
+    const int K = xrows ? nx : ny, L = xrows ? ny : nx;
+    const int Kp = N <= M ? N : M, Lp = N <= M ? M : N;         // the carving; Kp == K and Lp == L without ROWS
     double* u = reinterpret_cast<double*>(emd_sm);              // [K] row duals
-    double* v = u + K;                                          // [L] column duals
-    double* sp = v + L;                                         // [L] cost of the cheapest path found to a column in this search
-    float* rs = reinterpret_cast<float*>(sp + L);               // [3][K]
-    float* cs = rs + 3 * K;                                     // [3][L]
-    int* col4row = reinterpret_cast<int*>(cs + 3 * L);          // [K]
-    int* row4col = col4row + K;                                 // [L]
-    int* path = row4col + L;                                    // [L] the row a column's cheapest path comes from
-    int* scanned = path + L;                                    // [L]
+    double* v = u + Kp;                                         // [L] column duals
+    double* sp = v + Lp;                                        // [L] cost of the cheapest path found to a column in this search
+    float* rs = reinterpret_cast<float*>(sp + Lp);              // [3][K]
+    float* cs = rs + 3 * Kp;                                    // [3][L]
+    int* col4row = reinterpret_cast<int*>(cs + 3 * Lp);         // [K]
+    int* row4col = col4row + Kp;                                // [L]
+    int* path = row4col + Lp;                                   // [L] the row a column's cheapest path comes from
+    int* scanned = path + Lp;                                   // [L]
     const float* xr = a.x + (long)b * a.x_bstride;
     const float* yr = a.y + (long)b * a.y_bstride;
     const float* rr = xrows ? xr : yr;
     const float* cr = xrows ? yr : xr;
-    int* match = a.match + (long)b * N;
     int bad = 0;
     for (int i = tid; i < K; i += NT) {
         const float p = rr[3 * i], q = rr[3 * i + 1], r = rr[3 * i + 2];
@@ -163,12 +179,12 @@ __global__ __launch_bounds__(NT) void k_emd_assign(EmdDev a) {
         if (tid == 0) { a.part[b] = __builtin_nan(""); a.status[b] = fail; }
         return;
     }
-    for (int i = tid; i < N; i += NT) {                         // N <= L: sp has room for every x_i's matched distance
-        const int m = xrows ? col4row[i] : row4col[i];
+    for (int i = tid; i < N; i += NT) {                         // N <= Lp: sp has room for every x_i's matched distance
+        const int m = (!ROWS || i < nx) ? (xrows ? col4row[i] : row4col[i]) : -1;
         match[i] = m;
         double d = 0.0;
         if (m >= 0) {
-            const int c = clampi(m, M);
+            const int c = clampi(m, ny);
             d = xrows ? (double)set_dist(rs[i], rs[K + i], rs[2 * K + i], cs[c], cs[L + c], cs[2 * L + c])
                       : (double)set_dist(cs[i], cs[L + i], cs[2 * L + i], rs[c], rs[K + c], rs[2 * K + c]);
         }
@@ -178,14 +194,19 @@ __global__ __launch_bounds__(NT) void k_emd_assign(EmdDev a) {
     if (tid == 0) {
         double s = 0.0;
         for (int i = 0; i < N; ++i) s += sp[i];                 // ascending i; an unmatched x_i adds +0
-        a.part[b] = s;
+        a.part[b] = ROWS ? s / (double)K : s;
         a.status[b] = EMD_OK;
     }
 }
 
-__global__ __launch_bounds__(ET) void k_emd_grad(EmdDev a, SetGradDev g) {
+// ROWS: the scale is the graph's own 1 / (B_total K_b); padding rows get exact zeros, a failed graph NaN in its real rows only
+template <bool ROWS>
+__global__ __launch_bounds__(ET) void k_emd_grad(EmdDev a, SetRows rw, SetGradDev g) {
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int K = a.N < a.M ? a.N : a.M;
+    int nx = a.N, ny = a.M;
+    if constexpr (ROWS) set_rows_of(rw, b, a.N, a.M, nx, ny);
+    const int Kb = nx < ny ? nx : ny;
+    const int K = ROWS ? (Kb > 0 ? Kb : 1) : (a.N < a.M ? a.N : a.M);    // an empty graph has no real row to scale
     const float go = g.gout ? g.gout[0] : 1.f;
     const float s = (float)((double)go * g.w_emd / ((double)g.B_total * K));      // the mean's 1 / (B_total K)
     const bool failed = a.status[b] != EMD_OK;
@@ -196,8 +217,9 @@ __global__ __launch_bounds__(ET) void k_emd_grad(EmdDev a, SetGradDev g) {
     for (int i = tid; i < a.N; i += ET) {
         float v[3] = {0.f, 0.f, 0.f};
         const int m = match[i];
-        if (failed) v[0] = v[1] = v[2] = __builtin_nanf("");
-        else if (m >= 0) set_pull(xr + 3 * i, yr + 3 * clampi(m, a.M), s, v);
+        if (ROWS && i >= nx) {}
+        else if (failed) v[0] = v[1] = v[2] = __builtin_nanf("");
+        else if (m >= 0) set_pull(xr + 3 * i, yr + 3 * clampi(m, ny), s, v);
         if (g.add) { gr[3 * i] += v[0]; gr[3 * i + 1] += v[1]; gr[3 * i + 2] += v[2]; }
         else { gr[3 * i] = v[0]; gr[3 * i + 1] = v[1]; gr[3 * i + 2] = v[2]; }
     }
@@ -206,22 +228,27 @@ __global__ __launch_bounds__(ET) void k_emd_grad(EmdDev a, SetGradDev g) {
 
 size_t emd_max_points() { return EMD_LDS_BUDGET / 40 - 2; }     // 40 bytes a point covers 24 K + 40 L
 
-hipError_t launch_emd_assign(const EmdDev& a, hipStream_t st) {
+hipError_t launch_emd_assign(const EmdDev& a, const SetRows& rows, hipStream_t st) {
     const int K = a.N < a.M ? a.N : a.M, L = a.N < a.M ? a.M : a.N;
     static unsigned long long attr_devices = 0;                 // per-device function attribute (see launch_chamfer)
     int dev_id = 0;
     if (hipGetDevice(&dev_id) != hipSuccess) dev_id = 0;
     if (dev_id >= 64 || !(attr_devices >> dev_id & 1ull)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_emd_assign<EA>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           EMD_LDS_BUDGET);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_emd_assign<EA, false>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, EMD_LDS_BUDGET);
+        if (e != hipSuccess) return e;
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_emd_assign<EA, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                EMD_LDS_BUDGET);
         if (e != hipSuccess) return e;
         if (dev_id < 64) attr_devices |= 1ull << dev_id;
     }
-    hipLaunchKernelGGL(k_emd_assign<EA>, dim3(a.B), dim3(EA), emd_lds_bytes(K, L), st, a);
+    if (rows.nx) hipLaunchKernelGGL((k_emd_assign<EA, true>), dim3(a.B), dim3(EA), emd_lds_bytes(K, L), st, a, rows);
+    else hipLaunchKernelGGL((k_emd_assign<EA, false>), dim3(a.B), dim3(EA), emd_lds_bytes(K, L), st, a, rows);
     return hipGetLastError();
 }
-hipError_t launch_emd_grad(const EmdDev& a, const SetGradDev& g, hipStream_t st) {
-    hipLaunchKernelGGL(k_emd_grad, dim3(a.B), dim3(ET), 0, st, a, g);
+hipError_t launch_emd_grad(const EmdDev& a, const SetRows& rows, const SetGradDev& g, hipStream_t st) {
+    if (rows.nx) hipLaunchKernelGGL(k_emd_grad<true>, dim3(a.B), dim3(ET), 0, st, a, rows, g);
+    else hipLaunchKernelGGL(k_emd_grad<false>, dim3(a.B), dim3(ET), 0, st, a, rows, g);
     return hipGetLastError();
 }
 

@@ -132,11 +132,14 @@ class TrainStep:
     [(term, weight), ...] of up to four terms, a term being "mse", "chamfer", "hausdorff" or an instance of torch.nn.MSELoss,
     ChamferLoss, HausdorffLoss, EarthMoverLoss (LossSpec checks it on the host).  step, evaluate, accumulate, apply and step_parts then run
     ag_train_step_losses; .last_loss_terms holds every step's terms before weighting, (n_future, n_terms) on the device.  A
-    Hausdorff term is a max over the whole batch: accumulate, step_parts and group= raise ValueError with one."""
+    Hausdorff term is a max over the whole batch: accumulate, step_parts and group= raise ValueError with one.
+    real_rows=True: every set term of the list runs over each graph's real rows - its live prefix, the first i with
+    attrs[b, i, 0] <= 0 - on the prediction and the label alike (set_losses.py, REAL ROWS); the batches DeviceDynDataset builds
+    are padded, and the set losses must not see the padding.  An MSE term keeps running over all rows, as in train.py."""
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, n_future=3, store_rest_state=False,
-                 group=None, global_rows=None, losses=None):
-        self.losses = LossSpec(losses)                          # host checks first: nothing below runs for a bad list
+                 group=None, global_rows=None, losses=None, real_rows=False):
+        self.losses = LossSpec(losses, real_rows=real_rows)   # host checks first: nothing below runs for a bad list
         if group is not None:
             self.losses.forbid_parts("__init__(group=...)")
         params = model.ordered_parameters()

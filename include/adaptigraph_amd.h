@@ -560,9 +560,10 @@ int ag_train_step_part(ag_ctx* ctx, void* stream, const float* d_state, const fl
 #define AG_LOSS_CHAMFER 1
 #define AG_LOSS_HAUSDORFF 2
 #define AG_LOSS_EMD 3
+#define AG_LOSS_ROWS 16         /* flag, or-ed onto AG_LOSS_CHAMFER, _HAUSDORFF or _EMD: the loss over each graph's real rows (below) */
 typedef struct ag_loss_spec {
     int32_t n_terms;            /* 1..4 */
-    int32_t kind[4];            /* AG_LOSS_* */
+    int32_t kind[4];            /* AG_LOSS_*, a set kind optionally | AG_LOSS_ROWS */
     float weight[4];            /* finite */
 } ag_loss_spec;
 
@@ -574,8 +575,8 @@ typedef struct ag_loss_spec {
  *                      AG_ERR_UNSUPPORTED: a max does not split into parts)
  * The sums run in fp64 in a fixed order (inside a graph, then over the graphs in index order) and are rounded once.  Arg-min and
  * arg-max take the lowest index among equals.  A NaN coordinate makes the loss NaN.  N + M must fit the LDS tile of
- * ag_cost_chamfer (<= ~13k points), else AG_ERR_UNSUPPORTED before anything is enqueued.  No masks: every row counts, as in the
- * reference's training losses.
+ * ag_cost_chamfer (<= ~13k points), else AG_ERR_UNSUPPORTED before anything is enqueued.  The plain kinds count every row, as
+ * the reference's training losses do; kind | AG_LOSS_ROWS counts each graph's real rows (below).
  * d_work: NULL, or B*(N+M) + 4 int32 that receive the arg-min tables (per graph: nearest y of every x, then nearest x of every
  * y) and the Hausdorff winners {b, i, b, j}.  Enqueue only.
  *   AG_LOSS_EMD        sum_b sum_{(i,j) in A_b} d(b,i,j) / (B_total * K), K = min(N, M)    (loss.py:25-60; splits into parts through
@@ -589,7 +590,25 @@ typedef struct ag_loss_spec {
  * prints a message and reuses the previous graph's indices there; that is not reproduced.)
  * d_work for AG_LOSS_EMD: the same B*(N+M) + 4 int32, holding first the (B, N) match table - entry (b, i) is the y index matched
  * to x_i of graph b, or -1 (N > M: N - M rows stay unmatched; a failed graph: every row) - then B status words (0 solved, 1
- * non-finite input, 2 a loop bound ran out). */
+ * non-finite input, 2 a loop bound ran out).
+ *
+ * kind | AG_LOSS_ROWS (valid on the three set kinds only; AG_LOSS_MSE | AG_LOSS_ROWS is AG_ERR_INVALID): padded batches.  Graph b's
+ * real rows are the first nx[b] rows of x[b] and the first ny[b] rows of y[b].  d_work is then REQUIRED (NULL: AG_ERR_INVALID) and
+ * has B*(N+M) + 4 + 2B int32: everything before the last 2B words keeps the layout and meaning above, and the last 2B words are
+ * INPUTS, nx[0..B) then ny[0..B).  The counts are clamped into [0, N] and [0, M] on the device before they bound a loop or address
+ * anything; rows behind them are never read, so NaN or inf there changes no output bit.  d, the arg-min rule, the tie rules and
+ * NaN propagation are those above, over the real rows:
+ *   AG_LOSS_CHAMFER | AG_LOSS_ROWS    (1/B_total) sum_b [ (1/nx_b) sum_{i<nx_b} min_{j<ny_b} d + (1/ny_b) sum_{j<ny_b} min_{i<nx_b} d ]
+ *                      - the mean over graphs of each graph's own Chamfer distance, not the pooled mean; it splits into parts
+ *                      through B_total with no count exchanged.  With full counts it is the plain kind up to the last place.
+ *   AG_LOSS_HAUSDORFF | AG_LOSS_ROWS  max_{b, i<nx_b} mx + max_{b, j<ny_b} my; with full counts the plain kind's bits.  Refused in parts.
+ *   AG_LOSS_EMD | AG_LOSS_ROWS        (1/B_total) sum_b (1/K_b) sum_{(i,j) in A_b} d, K_b = min(nx_b, ny_b), A_b the optimal assignment of
+ *                      the real rows; the smaller real cloud is the row side, x when the counts are equal.  The limits stay on
+ *                      the padded sizes N, M.  A non-finite coordinate in a real row fails that graph alone.
+ * A graph with an empty side (nx_b == 0 or ny_b == 0) is batch padding, a rule of this library (torch's mean over nothing is
+ * NaN): it adds 0 to Chamfer and Earth-mover, has no Hausdorff candidate, its gradient rows are 0, and it still counts in
+ * B_total; with every graph empty Hausdorff is 0 and the winners are -1.  Arg-min entries of padding rows are 0, match entries of
+ * padding or unmatched rows -1. */
 int ag_set_loss(ag_ctx* ctx, void* stream, const float* d_x, const float* d_y, int32_t B, int32_t N, int32_t M, int32_t B_total,
                 int32_t kind, float* d_out, int32_t* d_work);
 
@@ -599,7 +618,10 @@ int ag_set_loss(ag_ctx* ctx, void* stream, const float* d_x, const float* d_y, i
  * again), or the buffer an ag_set_loss call on the same inputs and kind filled (its tables are used; indices are clamped before
  * they address anything).  No atomics: repeated calls give the same bits.  Enqueue only.
  * AG_LOSS_EMD: d_grad_x[b,i] = d_grad_out[0] / (B_total * K) * (x_i - y_j) / d(b,i,j) for the matched pair (i, j), zero for an
- * unmatched x_i and at zero distance, NaN in every row of a failed graph. */
+ * unmatched x_i and at zero distance, NaN in every row of a failed graph.
+ * kind | AG_LOSS_ROWS: d_work is required - the buffer of the forward, whose last 2B words hold the counts.  Rows i >= nx[b] are
+ * written as exact 0; a real row's scale is d_grad_out[0] / (B_total * nx_b) for the x-side Chamfer sum, / (B_total * ny_b) for
+ * the y-side sum, / (B_total * K_b) for Earth-mover; a failed Earth-mover graph has NaN in its real rows. */
 int ag_set_loss_backward(ag_ctx* ctx, void* stream, const float* d_x, const float* d_y, int32_t B, int32_t N, int32_t M,
                          int32_t B_total, int32_t kind, const float* d_grad_out, float* d_grad_x, const int32_t* d_work);
 
@@ -615,7 +637,11 @@ int ag_set_loss_backward(ag_ctx* ctx, void* stream, const float* d_x, const floa
  * is B / B_total), and on an Earth-mover term (AG_LOSS_EMD, a mean over the B_total * n_p matched pairs; n_p <= 512 and 2 * n_p
  * within its LDS tile, else AG_ERR_UNSUPPORTED).  A Hausdorff term with B_total != B or accumulate != 0 returns AG_ERR_UNSUPPORTED; an unknown kind, a
  * non-finite weight or n_terms outside 1..4 AG_ERR_INVALID; 2 * n_p beyond the LDS tile with a set term AG_ERR_UNSUPPORTED - all
- * before anything is enqueued.  spec = {1, {AG_LOSS_MSE}, {1}} gives ag_train_step_part's bits; ag_train_step and
+ * before anything is enqueued.  A set kind may carry AG_LOSS_ROWS (Chamfer and Hausdorff terms of one list must agree on it, and
+ * Earth-mover terms among themselves, else AG_ERR_INVALID): graph b's real rows, of the prediction and of d_state_future[:, fi]
+ * alike, are then its first n_b rows, n_b = the first i < n_p with d_attrs[b, i, 0] <= 0, or n_p if there is none - the live
+ * prefix that the device data set writes.  An MSE term of the same list runs over all rows, as in train.py.
+ * spec = {1, {AG_LOSS_MSE}, {1}} gives ag_train_step_part's bits; ag_train_step and
  * ag_train_step_part themselves are unchanged and never run this path.  Enqueue only. */
 int ag_train_step_losses(ag_ctx* ctx, void* stream, const float* d_state, const float* d_attrs, const float* d_action,
                          const float* d_phys, const float* d_group, int32_t n_inst, const int32_t* d_recv, const int32_t* d_send,

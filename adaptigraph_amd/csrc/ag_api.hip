@@ -32,7 +32,7 @@ const OptName kOptions[] = {
     {"share_prefix", "AG_SHARE_PREFIX", &Options::share_prefix, false, -1, 1},
     {"stream_min_rows", "AG_STREAM_MIN_ROWS", &Options::stream_min_rows, false, 0, 0x7fffffff},
     {"pipeline_fork", "AG_PIPELINE_FORK", &Options::pipeline_fork, false, 0, 1},
-    {"edge_order", "AG_EDGE_ORDER", &Options::edge_order, false, 0, 1},
+    {"edge_order", "AG_EDGE_ORDER", &Options::edge_order, false, 0, 2},
     {"ell_lds_words", "AG_ELL_LDS_WORDS", &Options::ell_lds_words, false, 0, 16384},
 };
 void options_from_env(Options& o) {   // values from the environment are clamped into the option's range
@@ -165,6 +165,16 @@ void carve_work(const ag_ctx* c, Slab& s, Work& w, int Bc, int N, int n_inst, in
         w.ns_edge = s.take<int>((size_t)Bc * edge_cap);
         w.n_ns = s.take<int>(Bc);
         w.n_oo = s.take<int>(Bc);
+        w.ck_bits = nullptr; w.ck_off = nullptr; w.ck_list = nullptr;
+        // chunk list of Options::edge_order 2.  Carved whatever edge_order, ell_graph and self_dedupe say now: they are options of the
+        // context and may change between calls; the cost is small.  4 bytes per (candidate, slot) of list, 2 bits of bitmap and
+        // 512 counters per candidate - about 6 MB at the bench shape, under 1 % of the C rows of the same slots (NFP floats each).
+        if (roll && ell_stride > 0) {
+            const size_t slots = (size_t)N * (ell_stride + N - N_o);   // a row owns top-k + M slots
+            w.ck_bits = s.take<unsigned long long>((size_t)Bc * 2 * ((slots + 63) / 64));
+            w.ck_off = s.take<int>(2 + slots + (size_t)CHUNK_TOOL_KEYS * Bc);
+            w.ck_list = s.take<unsigned>((size_t)Bc * edge_cap);
+        }
         w.g.recv = w.recv; w.g.send = w.send; w.g.row_ptr = w.row_ptr; w.g.n_edges = w.n_edges;
     }
     if (roll) {

@@ -371,6 +371,22 @@ int decide_prefix(RollCall& r) {
     return AG_OK;
 }
 
+// Options::edge_order 2 for one launch: the relation encoder reads ONE list over the launch's live candidates (EdgeArgs::ck_list).
+// Only where the fp32 throughput chain runs on the slot-indexed graph with the self-loop dedupe, and (candidate, slot) fits the 32-bit
+// entry; every other launch keeps order 1.  g.B = the launch's candidates (the latency chains take over small launches).
+void chunk_list_for(const RollCall& r, const Work& w, EdgeArgs& ea, GraphBufs& g) {
+    ag_ctx* c = r.c;
+    ea.ck_list = nullptr; ea.ck_bits = nullptr; ea.ck_off = nullptr; ea.ck_shift = 0;
+    g.ck_list = nullptr; g.ck_n = nullptr; g.ck_shift = 0;
+    if (c->opt.edge_order != 2 || !r.ell_full || !r.dedupe || !w.ck_list || g.wb3 || g.B <= 0 || lat_edge_for(c, g)) return;
+    const long slots = (long)r.N * (r.k + r.p->M);
+    int shift = 1;
+    while ((1L << shift) < slots) ++shift;
+    if (shift >= 32 || ((unsigned long)(g.B - 1) >> (32 - shift)) != 0) return;
+    ea.ck_list = w.ck_list; ea.ck_bits = w.ck_bits; ea.ck_off = w.ck_off; ea.ck_shift = shift;
+    g.ck_list = w.ck_list; g.ck_n = w.ck_off; g.ck_shift = shift;
+}
+
 // GraphBufs of workspace w for nb candidate slots; with the self-loop dedupe the two constant C rows are copied behind the
 // last candidate's C rows of the workspace.  Also sets the workspace's RollBufs flags.
 int workspace_graph(RollCall& r, Work& w, int nb, hipStream_t s, GraphBufs& g) {
@@ -456,7 +472,8 @@ int run_base_rollout(RollCall& r) {
     RollArgs ra = roll_args(r, 0, 1);
     ra.H = 1; ra.eef_xz = r.b_eef; ra.eef_delta = r.b_eef + 2 * p->M; ra.repeat = r.b_zero;
     ra.write_obj_cls = 1; ra.all_states = r.b_states; ra.all_y = r.b_y;
-    const EdgeArgs ea = workspace_edge_args(r, w, 1);        // (the parked tool has no object in reach: the cta rule's flag stays 0)
+    EdgeArgs ea = workspace_edge_args(r, w, 1);              // (the parked tool has no object in reach: the cta rule's flag stays 0)
+    chunk_list_for(r, w, ea, g);
     { Scoped sc(c, FAM_ROLL_INIT); HIPCHK(c, launch_roll_init(ra, w.r, g, st)); }
     { Scoped sc(c, FAM_NODE_ENC); HIPCHK(c, node_enc_for(c, g, 0, 2L * p->N_o + p->M, st)); }
     for (int ai = 1; ai <= r.R_base; ++ai) {
@@ -616,8 +633,12 @@ int enqueue_chunks(RollCall& r) {
                     ea.share_stats = sl.d_share_stats; g.C_share = r.C_share; g.share_kb = r.kb;
                     ea.share_start = r.d_start; ea.share_cand = ra.cand; ea.share_b0 = b0;
                 }
+                chunk_list_for(r, w, ea, g);
                 if (!(timing_skip & 1) || ai == 1) {
                     HIPCHK(c, launch_edge_build(ea, cs, prof_mark, c));
+#ifdef AG_DIAG
+                    diag_chunk_dump(c->diag, ea, p->M, cs);  // AG_CHUNK_DUMP (diagnostic build only)
+#endif
                     if (g.ns_edge && !r.ell_full) { Scoped s(c, FAM_EDGE_EMIT); HIPCHK(c, launch_edge_nonself(w.recv, w.send, w.row_ptr, n_live, N, r.edge_cap, w.ns_edge, w.n_ns, ea.live, cs)); }
                 }
                 rc = run_model(c, g, w.r.pred, w.r.motion, cs);

@@ -131,11 +131,16 @@ struct Options {
                               //                     0 does not bring back the 5-MFMA step: a step with both features live is two two-block
                               //                     MFMAs per tile pair either way (same bits); only a build with -DAG_HS_EDGE=0
                               //                     -DAG_HS_NODE=0 has the former code
-    int edge_order = 1;       // [AG_EDGE_ORDER]     order of the relation encoder's work list (k_ell_index): 0 = slot order (receiver-major),
+    int edge_order = 2;       // [AG_EDGE_ORDER]     order of the relation encoder's work list (k_ell_index): 0 = slot order (receiver-major),
                               //                     1 = class-major - object-object slots by the signs and the dominant axis of
                               //                     pos_r - pos_s (24 classes), then every slot with a tool at either end, slot order inside
                               //                     a class.  The wavefronts of k_edge_enc then hold like edges and more of their k-steps are
-                              //                     all zero (zero_skip).  A C row does not depend on the lane that computes it: same bits
+                              //                     all zero (zero_skip).  A C row does not depend on the lane that computes it: same bits.
+                              //                     2 = chunk list: ONE list per launch over all its live candidates (k_chunk_*), object-object
+                              //                     slots by the transposed slot index (position in row, receiver) - the same slot of every
+                              //                     candidate adjacent, in candidate order - then the tool slots by sector and ring of
+                              //                     pos_r - pos_s.  fp32 throughput chain on the slot-indexed rollout graphs only; every other
+                              //                     launch, and a chunk whose (candidate, slot) does not fit 32 bits, takes order 1
     int ell_lds_words = 0;    // [AG_ELL_LDS_WORDS]  debug: LDS budget of k_ell_index's class bitmaps in 64-bit words (0 = the built-in
                               //                     16384); below 25 bitmaps the classes fall back to (object-object, tool), then to one list
     int share_first = -1;     // [AG_SHARE_FIRST]    first forward of a dynamics() call: the relation encoder runs ONCE over the
@@ -144,6 +149,7 @@ struct Options {
 };
 
 // ---- launchers (defined in the .hip files) ------------------------------------------------------------
+constexpr int CHUNK_TOOL_KEYS = 32 * 16;   // tool keys of the chunk list (Options::edge_order 2): sectors x rings, ag_edges.hip: chunk_tool_key
 struct EdgeArgs {
     const float* pos;           // (B,N,3) with `pos_bstride` floats between candidates
     long pos_bstride;
@@ -175,6 +181,11 @@ struct EdgeArgs {
     // Options::edge_order 1: ns_edge is written class-major (see there) and n_oo[b] = entries in front of the tool class (0 when the
     // classes did not fit the LDS budget `lds_words` and the list stayed in slot order).  n_oo null: slot order, nothing written.
     int* n_oo; int lds_words;
+    // Options::edge_order 2 (ck_list non-null; ell_full only): k_ell_index leaves the candidate's two slot bitmaps (object-object,
+    // tool) in ck_bits (B, 2, words) instead of a list of its own (n_ns[b] is still the count, n_oo[b] 0), and k_chunk_count / _scan /
+    // _fill write ONE list over the live candidates: ck_list[t] = candidate << ck_shift | slot, sorted by key (chunk_key in
+    // ag_edges.hip), ck_off[0] = entries, ck_off[1] = entries in front of the first tool key, behind them the scan scratch.
+    unsigned long long* ck_bits; int* ck_off; unsigned* ck_list; int ck_shift;
     int block_min_rows;         // Options::edge_block_min (-1: built-in threshold)
     const int* live;            // null, or device int: candidates [*live, B) of this launch have no forward left (device-planned
                                 // rollout, RollPlan): their workgroups exit and their graphs are presented as empty
@@ -279,6 +290,9 @@ struct GraphBufs {
     long self_row;                         // row of C where c_self[0..1] were copied (k_mp reads them from there)
     const int* ns_edge; const int* n_ns;   // (B,edge_cap), (B,) or null
     const int* n_oo;                       // (B,) or null: class-major list (Options::edge_order), entries [n_oo[b], n_ns[b]) are tool edges
+    // chunk list (Options::edge_order 2, EdgeArgs::ck_list) or null: k_edge_enc's tile t takes entries [128 t, 128 t + 128) of ck_list,
+    // candidate << ck_shift | slot each; ck_n[0] = entries (device side: the grid stays the host's upper bound), ck_n[1] = object-object ones
+    const unsigned* ck_list; const int* ck_n; int ck_shift;
     const float* wb3;                      // bf16x3 weight image: non-null selects the bf16x3 chains (ag_mlp.hip)
     const int* n_guard;                    // ag_forward: guarded per-candidate edge counts (k_edge_guard), else null
     // ---- ragged batches (masked rollouts, forward_dynamics.py:286-309: every candidate has its own number of valid

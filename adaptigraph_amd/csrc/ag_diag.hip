@@ -10,11 +10,16 @@
 //   AG_TIMING_SKIP=mask       TIMING ONLY, WRONG RESULTS: the rollout's step loop leaves out the edge builder (bit 0; the graph of
 //                             a look-ahead step's first forward is kept) and / or k_roll_update (bit 1; only the capturing step
 //                             runs it) - the upper bound of what fusing those launches into a neighbour could save (r05)
+//   AG_CHUNK_DUMP=path        write the chunk list (Options::edge_order 2) of the context's AG_CHUNK_DUMP_AT-th launch that builds one
+//                             (default 0; synchronises!) to `path`, with the graph it was built from: int32 words B, N, stride,
+//                             edge_cap, shift, entries, object-object entries, tools; the list; deg (B, N); send (B, edge_cap);
+//                             positions (B, N, 3) as floats; the adjacency threshold (tests/test_gpu_chunk_order.py)
 #ifdef AG_DIAG
 #include "ag_common.h"
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 #include <vector>
 
 namespace ag {
@@ -22,6 +27,7 @@ namespace ag {
 struct Diag {
     int clock_left = 0, node_left = 0, fail_at_chunk = -1, timing_skip = 0;
     bool node_tail = false;
+    std::string chunk_dump; int chunk_dump_at = 0, chunk_lists = 0;
     unsigned long long* dbg_e = nullptr; unsigned cap_e = 0;
     unsigned long long* dbg_n = nullptr; unsigned cap_n = 0; unsigned tail_nwg = 0;
 };
@@ -32,10 +38,37 @@ void* diag_create() {
     if (const char* e = getenv("AG_NODE_PROBE")) { const int v = atoi(e); d->node_left = v > 0 ? v : 0; d->node_tail = v < 0; }
     if (const char* e = getenv("AG_TEST_FAIL_AT_CHUNK")) d->fail_at_chunk = atoi(e);
     if (const char* e = getenv("AG_TIMING_SKIP")) d->timing_skip = atoi(e);
+    if (const char* e = getenv("AG_CHUNK_DUMP")) d->chunk_dump = e;
+    if (const char* e = getenv("AG_CHUNK_DUMP_AT")) d->chunk_dump_at = atoi(e);
     return d;
 }
 int diag_fail_at_chunk(void* v) { return v ? static_cast<Diag*>(v)->fail_at_chunk : -1; }
 int diag_timing_skip(void* v) { return v ? static_cast<Diag*>(v)->timing_skip : 0; }
+
+void diag_chunk_dump(void* v, const EdgeArgs& ea, int n_tools, hipStream_t st) {
+    Diag* d = static_cast<Diag*>(v);
+    if (!d || d->chunk_dump.empty() || !ea.ck_list || d->chunk_lists++ != d->chunk_dump_at) return;
+    (void)hipStreamSynchronize(st);
+    int B = ea.B;
+    if (ea.live) { int live = 0; (void)hipMemcpy(&live, ea.live, 4, hipMemcpyDeviceToHost); B = std::min(B, live); }
+    int n[2] = {0, 0};
+    (void)hipMemcpy(n, ea.ck_off, 8, hipMemcpyDeviceToHost);
+    const int head[8] = {B, ea.N, ea.ell_stride, ea.edge_cap, ea.ck_shift, n[0], n[1], n_tools};
+    std::vector<int> list((size_t)n[0]), deg((size_t)B * ea.N), send((size_t)B * ea.edge_cap);
+    std::vector<float> pos((size_t)B * ea.N * 3);
+    if (n[0]) (void)hipMemcpy(list.data(), ea.ck_list, list.size() * 4, hipMemcpyDeviceToHost);
+    if (B) {
+        (void)hipMemcpy(deg.data(), ea.deg, deg.size() * 4, hipMemcpyDeviceToHost);
+        (void)hipMemcpy(send.data(), ea.send, send.size() * 4, hipMemcpyDeviceToHost);
+        (void)hipMemcpy2D(pos.data(), (size_t)ea.N * 12, ea.pos, (size_t)ea.pos_bstride * 4, (size_t)ea.N * 12, B, hipMemcpyDeviceToHost);
+    }
+    if (FILE* f = fopen(d->chunk_dump.c_str(), "wb")) {
+        fwrite(head, 4, 8, f);
+        fwrite(list.data(), 4, list.size(), f); fwrite(deg.data(), 4, deg.size(), f); fwrite(send.data(), 4, send.size(), f);
+        fwrite(pos.data(), 4, pos.size(), f); fwrite(&ea.thr, 4, 1, f);
+        fclose(f);
+    }
+}
 
 static double node_clock(const std::vector<unsigned long long>& h, unsigned nwg, int* n_out) {
     double ghz = 0; int n = 0;

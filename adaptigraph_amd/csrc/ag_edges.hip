@@ -51,7 +51,8 @@ struct EdgeDev {
     int* ell;                            // (B, N, k) kept non-merged senders per row (top-k active only)
     int ell_full, ell_stride; long ell_bstride;   // see EdgeArgs
     int* ns_edge; int* n_ns;
-    int* n_oo; int n_cls;                // k_ell_index<true>: bitmaps (25, or 2), entries in front of the tool class; see EdgeArgs
+    int* n_oo; int n_cls;                // k_ell_index<1>: bitmaps (25, or 2), entries in front of the tool class; see EdgeArgs
+    unsigned long long* ck_bits; int* ck_off; unsigned* ck_list; int ck_shift;   // k_ell_index<2>, k_chunk_*: see EdgeArgs
     int* deg; int* slice_tot; int* cta_flag;
     int* recv; int* send; int* row_ptr; int* n_edges; int* overflow; int max_nR; int zero_on_overflow;
     int block_min_rows;                  // slices with at least this many rows take the 64-rows-per-wavefront path
@@ -741,18 +742,41 @@ __device__ __forceinline__ int edge_class(const float* __restrict__ p, int i, in
     if (fabsf(dz) > m) ax = 2;
     return ((dx < 0.0f ? 1 : 0) | (dy < 0.0f ? 2 : 0) | (dz < 0.0f ? 4 : 0)) * 3 + ax;
 }
-template <bool CLS>
+// key of a tool slot in the chunk list (Options::edge_order 2, see k_chunk_count below): sector * 16 + ring of d = pos_i - pos_j
+__device__ __forceinline__ int chunk_tool_key(const float* __restrict__ p, int i, int j, float thr2) {
+    const float dx = __fsub_rn(p[3 * i + 0], p[3 * j + 0]), dy = __fsub_rn(p[3 * i + 1], p[3 * j + 1]), dz = __fsub_rn(p[3 * i + 2], p[3 * j + 2]);
+    const float ax = fabsf(dx), az = fabsf(dz);
+    const bool swap = az > ax;
+    const float mn = swap ? ax : az, mx = swap ? az : ax;
+    const int fine = (mn >= __fmul_rn(0.19891237f, mx) ? 1 : 0) + (mn >= __fmul_rn(0.41421357f, mx) ? 1 : 0) +
+                     (mn >= __fmul_rn(0.66817864f, mx) ? 1 : 0);   // tan of 11.25, 22.5, 33.75 degrees
+    const int sector = ((dx < 0.0f ? 1 : 0) | (dz < 0.0f ? 2 : 0) | (swap ? 4 : 0)) * 4 + fine;
+    const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+    int ring = 0;
+#pragma unroll
+    for (int k = 1; k < 16; ++k) ring += d2 >= __fmul_rn((float)(k * k), thr2) ? 1 : 0;
+    return sector * 16 + ring;
+}
+// MODE 0: slot order, 1: class-major (CLS), 2: the candidate's two slot bitmaps go to global memory for the chunk list (below), with
+// the count of its tool slots per key (an LDS histogram, stored key-major), and no list is written here - one pass, no scan.
+template <int MODE>
 __global__ __launch_bounds__(EW) void k_ell_index(EdgeDev a) {
+    constexpr bool CLS = MODE == 1;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned long long* bits = reinterpret_cast<unsigned long long*>(smem);
     __shared__ int wave_tot[EWAVES];
     __shared__ int n_shared;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ int tool_hist[MODE == 2 ? CHUNK_TOOL_KEYS : 1];
+    static_assert(CHUNK_TOOL_KEYS <= EW, "one thread per tool key");
+    int* tool_cnt = MODE == 2 ? a.ck_off + 2 + a.N * a.ell_stride + (long)b * CHUNK_TOOL_KEYS : nullptr;   // [candidate][key]
     if (a.live && b >= *a.live) {                           // no forward left: nothing for the relation encoder to do
+        if (MODE == 2 && tid < CHUNK_TOOL_KEYS) tool_cnt[tid] = 0;
         if (tid == 0) { a.n_ns[b] = 0; a.n_edges[b] = 0; if (a.n_oo) a.n_oo[b] = 0; }
         return;
     }
     if (tid == 0) n_shared = 0;
+    if (MODE == 2 && tid < CHUNK_TOOL_KEYS) tool_hist[tid] = 0;   // (barriers below, before pass 1)
     // edges of the candidate = sum of its slice totals: one load per thread and a reduction (a loop over the slices in every
     // thread is a chain of dependent scalar loads - 127 of them for one cloth-sized graph: most of the kernel's 24 us)
     int total = 0;
@@ -786,7 +810,9 @@ __global__ __launch_bounds__(EW) void k_ell_index(EdgeDev a) {
     const float* cpos = a.pos + (long)b * a.pos_bstride;
     const uint8_t* ctool = a.tool + (long)b * a.N;
     // ---- pass 1: one slot per lane
-    int shared = 0;
+    int shared = 0, kept = 0;
+    unsigned long long* gbits = MODE == 2 ? a.ck_bits + (long)b * 2 * nw : nullptr;
+    const float ck_thr2 = MODE == 2 ? thr2_of(a, b, thr_of(a, b)) : 0.0f;
     constexpr int UN = 8;                                   // words per wavefront and trip: the loads of all eight are issued together
     for (int eb = wave * 64; eb < nw * 64; eb += UN * EW) { // wave-uniform trip count: the ballots below see whole words
       int iu[UN], du[UN], ju[UN];
@@ -819,7 +845,14 @@ __global__ __launch_bounds__(EW) void k_ell_index(EdgeDev a) {
             pk[e] = v;
         }
         if (valid) recv[e] = i;
-        if (CLS) {
+        if (MODE == 2) {
+            bool tl = false;
+            if (own) tl = (ctool[i] | ctool[j]) != 0;
+            if (tl) atomicAdd(&tool_hist[chunk_tool_key(cpos, i, j, ck_thr2)], 1);
+            const unsigned long long bo = __ballot(own && !tl), bt = __ballot(tl);
+            if (lane == 0) { gbits[e0 >> 6] = bo; gbits[nw + (e0 >> 6)] = bt; }
+            kept += __popcll(bo) + __popcll(bt);            // (wave-uniform)
+        } else if (CLS) {
             int cls = 0;
             if (own) cls = (ctool[i] | ctool[j]) ? K - 1 : (K == 2 ? 0 : edge_class(cpos, i, j));
             unsigned long long keep = 0;
@@ -835,14 +868,16 @@ __global__ __launch_bounds__(EW) void k_ell_index(EdgeDev a) {
       }
     }
     if (hide) for (int i = tid; i < a.N; i += EW) deg[i] = 0;
+    if (MODE == 2 && lane == 63) wave_tot[wave] = kept;
     __syncthreads();
     // ---- pass 2: contiguous words per thread, block scan of the popcounts, set bits out in slot order
-    const int nwt = K * nw;                                 // the class bitmaps as one run of words
+    const int nwt = MODE == 2 ? 0 : K * nw;                 // the class bitmaps as one run of words
     const int per = (nwt + EW - 1) / EW;
     const int w0 = min(nwt, tid * per), w1 = min(nwt, w0 + per);
     int mine = 0;
     for (int w = w0; w < w1; ++w) mine += __popcll(bits[w]);
     int incl = mine;
+    if (MODE != 2) {
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
         const int v = __shfl_up(incl, o);
@@ -850,11 +885,14 @@ __global__ __launch_bounds__(EW) void k_ell_index(EdgeDev a) {
     }
     if (lane == 63) wave_tot[wave] = incl;
     __syncthreads();
+    }
     int before = 0, all = 0;
 #pragma unroll
     for (int w = 0; w < EWAVES; ++w) { const int v = wave_tot[w]; before += w < wave ? v : 0; all += v; }
     int pos = before + incl - mine;
-    if (CLS) {
+    if (MODE == 2) {
+        if (tid < CHUNK_TOOL_KEYS) tool_cnt[tid] = tool_hist[tid];   // (complete: the barrier behind pass 1)
+    } else if (CLS) {
         const int wt = (K - 1) * nw;                        // first word of the tool class
         for (int w = w0; w < w1; ++w) {
             if (w == wt) a.n_oo[b] = pos;                   // (exactly one thread's run holds word wt: nw > 0)
@@ -882,12 +920,140 @@ __global__ __launch_bounds__(EW) void k_ell_index(EdgeDev a) {
     }
     if (tid == EW - 1) {
         a.n_ns[b] = all;
-        if (!CLS && a.n_oo) a.n_oo[b] = 0;                  // slot order: no tool segment, every tile of k_edge_enc carries a full mask
+        if (!CLS && a.n_oo) a.n_oo[b] = 0;                  // slot order / chunk list: no tool segment of the candidate's own
         a.n_edges[b] = hide ? 0 : total;
         if (a.overflow && total > a.max_nR) atomicMax(a.overflow, total);
         if (pk && a.share_stats) {                           // integer counters: order-free
             atomicAdd(a.share_stats + 0, (unsigned long long)n_shared);
             atomicAdd(a.share_stats + 1, (unsigned long long)all);
+        }
+    }
+}
+
+// ---- chunk list (Options::edge_order 2): ONE work list for the relation encoder per launch, over all live candidates.  A wavefront
+// of k_edge_enc can leave a k-step out only if the feature is zero in all 32 of its rows, and 32 consecutive entries of one
+// candidate's list are not that alike; the candidates of a chunk start from one cloth and stay close to it, so the SAME slot of 32
+// candidates is (tools/chunk_order_census.py restates the key; profiles/chunk_order_census.txt).  Counting sort by key, three small
+// kernels behind k_ell_index<2>, which left every candidate's slot bitmaps (object-object, tool) in ck_bits and its tool-key counts:
+//   * object-object slot (receiver i, position t in the row): key = t * N + i, the transposed slot index - consecutive keys are the
+//     same position (senders ascend along a row: on a grid, the same direction) of consecutive receivers, so the four wavefronts of
+//     a tile are alike too.  Entries of one key in candidate order, compacted: a slot few candidates hold wastes no tile;
+//   * a slot with a tool at either end: behind every object-object key, key = N * stride + sector * 16 + ring of d = pos_r - pos_s at
+//     the frame the builder read, by comparisons only (a NaN compares false: sector bits 0, ring 0) - 32 sectors of 11.25 degrees in
+//     the x-z plane, rings |d|^2 >= k^2 thr^2, k = 1..15.  Inside a key by candidate, and inside a candidate in arrival order (integer
+//     atomics; no result can depend on it: a C row is stored by slot, and a row's chain does not depend on lane, workgroup or launch).
+// ck_off[0] = entries, ck_off[1] = object-object entries; behind them the counts, then first entries, of the N * stride object-object
+// keys and of the tool (candidate, key) pairs [candidate * CHUNK_TOOL_KEYS + key] (a key's entries: candidate by candidate).
+constexpr int CKW = 256;                                    // four wavefronts, one 64-slot word each
+static_assert(CHUNK_TOOL_KEYS == 32 * 16, "chunk_tool_key: 32 sectors x 16 rings");
+// object-object counts: a wavefront takes one 64-slot word, lane l loads that word of candidate 64 g + l, and 64 ballots transpose
+// the group: ballot s = the candidates that hold slot s.  Lane s keeps the count of its slot.
+__global__ __launch_bounds__(CKW) void k_chunk_count(EdgeDev a) {
+    const int lane = threadIdx.x & 63;
+    const int nslots = a.N * a.ell_stride, nw = (nslots + 63) >> 6;
+    const int w = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (CKW / 64) + (threadIdx.x >> 6)));
+    if (w >= nw) return;
+    const int live = a.live ? min(*a.live, a.B) : a.B;
+    int n = 0;
+    for (int b0 = 0; b0 < live; b0 += 64) {
+        const unsigned long long m = b0 + lane < live ? a.ck_bits[(long)(b0 + lane) * 2 * nw + w] : 0ull;
+#pragma unroll
+        for (int s = 0; s < 64; ++s) {
+            const unsigned long long who = __ballot((m >> s & 1ull) != 0);
+            if (lane == s) n += __popcll(who);
+        }
+    }
+    const int e = w * 64 + lane;
+    if (e < nslots) { const int i = e / a.ell_stride, t = e - i * a.ell_stride; a.ck_off[2 + t * a.N + i] = n; }
+}
+// the entries.  Workgroups [0, words / 4): object-object, as k_chunk_count - lane l = candidate 64 g + l writes its entry of slot s
+// behind the entries of the candidates in front of it (one coalesced run per slot and group; lane s carries the slot's next entry).
+// Workgroups behind them, words / 4 per candidate: a lane with a tool slot takes the next entry of its (key, candidate).
+__global__ __launch_bounds__(CKW) void k_chunk_fill(EdgeDev a) {
+    const int lane = threadIdx.x & 63;
+    const int nslots = a.N * a.ell_stride, nw = (nslots + 63) >> 6, wgs = (nw + CKW / 64 - 1) / (CKW / 64);
+    const int blk = (int)blockIdx.x % wgs, part = (int)blockIdx.x / wgs;
+    const int w = __builtin_amdgcn_readfirstlane(blk * (CKW / 64) + (int)(threadIdx.x >> 6));
+    if (w >= nw) return;
+    const int live = a.live ? min(*a.live, a.B) : a.B;
+    const int e = w * 64 + lane;
+    if (part == 0) {
+        int next = 0;                                       // lane s: next entry of slot 64 w + s
+        if (e < nslots) { const int i = e / a.ell_stride, t = e - i * a.ell_stride; next = a.ck_off[2 + t * a.N + i]; }
+        for (int b0 = 0; b0 < live; b0 += 64) {
+            const unsigned long long m = b0 + lane < live ? a.ck_bits[(long)(b0 + lane) * 2 * nw + w] : 0ull;
+            const unsigned cand = (unsigned)(b0 + lane) << a.ck_shift | (unsigned)(w * 64);
+#pragma unroll
+            for (int s = 0; s < 64; ++s) {
+                const bool mine = (m >> s & 1ull) != 0;
+                const unsigned long long who = __ballot(mine);
+                const int at = __builtin_amdgcn_readlane(next, s);
+                if (mine) a.ck_list[at + __popcll(who & lanes_below(lane))] = cand | (unsigned)s;
+                if (lane == s) next += __popcll(who);
+            }
+        }
+        return;
+    }
+    const int b = part - 1;
+    if (b >= live) return;
+    const unsigned long long m = a.ck_bits[((long)b * 2 + 1) * nw + w];
+    if (!(m >> lane & 1ull)) return;
+    const int i = e / a.ell_stride;
+    const int j = a.ell[(long)b * a.ell_bstride + e];
+    const int key = chunk_tool_key(a.pos + (long)b * a.pos_bstride, i, j, thr2_of(a, b, thr_of(a, b)));
+    const int at = atomicAdd(a.ck_off + 2 + nslots + (long)b * CHUNK_TOOL_KEYS + key, 1);
+    a.ck_list[at] = (unsigned)b << a.ck_shift | (unsigned)e;
+}
+// one workgroup: exclusive scan of the N * stride object-object counts and, behind them, of the tool keys' totals over the candidates;
+// the thread of a tool key then hands the key's entries out candidate by candidate.  In place.
+__global__ __launch_bounds__(EW) void k_chunk_scan(EdgeDev a) {
+    __shared__ int wave_tot[EWAVES];
+    __shared__ int ktot[CHUNK_TOOL_KEYS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nslots = a.N * a.ell_stride, nk = nslots + CHUNK_TOOL_KEYS;
+    int* off = a.ck_off + 2;
+    int* tool = off + nslots;                               // [candidate][key], every candidate of the launch written by k_ell_index<2>
+    if (tid < CHUNK_TOOL_KEYS) {
+        int tot = 0;
+#pragma unroll 8
+        for (int b = 0; b < a.B; ++b) tot += tool[(long)b * CHUNK_TOOL_KEYS + tid];
+        ktot[tid] = tot;
+    }
+    __syncthreads();
+    const int per = (nk + EW - 1) / EW;
+    const int k0 = min(nk, tid * per), k1 = min(nk, k0 + per);
+    int mine = 0;
+    for (int k = k0; k < k1; ++k) mine += k < nslots ? off[k] : ktot[k - nslots];
+    int incl = mine;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int v = __shfl_up(incl, o);
+        if (lane >= o) incl += v;
+    }
+    if (lane == 63) wave_tot[wave] = incl;
+    __syncthreads();
+    int before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < EWAVES; ++w) { const int v = wave_tot[w]; before += w < wave ? v : 0; all += v; }
+    int pos = before + incl - mine;
+    for (int k = k0; k < k1; ++k) {
+        if (k == nslots) a.ck_off[1] = pos;                 // (exactly one thread's run holds the first tool key)
+        if (k < nslots) { const int n = off[k]; off[k] = pos; pos += n; }
+        else { const int n = ktot[k - nslots]; ktot[k - nslots] = pos; pos += n; }   // (a thread's own run: no other thread reads it before the barrier)
+    }
+    if (tid == 0) a.ck_off[0] = all;
+    __syncthreads();
+    if (tid < CHUNK_TOOL_KEYS) {
+        int at = ktot[tid];
+        for (int b0 = 0; b0 < a.B; b0 += 8) {
+            int n[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) n[u] = b0 + u < a.B ? tool[(long)(b0 + u) * CHUNK_TOOL_KEYS + tid] : 0;
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                if (b0 + u < a.B) tool[(long)(b0 + u) * CHUNK_TOOL_KEYS + tid] = at;
+                at += n[u];
+            }
         }
     }
 }
@@ -903,6 +1069,7 @@ hipError_t launch_edge_build(const EdgeArgs& h, hipStream_t st, void (*mark)(voi
     a.ell_stride = a.ell_full ? h.ell_stride : a.k;
     a.ell_bstride = a.ell_full ? h.ell_bstride : (long)h.N * a.k;
     a.ns_edge = h.ns_edge; a.n_ns = h.n_ns; a.n_oo = h.n_oo; a.n_cls = 1;
+    a.ck_bits = h.ck_bits; a.ck_off = h.ck_off; a.ck_list = h.ck_list; a.ck_shift = h.ck_shift;
     a.recv = h.recv; a.send = h.send; a.row_ptr = h.row_ptr; a.n_edges = h.n_edges; a.overflow = h.overflow;
     a.max_nR = h.max_nR; a.zero_on_overflow = h.zero_on_overflow; a.live = h.live;
     a.send_pk = a.ell_full ? h.send_pk : nullptr; a.base_send = h.base_send; a.base_deg = h.base_deg; a.base_stride = h.base_stride;
@@ -921,10 +1088,10 @@ hipError_t launch_edge_build(const EdgeArgs& h, hipStream_t st, void (*mark)(voi
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_edge_emit), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 160 * 1024 - 256);
         if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ell_index<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ell_index<0>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 160 * 1024 - 256);
         if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ell_index<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ell_index<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 160 * 1024 - 256);
         if (e != hipSuccess) return e;
         if (dev_id < 64) attr_devices |= 1ull << dev_id;
@@ -939,8 +1106,15 @@ hipError_t launch_edge_build(const EdgeArgs& h, hipStream_t st, void (*mark)(voi
         // class bitmaps inside the same 128 KB (or the debug budget): 25, else (object-object, tool), else the one list of slot order
         const long budget = h.lds_words > 0 && h.lds_words < ELL_BITMAP_MAX_WORDS64 ? h.lds_words : ELL_BITMAP_MAX_WORDS64;
         a.n_cls = !a.n_oo ? 1 : ELL_CLASSES * nw <= budget ? ELL_CLASSES : 2 * nw <= budget ? 2 : 1;
-        if (a.n_cls > 1) hipLaunchKernelGGL(k_ell_index<true>, dim3(h.B), dim3(EW), (size_t)a.n_cls * nw * 8, st, a);
-        else hipLaunchKernelGGL(k_ell_index<false>, dim3(h.B), dim3(EW), (size_t)nw * 8, st, a);
+        if (a.ck_list) {                                    // chunk list: bitmaps to global, count, scan, fill
+            const unsigned wgs = (unsigned)((nw + CKW / 64 - 1) / (CKW / 64));
+            hipLaunchKernelGGL(k_ell_index<2>, dim3(h.B), dim3(EW), 0, st, a);
+            hipLaunchKernelGGL(k_chunk_count, dim3(wgs), dim3(CKW), 0, st, a);
+            hipLaunchKernelGGL(k_chunk_scan, dim3(1), dim3(EW), 0, st, a);
+            hipLaunchKernelGGL(k_chunk_fill, dim3(wgs * ((unsigned)h.B + 1u)), dim3(CKW), 0, st, a);
+        }
+        else if (a.n_cls > 1) hipLaunchKernelGGL(k_ell_index<1>, dim3(h.B), dim3(EW), (size_t)a.n_cls * nw * 8, st, a);
+        else hipLaunchKernelGGL(k_ell_index<0>, dim3(h.B), dim3(EW), (size_t)nw * 8, st, a);
     }
     else hipLaunchKernelGGL(k_edge_emit, dim3(h.B * h.slices), dim3(EW), lds, st, a);
     if (mark) mark(mark_ctx, FAM_EDGE_EMIT, 1);

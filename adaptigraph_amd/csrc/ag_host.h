@@ -26,6 +26,7 @@ void* diag_create();
 void diag_destroy(void* diag);
 int diag_fail_at_chunk(void* diag);
 int diag_timing_skip(void* diag);
+void diag_chunk_dump(void* diag, const EdgeArgs& ea, int n_tools, hipStream_t st);
 #endif
 
 // A call's workspace: buffers are taken in order, each 256-byte aligned.  Without a base the slab only MEASURES: take() advances
@@ -188,6 +189,7 @@ struct Work {
     int* ell; int* deg; int* slice_tot; int* cta_flag;
     int* recv; int* send; int* row_ptr; int* n_edges;
     int* ns_edge; int* n_ns; int* n_oo;
+    unsigned long long* ck_bits; int* ck_off; unsigned* ck_list;   // chunk list (EdgeArgs::ck_list), slot-indexed rollout graphs only
     int* send_pk;                // first forward of a dynamics() call (GraphBufs::send_pk)
     int* rowlist; int* n_rows;   // ragged batches (GraphBufs::rowlist)
 };
@@ -218,6 +220,7 @@ int pick_slices(const ag_ctx* c, int B, int N);
 int clamp_chunk_for_offsets(int Bc, int N, int c_cap);
 int auto_chunk(const ag_ctx* c, int B, int N);
 bool lat_node_for(const ag_ctx* c, const GraphBufs& g);
+bool lat_edge_for(const ag_ctx* c, const GraphBufs& g);
 hipError_t node_enc_for(const ag_ctx* c, const GraphBufs& g, long row0, long nrows, hipStream_t st);
 int run_edge_chain(ag_ctx* c, const GraphBufs& g, hipStream_t st);
 int run_model(ag_ctx* c, const GraphBufs& g, float* pred_pos, float* pred_motion, hipStream_t st);

@@ -393,6 +393,7 @@ struct GDev {
     long row0, nrows;          // k_node_enc: slice of rows to encode
     const int* ns_edge; const int* n_ns;   // k_edge_enc: non-self-loop edge list (null = every edge)
     const int* n_oo;                       // k_edge_enc: class-major list, entries from n_oo[b] on are tool edges (null = slot order)
+    const unsigned* ck_list; const int* ck_n; int ck_shift;   // k_edge_enc: chunk list (GraphBufs::ck_list) or null
     const float* wb3;                      // bf16x3 weight image (null = exact fp32 mode)
     // message passing fused into the propagate chains (gather_agg): inputs of THIS round (Uin/Vin: the class table in the
     // first round of a rollout step, else what the previous round's chain wrote) - never the buffers this launch writes
@@ -688,16 +689,19 @@ __global__ __launch_bounds__(WG, 2) void k_edge_enc(GDev g) {
     int zi = 0;
     asm volatile("" : "+s"(zi));                           // per-tile opaque zero (see above)
     const float* const wts = g.w + zi;
-    const int b = (int)(blk % (unsigned)g.B);
-    const int e0 = (int)(blk / (unsigned)g.B) * WG_ROWS;
-    const int ne = g.n_ns ? g.n_ns[b] : g.n_edges[b];       // rows to encode: all edges, or the non-self-loop ones
+    // chunk list (GDev::ck_list): tile blk takes entries [128 blk, 128 blk + 128) of the launch's one list, a lane decodes its own
+    // (candidate, slot), and the tiles at or past the device-side count exit - the grid is the host's upper bound
+    const bool ck = g.ck_list != nullptr;
+    const int b = ck ? 0 : (int)(blk % (unsigned)g.B);
+    const int e0 = (int)(ck ? blk : blk / (unsigned)g.B) * WG_ROWS;
+    const int ne = ck ? g.ck_n[0] : g.n_ns ? g.n_ns[b] : g.n_edges[b];   // rows to encode: all edges, or the non-self-loop ones
     if (e0 >= ne) continue;                                  // whole workgroup past this candidate's edges
     // Zero skip per tile (AG_ZS_EDGE, top of the file).  Shipped (2): every tile builds its masks, whatever the order of the work
     // list.  The gated build (1) does so only for the tiles that start inside the object-object classes of a class-major list
     // (GDev::n_oo; null = slot order: never); a tile that starts at or past n_oo[b] holds tool edges only (7 % dead k-steps against
     // 20 %, but 28-48 % half-dead), and there its mask is not built and every k-step counts as live on both halves.
     int skip = 0;
-    if (ZS_EDGE) skip = g.zero_skip && (ZS_EDGE_ALL || (g.n_oo && e0 < g.n_oo[b])) ? 1 : 0;
+    if (ZS_EDGE) skip = g.zero_skip && (ZS_EDGE_ALL || (ck ? e0 < g.ck_n[1] : g.n_oo && e0 < g.n_oo[b])) ? 1 : 0;
 #ifdef AG_DIAG
     if (g.dbg && tid == 0) {
         g.dbg[blk * 4 + 0] = __builtin_amdgcn_s_memtime();
@@ -711,10 +715,13 @@ __global__ __launch_bounds__(WG, 2) void k_edge_enc(GDev g) {
 
     const int t = e0 + wave * 32 + (lane & 31);
     const bool valid = t < ne;
-    const int el = g.ns_edge ? g.ns_edge[(long)b * g.edge_cap + (valid ? t : 0)] : t;   // edge id (C row) of this lane
+    const unsigned ent = ck ? g.ck_list[valid ? t : e0] : 0u;   // (a lane past the end decodes the tile's first entry and stores nothing)
+    const int bl = ck ? (int)(ent >> g.ck_shift) : b;        // candidate of this lane
+    const int el = ck ? (int)(ent & ((1u << g.ck_shift) - 1u))
+                      : g.ns_edge ? g.ns_edge[(long)b * g.edge_cap + (valid ? t : 0)] : t;   // edge id (C row) of this lane
     const int elc = valid ? el : (g.ns_edge ? el : 0);
-    const int r = g.recv[(long)b * g.edge_cap + elc], s = g.send[(long)b * g.edge_cap + elc];
-    const long pr = (long)b * g.N + r, ps = (long)b * g.N + s;
+    const int r = g.recv[(long)bl * g.edge_cap + elc], s = g.send[(long)bl * g.edge_cap + elc];
+    const long pr = (long)bl * g.N + r, ps = (long)bl * g.N + s;
     float f[8 * EDGE_L1_CHUNKS];
     {
         const float* nr = g.node_in + pr * NODE_IN; const float* nsnd = g.node_in + ps * NODE_IN;
@@ -746,7 +753,7 @@ __global__ __launch_bounds__(WG, 2) void k_edge_enc(GDev g) {
     layer160<Q_FLOATS, true, false, ZS_EDGE, HS_EDGE>(lds, wts + WL::E_L3, wts + WL::E_W1, x, y, tid, lane, live_of<HS_EDGE>(x, skip, g.half_step));
     relu_one(y, lane);
     layer160<0, true, false, ZS_EDGE, HS_EDGE>(lds, wts + WL::E_W1, nullptr, y, x, tid, lane, live_of<HS_EDGE>(y, skip, g.half_step));
-    store_rows_t(x, g.C, (int)((long)b * g.c_cap + el), valid, stg, lane);
+    store_rows_t(x, g.C, (int)((long)bl * g.c_cap + el), valid, stg, lane);
 #ifdef AG_DIAG
     if (g.dbg && tid == 0) {
         g.dbg[blk * 4 + 2] = __builtin_amdgcn_s_memtime();
@@ -1232,6 +1239,7 @@ static GDev to_dev(const float* w, const GraphBufs& g) {
     d.cls_on = g.cls_on; d.N_o = g.N_o; d.M = g.M; d.first_round = 0; d.vmask = g.vmask; d.c_eff = g.c_eff; d.c_P = g.c_P;
     d.row0 = 0; d.nrows = (long)g.B * g.N;
     d.ns_edge = g.ns_edge; d.n_ns = g.n_ns; d.n_oo = g.n_oo;
+    d.ck_list = g.ck_list; d.ck_n = g.ck_n; d.ck_shift = g.ck_shift;
     d.wb3 = g.wb3;
     d.Uin = nullptr; d.Vin = nullptr; d.deg = g.deg; d.ell_stride = g.ell_stride; d.dedupe = g.c_self ? 1 : 0;
     d.self_row = (unsigned)g.self_row; d.n_guard = g.n_guard;

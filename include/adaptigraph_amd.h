@@ -182,16 +182,23 @@ int ag_ctx_set_chunk(ag_ctx* ctx, int32_t candidates_per_chunk);
  *                                         both features live stays two two-block MFMAs per tile pair (same bits); only a build
  *                                         with -DAG_HS_EDGE=0 -DAG_HS_NODE=0 has the former code
  *   "edge_order"     [AG_EDGE_ORDER]      order of the relation encoder's work list on the rollout's slot-indexed graphs: 0 = slot
- *                                         order (receiver-major); 1 (default) = class-major: the object-object slots by the sign bits
+ *                                         order (receiver-major); 1 = class-major: the object-object slots by the sign bits
  *                                         and the dominant axis of pos_r - pos_s at the current frame (24 classes), then every slot
  *                                         with a tool particle at either end, slot order inside a class.  Wavefronts of the relation
  *                                         encoder then hold like edges, more of their k-steps are all zero, and with "zero_skip" the
  *                                         fp32 relation-encoder chain branches over them (in every tile, also with order 0).
+ *                                         2 (default) = chunk list: one list per launch over all its live candidates - the
+ *                                         object-object slots by the transposed slot index (position in row, receiver), the same
+ *                                         slot of every candidate adjacent and in candidate order, then the tool slots by sector
+ *                                         (32, x-z plane) and ring (16, |pos_r - pos_s| in adjacency thresholds).  The candidates of
+ *                                         a chunk stay close to one start state, so a wavefront's 32 rows are alike.  It serves the
+ *                                         fp32 throughput chain on the slot-indexed graphs; bf16x3, the latency-mode chains, the
+ *                                         shared base graph and a chunk whose (candidate, slot) does not fit 32 bits take order 1.
  *                                         A C row is stored by slot and does not depend on the lane that computes it: same bits
  *   "ell_lds_words"  [AG_ELL_LDS_WORDS]   debug: LDS budget, in 64-bit words, of the class bitmaps of "edge_order" 1 (0 = the
  *                                         built-in 16384 = 128 KB).  A graph whose 25 bitmaps do not fit takes two classes
  *                                         (object-object, tool), then the one list of slot order; tests reach the fallbacks with it
- * Unknown names and values outside an option's range return AG_ERR_INVALID (ranges: edge_order 0..1, ell_lds_words 0..16384, stream_min_rows 0..INT32_MAX, pipeline_fork 0..1, streams 0..4, chunk 0..2^20, latency -1..1,
+ * Unknown names and values outside an option's range return AG_ERR_INVALID (ranges: edge_order 0..2, ell_lds_words 0..16384, stream_min_rows 0..INT32_MAX, pipeline_fork 0..1, streams 0..4, chunk 0..2^20, latency -1..1,
  * the 0/1 switches 0..1, edge_wgs 1..65536, edge_block_min -1..INT32_MAX, enc_persist 0..2^20, stagger_us 0..1000,
  * device_decode -1..1, share_first -1..1, share_prefix -1..1). */
 int ag_ctx_set_option(ag_ctx* ctx, const char* name, int32_t value);

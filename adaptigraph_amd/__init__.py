@@ -46,6 +46,7 @@ from .physics_param_optimizer import (dynamics_error, dynamics_error_sweep, dyna
                                       optimize_grad_device, dynamics_error_grad_device)
 from .mppi import angle_normalize, clip_actions, sample_action_seq, optimize_action_mppi, mpc_iteration
 from .planner import Planner
+from .cma import CmaSearch
 from .rollout import rollout_eval, rollout_eval_step, surface_bounds, rollout_eval_batch, eval_schedule, EvalResult
 from .train_step import TrainStep
 from .set_losses import ChamferLoss, HausdorffLoss, EarthMoverLoss, earth_mover_assignment, LossSpec, prefix_counts
@@ -60,4 +61,5 @@ __all__ = ["hw_queues", "Engine", "default_engine", "dynamics", "dynamics_masked
            "dynamics_masked_diff", "chamfer_diff", "dynamics_error_grad", "optimize_grad", "TrainStep", "PhysParamFit",
            "optimize_grad_device", "dynamics_error_grad_device", "DeviceDynDataset", "BatchDraws", "construct_edges_graphs",
            "nonfixed_rule_graphs", "surface_rule_graphs", "BackoffPlan", "RuleConfig", "rule_attempt", "backoff_rounds", "attempt_with_backoff",
-           "ChamferLoss", "HausdorffLoss", "EarthMoverLoss", "earth_mover_assignment", "LossSpec", "prefix_counts", "perception", "fps_cloud", "construct_graph", "state_cur_from_points"]
+           "ChamferLoss", "HausdorffLoss", "EarthMoverLoss", "earth_mover_assignment", "LossSpec", "prefix_counts", "perception", "fps_cloud", "construct_graph", "state_cur_from_points",
+           "CmaSearch"]

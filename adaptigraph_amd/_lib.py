@@ -35,10 +35,14 @@ EXPORTS = ["ag_abi_version", "ag_ctx_create", "ag_ctx_destroy", "ag_last_error",
            "ag_fps_batch", "ag_dataset_assemble", "ag_build_edges_graphs", "ag_eval_step",
            "ag_edges_nonfixed_rule_graphs", "ag_edges_surface_rule_graphs",
            "ag_set_loss", "ag_set_loss_backward", "ag_train_step_losses", "ag_fps_cloud"]
+# the CMA-ES search is a library of its own (include/adaptigraph_amd_cma.h; tests/test_cma_restate.py holds these to that header)
+CMA_LIB_PATH = os.path.join(_HERE, "csrc", "libadaptigraph_hip_cma.so")
+CMA_EXPORTS = ["ag_cma_state_doubles", "ag_cma_init", "ag_cma_ask", "ag_cma_tell", "ag_cma_last_error"]
 
 AG_LOSS_MSE, AG_LOSS_CHAMFER, AG_LOSS_HAUSDORFF, AG_LOSS_EMD = 0, 1, 2, 3
 AG_LOSS_ROWS = 16                       # flag on a set kind: each graph's real rows (adaptigraph_amd.h, ag_set_loss)
 EMD_MAX_MATCH = 512             # min(N, M) the Earth-mover loss serves (ag_common.h)
+CMA_MAX_N, CMA_MIN_POP, CMA_MAX_POP, CMA_HDR = 64, 4, 32768, 24      # limits and header words of a CMA-ES state (ag_common.h)
 
 OPTIONS = ["streams", "chunk", "latency", "ragged", "ell_graph", "self_dedupe", "repeat_sort", "edge_wgs", "edge_block_min",
            "enc_persist", "stagger_us", "device_decode", "zigzag", "share_first", "share_prefix", "stream_min_rows", "pipeline_fork", "zero_skip",
@@ -182,4 +186,31 @@ def load():
         if name not in ("ag_abi_version", "ag_last_error"):
             fn.restype = C.c_int
     _lib = lib
+    return lib
+
+
+_cma = None
+
+
+def load_cma():
+    """Load the CMA-ES library (once).  Raises RuntimeError with build instructions when it is absent."""
+    global _cma
+    if _cma is not None:
+        return _cma
+    if not os.path.exists(CMA_LIB_PATH):
+        raise RuntimeError(
+            f"adaptigraph_amd: CMA-ES library not built ({CMA_LIB_PATH}). Run `python -c 'import __graft_entry__ as g; "
+            f"g.build()'` or adaptigraph_amd/csrc/build.sh. There is no CPU fallback.")
+    lib = C.CDLL(CMA_LIB_PATH)
+    vp, i32, f64 = C.c_void_p, C.c_int32, C.c_double
+    lib.ag_cma_state_doubles.argtypes = [i32, i32]
+    lib.ag_cma_init.argtypes = [i32, vp, i32, i32, vp, f64, vp, vp, vp, vp, f64, i32, vp]
+    lib.ag_cma_ask.argtypes = [i32, vp, vp, vp, vp, vp]
+    lib.ag_cma_tell.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.ag_cma_last_error.argtypes = []
+    lib.ag_cma_last_error.restype = C.c_char_p
+    for name in CMA_EXPORTS:
+        if name != "ag_cma_last_error":
+            getattr(lib, name).restype = C.c_int
+    _cma = lib
     return lib

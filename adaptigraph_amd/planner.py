@@ -1,4 +1,4 @@
-"""`Planner` behind the reference's class interface (src/planning/real_world/planner.py:38-323), MPPI only.
+"""`Planner` behind the reference's class interface (src/planning/real_world/planner.py:38-323): MPPI, and a CMA-ES search.
 
 Same config dictionary, same methods, same result dictionaries: plan.py:177-247 and random_interact.py:168-214 can
 construct it and call `trajectory_optimization` / `merge_res` unchanged.  The class is host logic around the two
@@ -23,6 +23,9 @@ arithmetic of the hot path.  What is new:
   The two callables must be rank-local (no collective of their own: the ranks evaluate different calls); an error any rank meets
   ("Exceeds max dims", ...) is raised by `merge_res` on EVERY rank, after the exchange - never inside one rank's call, which would
   leave the others hanging in the collective.  `trajectory_optimization_chunked` deals contiguous chunk ranges the same way.
+* `planner_type` 'CMA' (not in the reference's list): `trajectory_optimization_cma` - the MPPI round loop with a covariance-adapting
+  search (cma.CmaSearch, csrc/ag_cma.hip) in place of the sampler and the softmax update; config keys `cma_sigma0` (0.25) and
+  `cma_periodic` ([2] for 4-component actions).  Its calls are never dealt to side streams or ranks; a lone call waits once.
 * `planner_type` 'GD' raises NotImplementedError: it differentiates through the rollout and the engine has no backward.
 * The reference's own loop - 40 x `trajectory_optimization`, then `merge_res` - is served as it stands (r05): when
   `model_rollout_fn` is the engine's `dynamics` behind a `functools.partial` (what plan.py:190 builds), consecutive calls on
@@ -178,7 +181,7 @@ class Planner(object):
         self.action_lower_lim = config["action_lower_lim"]
         self.action_upper_lim = config["action_upper_lim"]
         self.planner_type = config["planner_type"]
-        assert self.planner_type in ["GD", "MPPI", "MPPI_GD"]
+        assert self.planner_type in ["GD", "MPPI", "MPPI_GD", "CMA"]
         assert type(self.action_lower_lim) == torch.Tensor and type(self.action_upper_lim) == torch.Tensor
         assert self.action_lower_lim.shape == (self.action_dim,)
         assert self.action_upper_lim.shape == (self.action_dim,)
@@ -194,6 +197,12 @@ class Planner(object):
         self.rollout_best = config.get("rollout_best", True)
         self.lr = config.get("lr", 1e-3)
         self.group = config.get("group", None)
+        # planner_type 'CMA' (trajectory_optimization_cma): the start step as a fraction of each coordinate's range - a default
+        # argument, not a tuned value - and the action components that wrap (the push angle of an (x, z, theta, length) action)
+        self.cma_sigma0 = float(config.get("cma_sigma0", 0.25))
+        self.cma_periodic = [int(k) for k in config.get("cma_periodic", [2] if self.action_dim == 4 else [])]
+        self.last_cma = None         # the CmaSearch of the last 'CMA' call
+        self._cma_limits = None
         # Optional, off by default (the reference's call pattern): the rollout of the best sampled sequence is taken from the
         # batch it was sampled in instead of being computed again with a batch of one (planner.py:268-271).  Exact on this
         # engine - a candidate's rollout does not depend on its batch, bit for bit - and NOT in general (a BLAS-backed
@@ -315,6 +324,12 @@ class Planner(object):
             if self._can_wait_once(state_cur):
                 return self._one_wait_call(state_cur, act_seq)
             return self.trajectory_optimization_mppi(state_cur, act_seq)
+        if self.planner_type == "CMA":
+            # never dealt to side streams or ranks (_pipeline_off_static); a caller's chunk loop + merge_res = independent restarts
+            self.check_pending(block=True)
+            if self._can_wait_once(state_cur):
+                return self._one_wait_call(state_cur, act_seq, self.trajectory_optimization_cma)
+            return self.trajectory_optimization_cma(state_cur, act_seq)
         if self.planner_type == "GD":
             return self.trajectory_optimization_gd(state_cur, act_seq)
         if self.planner_type == "MPPI_GD":
@@ -438,8 +453,10 @@ class Planner(object):
         why = None
         bound = _repeat_bound(self._eng_rollout.keywords["ppm_optimizer"].task_config)
         uppers = []
-        for what, fn, mine, theirs in (("sampling_action_seq_fn", self.sample_action_sequences, self.sample_action_sequences_default, _mppi.sample_action_seq),
-                                       ("optimize_action_mppi_fn", self.optimize_action_mppi, self.optimize_action_mppi_default, _mppi.optimize_action_mppi)):
+        # 'CMA': every sample is folded into the planner's own limits (CmaSearch), whatever sampler and update are configured
+        for what, fn, mine, theirs in (() if self.planner_type == "CMA" else
+                                      (("sampling_action_seq_fn", self.sample_action_sequences, self.sample_action_sequences_default, _mppi.sample_action_seq),
+                                       ("optimize_action_mppi_fn", self.optimize_action_mppi, self.optimize_action_mppi_default, _mppi.optimize_action_mppi))):
             if getattr(fn, "__func__", None) is getattr(mine, "__func__", object()) and getattr(fn, "__self__", None) is self:
                 if what == "optimize_action_mppi_fn" and self.clip_action_sequences != self.clip_actions_default and not (
                         isinstance(self.clip_action_sequences, functools.partial) and self.clip_action_sequences.func is _mppi.clip_actions):
@@ -449,7 +466,9 @@ class Planner(object):
                 uppers.append(fn.keywords["action_upper_lim"])
             else:
                 why = f"{what} is neither the planner's default nor functools.partial(adaptigraph_amd.{theirs.__name__}, action_upper_lim=...)"
-        if isinstance(self.clip_action_sequences, functools.partial) and self.clip_action_sequences.func is _mppi.clip_actions \
+        if self.planner_type == "CMA":
+            uppers.append(self.action_upper_lim)
+        elif isinstance(self.clip_action_sequences, functools.partial) and self.clip_action_sequences.func is _mppi.clip_actions \
                 and self.clip_action_sequences.keywords.get("action_upper_lim") is not None:
             uppers.append(self.clip_action_sequences.keywords["action_upper_lim"])
         if bound is None:
@@ -501,10 +520,10 @@ class Planner(object):
         return (self._eng_rollout is not None and self.pipeline_chunks != 0 and not self.verbose and state_cur.is_cuda
                 and not torch.cuda.is_current_stream_capturing() and self._repeats_within_bound() is None)
 
-    def _one_wait_call(self, state_cur, act_seq):
+    def _one_wait_call(self, state_cur, act_seq, optimise=None):
         self._call_flags, self._call_one_stream = [], False
         try:
-            res = self.trajectory_optimization_mppi(state_cur, act_seq)
+            res = (optimise or self.trajectory_optimization_mppi)(state_cur, act_seq)
             flags = self._call_flags
         finally:
             self._call_flags, self._call_one_stream = None, True
@@ -591,6 +610,60 @@ class Planner(object):
                                        if isinstance(v, torch.Tensor) and isinstance(best_rows[key], torch.Tensor)
                                        and v.shape == best_rows[key].shape else v) for key, v in round_rows.items()}
                 best_reward = torch.where(better, round_reward, best_reward)
+            if self.verbose:
+                model_outputs.append(model_out)
+                eval_outputs.append(eval_out)
+        act_seq = best_act_seq
+        best_model_out = best_eval_out = None
+        if self.rollout_best:
+            best_model_out = best_rows if best_rows is not None else self._rollout(state_cur, act_seq.unsqueeze(0))
+            best_eval_out = self.evaluate_traj(best_model_out["state_seqs"], act_seq.unsqueeze(0), state_cur=state_cur)
+        return {"act_seq": act_seq,
+                "model_outputs": model_outputs if self.verbose else None,
+                "eval_outputs": eval_outputs if self.verbose else None,
+                "best_model_output": best_model_out,
+                "best_eval_output": best_eval_out}
+
+    @torch.no_grad()
+    def trajectory_optimization_cma(self, state_cur, act_seq):
+        """The round loop of trajectory_optimization_mppi with a CMA-ES search (cma.CmaSearch) in place of the sampler and the MPPI
+        update: the mean starts at `act_seq`, a generation is n_sample candidates, there are n_update_iter generations, rewards are
+        maximised.  The search runs over the flattened (n_look_ahead x action_dim) sequence inside the planner's limits (folded;
+        `cma_periodic` components wrap with period 2 pi), start step `cma_sigma0` of each coordinate's range.  Same result dictionary:
+        'act_seq' is the best SAMPLED sequence over all generations.  The winner's rows are picked with the tell's device-side
+        `order` / `improved` - no Python bool of a device value, no wait between generations."""
+        from .cma import CmaSearch
+        H, A = self.n_look_ahead, self.action_dim
+        if self._cma_limits is None:                         # host copies of the limits, read back once
+            self._cma_limits = (self.action_lower_lim.detach().to("cpu", torch.float64).repeat(H),
+                                self.action_upper_lim.detach().to("cpu", torch.float64).repeat(H))
+        lo, hi = self._cma_limits
+        search = CmaSearch(act_seq.detach().reshape(-1), self.cma_sigma0, lo, hi, popsize=self.n_sample, device=self.device,
+                           periodic=[h * A + k for h in range(H) for k in self.cma_periodic], maximize=True)
+        self.last_cma = search
+        model_outputs, eval_outputs = [], []
+        best_act_seq = best_rows = None
+        for i in range(self.n_update_iter):
+            if self.verbose:
+                print(f"chunk: {self.chunk_id}/{self.total_chunks}, iter: {i}/{self.n_update_iter}")
+            act_seqs = search.ask().reshape(self.n_sample, H, A)
+            model_out = self._rollout(state_cur, act_seqs, update_round=i)
+            assert type(model_out["state_seqs"]) == torch.Tensor
+            eval_out = self._evaluate(model_out, act_seqs, state_cur)
+            reward_seqs = eval_out["reward_seqs"]
+            assert reward_seqs.shape == (self.n_sample,)
+            search.tell(reward_seqs)
+            top, better = search.order[:1], search.improved
+            round_act = torch.index_select(act_seqs, 0, top)[0]
+            round_rows = self._pick(model_out, top, act_seqs.shape[0]) if self.reuse_best_rollout else None
+            if i == 0:
+                best_act_seq, best_rows = round_act, round_rows
+            else:
+                best_act_seq = torch.where(better, round_act, best_act_seq)
+                if round_rows is not None:
+                    best_rows = {key: (torch.where(better.to(v.device), v, best_rows[key])
+                                       if isinstance(v, torch.Tensor) and isinstance(best_rows[key], torch.Tensor)
+                                       and v.shape == best_rows[key].shape else v) for key, v in round_rows.items()}
             if self.verbose:
                 model_outputs.append(model_out)
                 eval_outputs.append(eval_out)

@@ -38,6 +38,10 @@ EXPORTS = ["ag_abi_version", "ag_ctx_create", "ag_ctx_destroy", "ag_last_error",
 # the CMA-ES search is a library of its own (include/adaptigraph_amd_cma.h; tests/test_cma_restate.py holds these to that header)
 CMA_LIB_PATH = os.path.join(_HERE, "csrc", "libadaptigraph_hip_cma.so")
 CMA_EXPORTS = ["ag_cma_state_doubles", "ag_cma_init", "ag_cma_ask", "ag_cma_tell", "ag_cma_last_error"]
+# so is the cell-list edge builder (include/adaptigraph_amd_cells.h; tests/test_cells_restate.py holds this to that header); it works
+# on the engine's contexts and links against the engine's library
+CELLS_LIB_PATH = os.path.join(_HERE, "csrc", "libadaptigraph_hip_cells.so")
+CELLS_EXPORTS = ["ag_build_edges_cells"]
 
 AG_LOSS_MSE, AG_LOSS_CHAMFER, AG_LOSS_HAUSDORFF, AG_LOSS_EMD = 0, 1, 2, 3
 AG_LOSS_ROWS = 16                       # flag on a set kind: each graph's real rows (adaptigraph_amd.h, ag_set_loss)
@@ -213,4 +217,26 @@ def load_cma():
         if name != "ag_cma_last_error":
             getattr(lib, name).restype = C.c_int
     _cma = lib
+    return lib
+
+
+_cells = None
+
+
+def load_cells():
+    """Load the cell-list edge builder's library (once), behind the engine's, which it links against.  Raises RuntimeError with
+    build instructions when it is absent."""
+    global _cells
+    if _cells is not None:
+        return _cells
+    load()
+    if not os.path.exists(CELLS_LIB_PATH):
+        raise RuntimeError(
+            f"adaptigraph_amd: cell-list edge builder not built ({CELLS_LIB_PATH}). Run `python -c 'import __graft_entry__ as g; "
+            f"g.build()'` or adaptigraph_amd/csrc/build.sh. There is no CPU fallback.")
+    lib = C.CDLL(CELLS_LIB_PATH)
+    vp, i32, f32 = C.c_void_p, C.c_int32, C.c_float
+    lib.ag_build_edges_cells.argtypes = [vp, vp, vp, C.c_int64, vp, vp, i32, i32, f32, vp, vp, i32, i32, C.c_int64, vp, vp, vp, vp]
+    lib.ag_build_edges_cells.restype = C.c_int
+    _cells = lib
     return lib

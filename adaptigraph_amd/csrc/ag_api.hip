@@ -211,8 +211,18 @@ int pick_slices(const ag_ctx* c, int B, int N) {
 }
 
 // the gather (ag_mlp.hip: gather_agg) addresses C, U and V with 32-bit element offsets: a launch chunk must keep every buffer below 2^32 floats
+constexpr long kMaxOffsetRows = ((1L << 32) / NFP) - 512;    // rows of NFP floats addressable with a 32-bit element offset
+// A launch chunk is at least one graph, so the clamp below cannot help a single graph whose node rows or edge slots exceed the
+// bound (reachable since the cell-list builder serves graphs beyond the LDS builder's 4096 particles): refused here.
+int check_graph_rows(ag_ctx* c, const char* me, int N, int edge_cap) {
+    const long c_cap = (long)round_up((size_t)edge_cap, 256);
+    if (N > kMaxOffsetRows || c_cap > kMaxOffsetRows)
+        return fail(c, AG_ERR_UNSUPPORTED, "%s: N=%d / edge_cap=%d exceed the %ld rows per graph that 32-bit activation offsets address", me, N,
+                    edge_cap, kMaxOffsetRows);
+    return AG_OK;
+}
 int clamp_chunk_for_offsets(int Bc, int N, int c_cap) {
-    const long max_rows = ((1L << 32) / NFP) - 512;          // rows of NFP floats addressable with a 32-bit element offset
+    const long max_rows = kMaxOffsetRows;
     const long by_c = max_rows / std::max(1, c_cap);
     const long by_n = max_rows / std::max(1, N);
     return (int)std::max(1L, std::min<long>(Bc, std::min(by_c, by_n)));
@@ -514,6 +524,7 @@ int ag_forward(ag_ctx* c, void* stream, const float* d_state, const float* d_att
         return fail(c, AG_ERR_INVALID, "ag_forward: null pointer");
     if (B < 1 || N < 1 || n_p < 1 || n_p > N || n_inst < 1 || edge_cap < 1)
         return fail(c, AG_ERR_INVALID, "ag_forward: bad sizes B=%d N=%d n_p=%d n_inst=%d edge_cap=%d", B, N, n_p, n_inst, edge_cap);
+    if (int rc0 = check_graph_rows(c, "ag_forward", N, edge_cap)) return rc0;
     SlotGuard call;
     int rc = begin_call(c, stream, call);
     if (rc) return rc;

@@ -78,6 +78,7 @@ int ag_backward_inputs(ag_ctx* c, void* stream, const float* d_state, const floa
         if (!d_w[k]) return fail(c, AG_ERR_INVALID, "ag_backward: null parameter %d", k);
     if (B < 1 || N < 1 || n_p < 1 || n_p > N || n_inst < 1 || edge_cap < 1)
         return fail(c, AG_ERR_INVALID, "ag_backward: bad sizes B=%d N=%d n_p=%d n_inst=%d edge_cap=%d", B, N, n_p, n_inst, edge_cap);
+    if (int rc0 = check_graph_rows(c, "ag_backward", N, edge_cap)) return rc0;
     if (c->dims.nf != NF || c->dims.in_dim != IN_DIM || c->dims.rel_dim != 5 + 3 * c->dims.n_his || c->dims.pstep < 1 || c->dims.pstep > 7)
         return fail(c, AG_ERR_UNSUPPORTED, "ag_backward: nf %d, in_dim %d, rel_dim %d, pstep %d not served", c->dims.nf, c->dims.in_dim,
                     c->dims.rel_dim, c->dims.pstep);

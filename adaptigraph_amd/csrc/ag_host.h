@@ -218,6 +218,7 @@ void carve_work(const ag_ctx* c, Slab& s, Work& w, int Bc, int N, int n_inst, in
 
 int pick_slices(const ag_ctx* c, int B, int N);
 int clamp_chunk_for_offsets(int Bc, int N, int c_cap);
+int check_graph_rows(ag_ctx* c, const char* me, int N, int edge_cap);   // one graph within the 32-bit activation offsets, or AG_ERR_UNSUPPORTED
 int auto_chunk(const ag_ctx* c, int B, int N);
 bool lat_node_for(const ag_ctx* c, const GraphBufs& g);
 bool lat_edge_for(const ag_ctx* c, const GraphBufs& g);

@@ -11,6 +11,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
+from . import _lib
 from .context import default_engine, ptr, current_stream, _require_gpu
 
 
@@ -100,6 +101,54 @@ def construct_edges_index(states, adj_thresh, mask, tool_mask, topk=10, connect_
     eng.check(eng.lib.ag_build_edges(eng.ctx, current_stream(dev), ptr(states), ptr(mask_u8), ptr(tool_u8), B, N, thr,
                                      ptr(thr_vec), int(topk), int(bool(connect_tools_all)), edge_cap, ptr(recv),
                                      ptr(send), ptr(row_ptr), ptr(n_edges)))
+    return EdgeList(recv, send, row_ptr, n_edges, N)
+
+
+CELLS_MAX_PARTICLES = 1 << 20   # ag_build_edges_cells (csrc/ag_cells.h)
+CELLS_MAX_TOPK = 128
+
+
+def construct_edges_cells(states, adj_thresh, mask, tool_mask, topk=10, connect_tools_all=False, edge_cap=None, single=False,
+                          engine=None):
+    """construct_edges_index from the cell-list builder (ag_build_edges_cells): the same EdgeList bit for bit, for graphs of up
+    to CELLS_MAX_PARTICLES particles and 1 <= topk <= CELLS_MAX_TOPK (NotImplementedError beyond, and for an edge_cap that does
+    not fit int32).  single: the single-graph builder's rule for every graph of the batch - the threshold squared in double and
+    then rounded, as construct_edges_from_states squares it, connect_tools_all unconditional and without tool<->tool edges.
+    Enqueue only; n_edges[b] is the TRUE count even above edge_cap, and then nothing else is written for graph b."""
+    dev = _require_gpu(states.device)
+    eng = engine or default_engine(dev)
+    states = states.to(torch.float32).contiguous()
+    B, N, sd = states.shape
+    assert sd == 3, "state_dim must be 3"
+    mask_u8 = mask.to(torch.bool).contiguous().view(torch.uint8)
+    tool_u8 = tool_mask.to(torch.bool).contiguous().view(torch.uint8)
+    thr, thr_vec, thr2_vec = 0.0, None, None
+    if isinstance(adj_thresh, torch.Tensor):
+        assert adj_thresh.numel() == B
+        if single:
+            thr2_vec = (adj_thresh.to(device=dev, dtype=torch.float64) ** 2).to(torch.float32).contiguous()
+        else:
+            thr_vec = adj_thresh.to(device=dev, dtype=torch.float32).contiguous()
+    elif single:
+        t = float(adj_thresh)
+        thr2_vec = torch.full((B,), float(np.float32(t * t)), device=dev, dtype=torch.float32)   # double product, one fp32 rounding
+    else:
+        thr = float(adj_thresh)
+    if edge_cap is None:
+        k = min(N, int(topk))
+        m = int(tool_mask.to(torch.bool).sum(1).max().item())
+        edge_cap = N * (k + m) if k < N else N * N
+    edge_cap = max(1, int(edge_cap))
+    if edge_cap > 2 ** 31 - 1:
+        raise NotImplementedError(f"construct_edges_cells: edge_cap={edge_cap} does not fit the int32 edge offsets (at most {2 ** 31 - 1})")
+    recv = torch.empty((B, edge_cap), device=dev, dtype=torch.int32)
+    send = torch.empty((B, edge_cap), device=dev, dtype=torch.int32)
+    row_ptr = torch.empty((B, N + 1), device=dev, dtype=torch.int32)
+    n_edges = torch.empty((B,), device=dev, dtype=torch.int32)
+    rule = (2 if single else 1) if connect_tools_all else 0
+    eng.check(_lib.load_cells().ag_build_edges_cells(eng.ctx, current_stream(dev), ptr(states), 0, ptr(mask_u8), ptr(tool_u8), B, N, thr,
+                                                     ptr(thr_vec), ptr(thr2_vec), int(topk), rule, edge_cap, ptr(recv), ptr(send),
+                                                     ptr(row_ptr), ptr(n_edges)))
     return EdgeList(recv, send, row_ptr, n_edges, N)
 
 

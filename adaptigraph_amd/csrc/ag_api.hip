@@ -1,6 +1,7 @@
 // C-ABI of the MI355X-native GNN-dynamics rollout engine (see include/adaptigraph_amd.h).
 // Host orchestration only: context, workspace, weight repacking, launch sequences.  No CPU compute fallback.
 #include "ag_host.h"
+#include "ag_cost.h"
 
 #include <cstdarg>
 

@@ -2,7 +2,7 @@
 // libadaptigraph_hip_cma.so, a library of its own beside the engine's: it needs no engine context.  The state is the caller's
 // buffer; the library keeps nothing between calls but the calling thread's last error message.
 #include "../../include/adaptigraph_amd_cma.h"
-#include "ag_common.h"
+#include "ag_cma.h"
 
 #include <algorithm>
 #include <cmath>

@@ -1,6 +1,7 @@
 // C-ABI, training-batch entry points: ag_fps_batch, ag_dataset_assemble (kernels in ag_dataset.hip).  The third call of the
 // batch build, ag_build_edges_graphs, sits with the other graph builders in ag_api.hip.
 #include "ag_host.h"
+#include "ag_dataset.h"
 
 using namespace ag;
 

@@ -1,5 +1,6 @@
 // C-ABI, graph construction: the edge builder entry points and the tool-attachment rules (see include/adaptigraph_amd.h).
 #include "ag_host.h"
+#include "ag_rules.h"
 
 using namespace ag;
 

@@ -1,6 +1,10 @@
 // C-ABI, training side (see include/adaptigraph_amd.h): the backward pass, device-side weight loading and Adam, the chained
 // training step and the physics-parameter fit.  Host orchestration only; context and shared helpers: ag_host.h.
 #include "ag_host.h"
+#include "ag_cost.h"      // chamfer_max_points
+#include "ag_ppm.h"
+#include "ag_setloss.h"
+#include "ag_train.h"
 
 using namespace ag;
 

@@ -1,6 +1,6 @@
 // (mu/mu_w, lambda)-CMA-ES on the device, gfx950 only: the optimiser behind CmaSearch and Planner(planner_type='CMA').  Standard
 // algorithm (Hansen, "The CMA Evolution Strategy: A Tutorial", 2016): positive weights only, no active update, no restarts, fp64
-// throughout.  The state is one caller-owned buffer of doubles (CmaLayout, ag_common.h); a generation is
+// throughout.  The state is one caller-owned buffer of doubles (CmaLayout, ag_cma.h); a generation is
 //   k_cma_ask   y_k = A z_k, genotype g_k = m + (sigma scale) o y_k, phenotype x_k = bound(g_k) rounded once to fp32.  One thread per
 //               (candidate, coordinate), grid-stride; A = C^(1/2) is staged in LDS (it is symmetric, so row j serves as column j and
 //               consecutive lanes read consecutive words).
@@ -21,7 +21,8 @@
 // every sweep the off-diagonal norm is summed from the off-diagonal entries themselves; the sweeps end at off <= 1e-15 |diag|, or
 // after CMA_SWEEPS.
 // No float atomics, no inter-workgroup traffic, every loop bounded before it is entered, every index read from a table clamped.
-#include "ag_common.h"
+#include "ag_cma.h"
+#include "ag_lds_optin.h"
 
 namespace ag {
 
@@ -370,16 +371,8 @@ __global__ __launch_bounds__(CT) void k_cma_tell(double* __restrict__ st, const 
 }
 
 hipError_t cma_tell_attr() {
-    static unsigned long long attr_devices = 0;                 // per-device function attribute (see launch_emd_assign)
-    int dev_id = 0;
-    if (hipGetDevice(&dev_id) != hipSuccess) dev_id = 0;
-    if (dev_id >= 64 || !(attr_devices >> dev_id & 1ull)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_cma_tell), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)CMA_TELL_LDS);
-        if (e != hipSuccess) return e;
-        if (dev_id < 64) attr_devices |= 1ull << dev_id;
-    }
-    return hipSuccess;
+    static std::atomic<unsigned long long> done{0};             // the dynamic-LDS opt-in, per device (ag_lds_optin.h)
+    return lds_opt_in(done, (int)CMA_TELL_LDS, k_cma_tell);
 }
 }  // namespace
 

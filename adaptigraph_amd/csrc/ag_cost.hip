@@ -5,7 +5,8 @@
 // pairwise or pointwise passes.  chamfer is the heavy one (N*M distance evaluations per row in both directions): both
 // clouds sit in LDS as SoA, every lane owns one point and scans the other cloud through LDS broadcasts - the same
 // tiling idea as the edge builder.  No atomics: fixed reduction trees, bit-reproducible.
-#include "ag_common.h"
+#include "ag_cost.h"
+#include "ag_lds_optin.h"
 
 namespace ag {
 
@@ -380,15 +381,8 @@ hipError_t launch_chamfer(const float* x, const float* y, const uint8_t* xm, con
                           int By, float* out, hipStream_t st) {
     ChamferDev a{x, y, xm, ym, out, R, N, M, By};
     const size_t lds = (size_t)(3 * ((N + 1) & ~1) + 3 * ((M + 1) & ~1)) * 4;
-    static unsigned long long attr_devices = 0;              // per-device function attribute (see ag_edges.hip)
-    int dev_id = 0;
-    if (hipGetDevice(&dev_id) != hipSuccess) dev_id = 0;
-    if (dev_id >= 64 || !(attr_devices >> dev_id & 1ull)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_chamfer),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048);
-        if (e != hipSuccess) return e;
-        if (dev_id < 64) attr_devices |= 1ull << dev_id;
-    }
+    static std::atomic<unsigned long long> done{0};          // the dynamic-LDS opt-in, per device (ag_lds_optin.h)
+    if (hipError_t e = lds_opt_in(done, 160 * 1024 - 2048, k_chamfer); e != hipSuccess) return e;
     hipLaunchKernelGGL(k_chamfer, dim3(R), dim3(CT), lds, st, a);
     return hipGetLastError();
 }
@@ -396,17 +390,11 @@ hipError_t launch_chamfer_backward(const float* x, const float* y, const uint8_t
                                    int By, const float* gout, int* nn, float* cnt, float* gx, hipStream_t st) {
     ChamferDev a{x, y, xm, ym, nullptr, R, N, M, By};
     const size_t lds = (size_t)(3 * ((N + 1) & ~1) + 3 * ((M + 1) & ~1)) * 4;
-    static unsigned long long attr_devices = 0;              // per-device function attribute (see launch_chamfer)
-    int dev_id = 0;
-    if (hipGetDevice(&dev_id) != hipSuccess) dev_id = 0;
-    if (dev_id >= 64 || !(attr_devices >> dev_id & 1ull)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_chamfer_nn),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048);
-        if (e != hipSuccess) return e;
-        if (dev_id < 64) attr_devices |= 1ull << dev_id;
-    }
+    static std::atomic<unsigned long long> done{0};          // the dynamic-LDS opt-in, per device (ag_lds_optin.h)
+    hipError_t e = lds_opt_in(done, 160 * 1024 - 2048, k_chamfer_nn);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_chamfer_nn, dim3(R), dim3(CT), lds, st, a, nn, cnt);
-    hipError_t e = hipGetLastError();
+    e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_chamfer_grad, dim3((unsigned)(((long)R * N + CT - 1) / CT)), dim3(CT), 0, st, a, (const int*)nn,
                        (const float*)cnt, gout, gx);

@@ -16,7 +16,9 @@
 // live in registers (PPT points per thread), the cloud in LDS as SoA; one barrier per selected point.
 // No atomics: every output has one writer.
 #include "../../include/adaptigraph_amd.h"
-#include "ag_common.h"
+#include "ag_dataset.h"
+#include "ag_dist.h"
+#include "ag_lds_optin.h"
 
 namespace ag {
 
@@ -30,10 +32,6 @@ constexpr int FPS_MAX_NOBJ = FW * FPS_PPT2;        // 1024 stage-1 points (16 KB
 size_t fps_max_points() { return FPS_MAX_POINTS; }
 int fps_max_nobj() { return FPS_MAX_NOBJ; }
 
-__device__ __forceinline__ float fps_d2(float xi, float yi, float zi, float xj, float yj, float zj) {
-    const float dx = __fsub_rn(xi, xj), dy = __fsub_rn(yi, yj), dz = __fsub_rn(zi, zj);
-    return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-}
 __device__ __forceinline__ unsigned long long fps_key(float d, int i) {
     return ((unsigned long long)__float_as_uint(d) << 32) | (0xffffffffu - (unsigned)i);
 }
@@ -84,7 +82,7 @@ __device__ __forceinline__ int fps_stage2(const float* sx, const float* sy, cons
         for (int u = 0; u < PPT2; ++u) {
             const int i = u * W + tid;
             if (i < n1) {
-                const float d = __fsqrt_rn(fps_d2(sx[i], sy[i], sz[i], cx, cy, cz));
+                const float d = __fsqrt_rn(dist_exact(sx[i], sy[i], sz[i], cx, cy, cz));
                 m2[u] = m2[u] > d ? d : m2[u];
                 const unsigned long long key = fps_key(m2[u], i);
                 best = key > best ? key : best;
@@ -144,7 +142,7 @@ __global__ __launch_bounds__(FW) void k_fps_batch(FpsDev a) {
         for (int u = 0; u < PPT; ++u) {
             const int i = u * FW + tid;
             if (i < n) {
-                const float d = fps_d2(x[i], y[i], z[i], cx, cy, cz);
+                const float d = dist_exact(x[i], y[i], z[i], cx, cy, cz);
                 md[u] = md[u] > d ? d : md[u];
                 const unsigned long long key = fps_key(md[u], i);
                 best = key > best ? key : best;
@@ -166,16 +164,8 @@ __global__ __launch_bounds__(FW) void k_fps_batch(FpsDev a) {
 template <int PPT>
 static hipError_t launch_fps(const FpsDev& a, int B, size_t lds, hipStream_t st) {
     if (lds > 64 * 1024) {               // above 64 KB of dynamic LDS: a per-device opt-in of the function
-        // (host threads may race on this mask: harmless, the attribute call is idempotent - at worst it is repeated)
-        static unsigned long long attr_devices = 0;
-        int dev_id = 0;
-        if (hipGetDevice(&dev_id) != hipSuccess) dev_id = 0;
-        if (dev_id >= 64 || !(attr_devices >> dev_id & 1ull)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_fps_batch<PPT>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
-            if (e != hipSuccess) return e;
-            if (dev_id < 64) attr_devices |= 1ull << dev_id;
-        }
+        static std::atomic<unsigned long long> done{0};
+        if (hipError_t e = lds_opt_in(done, 160 * 1024 - 256, k_fps_batch<PPT>); e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(k_fps_batch<PPT>, dim3(B), dim3(FW), lds, st, a);
     return hipGetLastError();
@@ -229,7 +219,7 @@ struct __attribute__((packed, aligned(4))) P3 { float x, y, z; };
 // one point of a sweep: its minimum against the centre, and the thread's running (bits, index) argmax
 __device__ __forceinline__ float cloud_visit(const P3* p, int i, int n, float md, float cx, float cy, float cz, int& bestb, int& besti) {
     const P3 q = p[i < n ? i : n - 1];                 // branch-free: a point past the end reads the last one and is not counted
-    const float d = fps_d2(q.x, q.y, q.z, cx, cy, cz);
+    const float d = dist_exact(q.x, q.y, q.z, cx, cy, cz);
     md = md > d ? d : md;
     const int mb = i < n ? (int)__float_as_uint(md) : -1;
     if (mb > bestb) { bestb = mb; besti = i; }

@@ -15,7 +15,7 @@
 //                             edge_cap, shift, entries, object-object entries, tools; the list; deg (B, N); send (B, edge_cap);
 //                             positions (B, N, 3) as floats; the adjacency threshold (tests/test_gpu_chunk_order.py)
 #ifdef AG_DIAG
-#include "ag_common.h"
+#include "ag_edges.h"
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>

@@ -2,17 +2,13 @@
 // both spell the reference's arithmetic and the top-k choice once: the exact pair distance, the wavefront helpers and the
 // rank-counting selection of the k-th smallest (distance, sender) key.  Device code only.
 #pragma once
-#include "ag_common.h"
+#include "ag_dist.h"   // dist_exact
 
 namespace ag {
 
 constexpr int CAP = 256;          // candidate-buffer entries per wavefront
 constexpr unsigned long long KEY_INF = ~0ull;
 
-__device__ __forceinline__ float dist_exact(float xi, float yi, float zi, float xj, float yj, float zj) {
-    const float dx = __fsub_rn(xi, xj), dy = __fsub_rn(yi, yj), dz = __fsub_rn(zi, zj);
-    return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-}
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");

@@ -30,8 +30,10 @@
 // Two kernels, no inter-workgroup communication inside a launch:
 //   k_edge_count : per-row kept list (ELL) + degree, slice totals, connect_tools_all flag
 //   k_edge_emit  : scan of degrees -> row_ptr, then writes (recv, send) in order
-#include "ag_common.h"
+#include "ag_edges.h"
+#include "ag_options.h"
 #include "ag_edge_select.h"
+#include "ag_lds_optin.h"
 #include <cstdlib>
 
 namespace ag {
@@ -673,14 +675,14 @@ __device__ __forceinline__ int edge_class(const float* __restrict__ p, int i, in
 }
 // key of a tool slot in the chunk list (Options::edge_order 2, see k_chunk_count below): sector * 16 + ring of d = pos_i - pos_j
 __device__ __forceinline__ int chunk_tool_key(const float* __restrict__ p, int i, int j, float thr2) {
-    const float dx = __fsub_rn(p[3 * i + 0], p[3 * j + 0]), dy = __fsub_rn(p[3 * i + 1], p[3 * j + 1]), dz = __fsub_rn(p[3 * i + 2], p[3 * j + 2]);
+    const float d2 = dist_exact(p[3 * i + 0], p[3 * i + 1], p[3 * i + 2], p[3 * j + 0], p[3 * j + 1], p[3 * j + 2]);
+    const float dx = __fsub_rn(p[3 * i + 0], p[3 * j + 0]), dz = __fsub_rn(p[3 * i + 2], p[3 * j + 2]);
     const float ax = fabsf(dx), az = fabsf(dz);
     const bool swap = az > ax;
     const float mn = swap ? ax : az, mx = swap ? az : ax;
     const int fine = (mn >= __fmul_rn(0.19891237f, mx) ? 1 : 0) + (mn >= __fmul_rn(0.41421357f, mx) ? 1 : 0) +
                      (mn >= __fmul_rn(0.66817864f, mx) ? 1 : 0);   // tan of 11.25, 22.5, 33.75 degrees
     const int sector = ((dx < 0.0f ? 1 : 0) | (dz < 0.0f ? 2 : 0) | (swap ? 4 : 0)) * 4 + fine;
-    const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
     int ring = 0;
 #pragma unroll
     for (int k = 1; k < 16; ++k) ring += d2 >= __fmul_rn((float)(k * k), thr2) ? 1 : 0;
@@ -1006,25 +1008,9 @@ hipError_t launch_edge_build(const EdgeArgs& h, hipStream_t st, void (*mark)(voi
     a.share_start = h.share_start; a.share_cand = h.share_cand; a.share_b0 = h.share_b0;
     a.block_min_rows = h.block_min_rows >= 0 ? h.block_min_rows : BLOCK_MIN_ROWS;   // A/B switch (Options::edge_block_min); results identical
     const size_t lds = edge_lds_bytes(h.N);
-    // the > 64 KB dynamic-LDS opt-in is a per-DEVICE function attribute: track it per device ordinal
-    static unsigned long long attr_devices = 0;
-    int dev_id = 0;
-    if (hipGetDevice(&dev_id) != hipSuccess) dev_id = 0;
-    if (dev_id >= 64 || !(attr_devices >> dev_id & 1ull)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_edge_count),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_edge_emit), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024 - 256);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ell_index<0>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024 - 256);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ell_index<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024 - 256);
-        if (e != hipSuccess) return e;
-        if (dev_id < 64) attr_devices |= 1ull << dev_id;
-    }
+    static std::atomic<unsigned long long> done{0};   // the > 64 KB dynamic-LDS opt-in, per device (ag_lds_optin.h)
+    if (hipError_t e = lds_opt_in(done, 160 * 1024 - 256, k_edge_count, k_edge_emit, k_ell_index<0>, k_ell_index<1>); e != hipSuccess)
+        return e;
     if (mark) mark(mark_ctx, FAM_EDGE_COUNT, 0);
     hipLaunchKernelGGL(k_edge_count, dim3(h.B * h.slices), dim3(EW), lds, st, a);
     if (mark) mark(mark_ctx, FAM_EDGE_COUNT, 1);

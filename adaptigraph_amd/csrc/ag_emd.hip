@@ -25,7 +25,8 @@
 //                x_i (N > M only).  One writer per element: overwrites, or adds to the chain's dLoss/dpred.
 // REAL ROWS (AG_LOSS_ROWS, template <bool ROWS>): the matching runs over the prefixes x[b, :nx_b], y[b, :ny_b] with K_b = min(nx_b,
 // ny_b) pairs, the loss is the mean over graphs of sum_b matched / K_b, the gradient scale g_out w / (B_total K_b); see k_emd_assign.
-#include "ag_common.h"
+#include "ag_setloss.h"
+#include "ag_lds_optin.h"
 
 namespace ag {
 
@@ -230,18 +231,8 @@ size_t emd_max_points() { return EMD_LDS_BUDGET / 40 - 2; }     // 40 bytes a po
 
 hipError_t launch_emd_assign(const EmdDev& a, const SetRows& rows, hipStream_t st) {
     const int K = a.N < a.M ? a.N : a.M, L = a.N < a.M ? a.M : a.N;
-    static unsigned long long attr_devices = 0;                 // per-device function attribute (see launch_chamfer)
-    int dev_id = 0;
-    if (hipGetDevice(&dev_id) != hipSuccess) dev_id = 0;
-    if (dev_id >= 64 || !(attr_devices >> dev_id & 1ull)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_emd_assign<EA, false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, EMD_LDS_BUDGET);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_emd_assign<EA, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                EMD_LDS_BUDGET);
-        if (e != hipSuccess) return e;
-        if (dev_id < 64) attr_devices |= 1ull << dev_id;
-    }
+    static std::atomic<unsigned long long> done{0};             // the dynamic-LDS opt-in, per device (ag_lds_optin.h)
+    if (hipError_t e = lds_opt_in(done, EMD_LDS_BUDGET, k_emd_assign<EA, false>, k_emd_assign<EA, true>); e != hipSuccess) return e;
     if (rows.nx) hipLaunchKernelGGL((k_emd_assign<EA, true>), dim3(a.B), dim3(EA), emd_lds_bytes(K, L), st, a, rows);
     else hipLaunchKernelGGL((k_emd_assign<EA, false>), dim3(a.B), dim3(EA), emd_lds_bytes(K, L), st, a, rows);
     return hipGetLastError();

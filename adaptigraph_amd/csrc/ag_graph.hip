@@ -1,7 +1,8 @@
 // Small HBM-bound kernels of the rollout step: model-input preparation, the guard for caller-built graphs and the per-step
 // rollout bookkeeping (tool keypoints, history shift, capture).  gfx950 only.  (The edge->node message passing lives in
 // ag_mlp.hip, fused into the propagate chains: gather_agg.)
-#include "ag_common.h"
+#include "ag_rollout.h"
+#include "ag_dist.h"
 #include <algorithm>
 
 namespace ag {
@@ -361,7 +362,7 @@ hipError_t launch_build_rowlist(const uint8_t* obj_mask, const int* cand, int b0
 }
 
 // ------------------------------------------------------------------------------------------------ device-side launch plan
-// See RollPlan (ag_common.h).  fp32 operations spelled in the reference's order (plan_utils.py:13-16: end = start -
+// See RollPlan (ag_rollout.h).  fp32 operations spelled in the reference's order (plan_utils.py:13-16: end = start -
 // push_length * (cos, sin); forward_dynamics.py:48-75: delta = end - start, side keypoints start +- c_k * (sin, cos)); the
 // transcendental functions are the device's (a GPU-resident reference would use the device's too), so decoded values agree
 // with a CPU decode to an ulp or two, not bit for bit.
@@ -454,12 +455,9 @@ hipError_t launch_roll_plan(const RollPlan& p, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------------------------ contact-free prefix
-// See ContactPlan (ag_common.h).  One workgroup per candidate.  The pair test is the edge builder's (ag_edges.hip: dist_exact,
-// pair_within): dis = ((dx*dx + dy*dy) + dz*dz) with separate roundings, adjacent <=> (dis - thr*thr) < 0 (graph.py:248-267).
-__device__ __forceinline__ float contact_dis(float xi, float yi, float zi, float xj, float yj, float zj) {
-    const float dx = __fsub_rn(xi, xj), dy = __fsub_rn(yi, yj), dz = __fsub_rn(zi, zj);
-    return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-}
+// See ContactPlan (ag_rollout.h).  One workgroup per candidate.  The pair test is the edge builder's (ag_dist.h: dist_exact;
+// ag_edges.hip: pair_within): dis = ((dx*dx + dy*dy) + dz*dz) with separate roundings, adjacent <=> (dis - thr*thr) < 0
+// (graph.py:248-267).
 constexpr int CT = 256;
 __global__ __launch_bounds__(CT) void k_contact_plan(ContactPlan p) {
     __shared__ float red[CT];
@@ -480,7 +478,7 @@ __global__ __launch_bounds__(CT) void k_contact_plan(ContactPlan p) {
             const float x = p.base_states[3 * i], y = p.base_states[3 * i + 1], z = p.base_states[3 * i + 2];
             for (int m2 = 0; m2 < p.M; ++m2) {
                 const float* xz = p.eef_xz + ((long)b * p.H * p.M + m2) * 2;
-                hit |= __fsub_rn(contact_dis(x, y, z, xz[0], ty, xz[1]), thr2) < 0.0f ? 1 : 0;
+                hit |= __fsub_rn(dist_exact(x, y, z, xz[0], ty, xz[1]), thr2) < 0.0f ? 1 : 0;
             }
         }
         hit = __syncthreads_or(hit);
@@ -508,7 +506,7 @@ __global__ __launch_bounds__(CT) void k_contact_plan(ContactPlan p) {
         for (int i = tid; i < p.N_o; i += CT) {
             const float x = S[3 * i], y = S[3 * i + 1], z = S[3 * i + 2];
             for (int m = 0; m < p.M; ++m)
-                hit |= __fsub_rn(contact_dis(x, y, z, tx[m], ty, tz[m]), thr2) < 0.0f ? 1 : 0;
+                hit |= __fsub_rn(dist_exact(x, y, z, tx[m], ty, tz[m]), thr2) < 0.0f ? 1 : 0;
         }
         if (__syncthreads_or(hit)) { d = ai; break; }
         for (int m = 0; m < p.M; ++m) { tx[m] = tx[m] + dx[m]; tz[m] = tz[m] + dz[m]; }   // forward_dynamics.py:164

@@ -2,7 +2,10 @@
 // call slots, the workspace slab and the helpers they share.  Everything declared here is defined once, in ag_api.hip.
 #pragma once
 #include "../../include/adaptigraph_amd.h"
-#include "ag_common.h"
+#include "ag_edges.h"
+#include "ag_model.h"
+#include "ag_options.h"
+#include "ag_rollout.h"
 
 #include <algorithm>
 #include <cmath>
@@ -14,13 +17,6 @@
 #include <vector>
 
 namespace ag {
-size_t edge_build_max_particles();
-int edge_ell_stride(int N, int topk);
-size_t lat_weights_floats();
-hipError_t launch_edge_enc_lat(const float* wl, const GraphBufs& g, hipStream_t st);
-hipError_t launch_node_enc_lat(const float* wl, const GraphBufs& g, long row0, long nrows, hipStream_t st);
-hipError_t launch_node_prop_lat(const float* wl, const GraphBufs& g, int round, bool last, float clamp, float* pred_pos,
-                                float* pred_motion, hipStream_t st);
 #ifdef AG_DIAG   // diagnostic build only (ag_diag.hip)
 void* diag_create();
 void diag_destroy(void* diag);

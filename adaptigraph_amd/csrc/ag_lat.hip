@@ -21,7 +21,7 @@
 // the weight image on both its output-row and its k side (ag_api.hip: pack_layer16).  So a batch gives the same bits
 // whichever kernel family its size selects, the self-loop constant rows are shared, and sharded == unsharded holds
 // across the switch (tests: test_latency_kernels_equal_throughput_kernels_bitwise).
-#include "ag_common.h"
+#include "ag_model.h"
 #include <cstdint>
 #include <cstdlib>
 

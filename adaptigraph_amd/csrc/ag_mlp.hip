@@ -21,7 +21,7 @@
 //   * Roofline: fp32 MFMA (157.3 TFLOP/s).  Per 32 rows a 160-wide layer is 380 MFMAs = 2*32*160*152 FLOP.
 //   * Rows are independent columns of the MFMA, so results do not depend on which lane / workgroup / chunk / GPU a
 //     row lands in: sharded == unsharded bit-for-bit.
-#include "ag_common.h"
+#include "ag_model.h"
 #include <cstdint>
 
 namespace ag {
@@ -67,10 +67,10 @@ struct Act { f32x16 t[5]; };
 // plain skip, 1.1 % faster per launch with half-steps (the tool tiles are 28-48 % half-dead, docs/EXPERIMENTS.md).  k_node_enc is built like the relation-encoder chain and is not on the flagship path (the class table goes
 // through the latency-mode chain); unmeasured, so it stays as it was.
 // docs/EXPERIMENTS.md, "Zero skip in the fp32 chains" and "Class-major work list".  -DAG_ZS_EDGE=0|2 / -DAG_ZS_ENC=1 / -DAG_ZS_NODE=0:
-// experiment builds.  The switches themselves (ZS_EDGE, ZS_EDGE_ALL, ZS_ENC, ZS_NODE) are defined in ag_common.h.
+// experiment builds.  The switches themselves (ZS_EDGE, ZS_EDGE_ALL, ZS_ENC, ZS_NODE) are defined in ag_model.h.
 // Half-steps (mma_act) per chain, fixed at build time like the skip they extend; 0 = the chain's code is the one without them,
 // instruction for instruction, and its layers are packed unpaired.  docs/EXPERIMENTS.md, "Half-dead k-steps at K = 1" and "Paired
-// weight image".  -DAG_HS_EDGE=0 / -DAG_HS_NODE=0: experiment builds (HS_EDGE, HS_NODE: ag_common.h, shared with the weight packer).
+// weight image".  -DAG_HS_EDGE=0 / -DAG_HS_NODE=0: experiment builds (HS_EDGE, HS_NODE: ag_model.h, shared with the weight packer).
 
 // ------------------------------------------------------------------------------------------------ staging
 // global -> LDS DMA (global_load_lds, 16 B per lane): NFLOATS (a multiple of 256) in 1-KB pieces, each wave-instruction

@@ -11,7 +11,7 @@
 // Both are tiny and latency-bound (B <= tens of thousands, 16 B per action); no roofline applies.
 // The sampler is fp32 throughout, each product/sum spelled in the reference's order (-ffp-contract=off: no FMA contraction); the
 // update keeps the reference's fp32 terms per candidate and reduces them in double (see k_mppi_update).
-#include "ag_common.h"
+#include "ag_cost.h"
 
 namespace ag {
 

@@ -7,7 +7,8 @@
 //   * the glue of the reference's loop body (src/dynamics/train/train.py:86-124): MSE in fp64 in a fixed order, the next state
 //     and action, the MSE gradient plus what the later steps say about a prediction, the shift of dLoss/dstate through the history
 // No float atomics: two calls on the same inputs give the same bits.
-#include "ag_common.h"
+#include "ag_model.h"
+#include "ag_train.h"
 #include <cstdint>
 #include <cstring>
 

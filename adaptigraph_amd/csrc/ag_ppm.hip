@@ -7,7 +7,7 @@
 //     rows of its last frame, and the mean-y path from its tool rows
 //   * the per-start reduction of error and gradient, history, best-so-far and Adam in double, in one small launch
 // No float atomics; every sum has a fixed order that does not depend on which other rows share the call.
-#include "ag_common.h"
+#include "ag_ppm.h"
 
 namespace ag {
 namespace {

@@ -18,7 +18,8 @@
 //                         everything of a graph in LDS; a graph reads nothing of its neighbours (k_rule_graphs)
 //   launch_surface_graphs the two-closest-planes rule for B graphs in the same pattern (k_surface_graphs)
 #include <math.h>
-#include "ag_common.h"
+#include "ag_rules.h"
+#include "ag_dist.h"
 
 namespace ag {
 
@@ -67,9 +68,7 @@ __device__ __forceinline__ int rule_tool_list(const RuleGraph& g, int M, int* s_
 // fp32 distance of the pair (receiver i, tool sender j), spelled like the edge builder's; both_tool: i is a tool too
 __device__ __forceinline__ float rule_pair_dis(const float* pos, const uint8_t* mask, int i, int j, bool both_tool) {
     if (!mask[j] || both_tool) return RULE_BIG;                         // graph.py:89-96
-    const float dx = __fsub_rn(pos[3 * i], pos[3 * j]), dy = __fsub_rn(pos[3 * i + 1], pos[3 * j + 1]),
-                dz = __fsub_rn(pos[3 * i + 2], pos[3 * j + 2]);
-    return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));   // graph.py:87-88
+    return dist_exact(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], pos[3 * j], pos[3 * j + 1], pos[3 * j + 2]);   // graph.py:87-88
 }
 
 // One receiver row: walks the base senders [e, e1) (ascending) and the tool list (ascending) as one merged sequence.  flag: bit 0

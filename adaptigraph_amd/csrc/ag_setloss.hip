@@ -15,17 +15,18 @@
 //                table for the j whose arg-min is i, in ascending j.  Hausdorff: only the two winning pairs.  The norm's gradient
 //                at zero distance is zero (torch).  Every x_i has one writer: no atomics, repeated runs give the same bits.
 // A NaN distance wins a min and a max, as in torch.min / torch.max, so a diverged prediction gives a NaN loss; its pull is NaN too
-// (set_pull, ag_common.h), so the gradient row of a NaN point is NaN and the rows of graphs without one keep their bits.
+// (set_pull, ag_setloss.h), so the gradient row of a NaN point is NaN and the rows of graphs without one keep their bits.
 // Equal maxima: the Hausdorff winner is the lowest (b, index), and k_set_grad gives that one pair the whole weight.  torch.max()
 // over the batch splits its gradient evenly among equal maxima instead (each of k tied rows gets 1/k).  Values and arg-min tables
 // are torch's either way; the gradients differ only at exact ties, which need duplicated points.  Kept: one winner per side is
 // what lets the backward read four ints instead of searching for ties (tests/test_set_loss_edges.py has the difference on record).
 // REAL ROWS (AG_LOSS_ROWS, template <bool ROWS>): on a padded batch graph b's clouds are the prefixes x[b, :nx_b], y[b, :ny_b], the
-// counts clamped into range where they are read (set_rows_of, ag_common.h) and a graph with an empty side wholly empty.  Only real
+// counts clamped into range where they are read (set_rows_of, ag_setloss.h) and a graph with an empty side wholly empty.  Only real
 // rows are loaded, strided over and searched; chamfer = (1 / B_total) sum_b [sx_b / nx_b + sy_b / ny_b] - the mean over graphs of
 // each graph's own Chamfer distance -, hausdorff = the max over the real rows of every graph (an empty graph has no candidate; none
 // at all: 0, winners -1); gradient rows behind nx_b are exact zeros.  ROWS = false is the code the plain kinds always had.
-#include "ag_common.h"
+#include "ag_setloss.h"
+#include "ag_lds_optin.h"
 
 namespace ag {
 
@@ -280,18 +281,8 @@ size_t set_loss_part_ints(int B) { return (size_t)B * 2; }
 
 hipError_t launch_set_nn(const SetLossDev& a, const SetRows& rows, hipStream_t st) {
     const size_t lds = (size_t)3 * ((size_t)a.N + a.M) * 4;
-    static unsigned long long attr_devices = 0;              // per-device function attribute (see launch_chamfer)
-    int dev_id = 0;
-    if (hipGetDevice(&dev_id) != hipSuccess) dev_id = 0;
-    if (dev_id >= 64 || !(attr_devices >> dev_id & 1ull)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_set_nn<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           160 * 1024 - 2048);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_set_nn<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024 - 2048);
-        if (e != hipSuccess) return e;
-        if (dev_id < 64) attr_devices |= 1ull << dev_id;
-    }
+    static std::atomic<unsigned long long> done{0};          // the dynamic-LDS opt-in, per device (ag_lds_optin.h)
+    if (hipError_t e = lds_opt_in(done, 160 * 1024 - 2048, k_set_nn<false>, k_set_nn<true>); e != hipSuccess) return e;
     if (rows.nx) hipLaunchKernelGGL(k_set_nn<true>, dim3(a.B), dim3(ST), lds, st, a, rows);
     else hipLaunchKernelGGL(k_set_nn<false>, dim3(a.B), dim3(ST), lds, st, a, rows);
     return hipGetLastError();

@@ -10,7 +10,8 @@
 // counting sort (k_send_csr), in ascending edge order.  Two calls on the same inputs are bit-identical, and a row's input
 // gradient does not depend on which other rows share its launch.  ag_backward_inputs adds one more dX GEMM: the particle
 // encoder's input gradient dH1 * W0, whose columns are dLoss/dphys and dLoss/daction.
-#include "ag_common.h"
+#include "ag_model.h"
+#include "ag_train.h"
 #include <algorithm>
 #include <cstdint>
 

@@ -180,5 +180,5 @@ def test_header_declares_the_kind_and_documents_the_work_layout():
     assert "d_work for AG_LOSS_EMD" in doc and "match table" in doc and "status words" in doc
     from adaptigraph_amd import _lib
     assert len(_lib.EXPORTS) == 51                                          # no new export (tests/test_abi.py holds them to the header)
-    common = open(os.path.join(ROOT, "adaptigraph_amd", "csrc", "ag_common.h")).read()
+    common = open(os.path.join(ROOT, "adaptigraph_amd", "csrc", "ag_setloss.h")).read()
     assert re.search(r"SET_LOSS_EMD = 3\b", common) and re.search(r"EMD_MAX_MATCH = (\d+)", common).group(1) == str(_lib.EMD_MAX_MATCH)

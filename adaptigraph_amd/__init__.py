@@ -34,7 +34,7 @@ def _hw_queues_default():
 hw_queues = _hw_queues_default()
 
 from .context import Engine, default_engine
-from .forward_dynamics import dynamics, dynamics_masked, dynamics_masked_diff, dynamics_mixed, rollout_work
+from .forward_dynamics import dynamics, dynamics_masked, dynamics_masked_diff, dynamics_mixed, rollout_work, dynamics_cells, dynamics_masked_cells
 from .graph import (EdgeList, construct_edges_from_states_batch, construct_edges_from_states, construct_edges_index,
                     construct_edges_cells,
                     construct_edges_with_backoff, pad_torch, truncate_graph, construct_edges_graphs, nonfixed_rule_graphs, surface_rule_graphs,
@@ -59,7 +59,7 @@ __all__ = ["hw_queues", "Engine", "default_engine", "dynamics", "dynamics_masked
            "construct_edges_index", "construct_edges_cells", "construct_edges_with_backoff", "pad_torch", "truncate_graph", "DynamicsPredictor", "decode_action", "chamfer",
            "mean_chamfer", "box_loss", "rope_penalty", "cloth_penalty", "granular_penalty", "running_cost", "dynamics_error", "dynamics_error_sweep", "angle_normalize",
            "clip_actions", "sample_action_seq", "optimize_action_mppi", "mpc_iteration", "Planner", "rollout_eval", "rollout_eval_step", "surface_bounds", "rollout_eval_batch", "eval_schedule", "EvalResult",
-           "dynamics_masked_diff", "chamfer_diff", "dynamics_error_grad", "optimize_grad", "TrainStep", "PhysParamFit",
+           "dynamics_masked_diff", "dynamics_cells", "dynamics_masked_cells", "chamfer_diff", "dynamics_error_grad", "optimize_grad", "TrainStep", "PhysParamFit",
            "optimize_grad_device", "dynamics_error_grad_device", "DeviceDynDataset", "BatchDraws", "construct_edges_graphs",
            "nonfixed_rule_graphs", "surface_rule_graphs", "BackoffPlan", "RuleConfig", "rule_attempt", "backoff_rounds", "attempt_with_backoff",
            "ChamferLoss", "HausdorffLoss", "EarthMoverLoss", "earth_mover_assignment", "LossSpec", "prefix_counts", "perception", "fps_cloud", "construct_graph", "state_cur_from_points",

@@ -1,4 +1,4 @@
-// C-ABI of the cell-list edge builder (include/adaptigraph_amd_cells.h): libadaptigraph_hip_cells.so, a library of its own
+// C-ABI of the cell-list edge builder and of the rollout over its graphs (include/adaptigraph_amd_cells.h): libadaptigraph_hip_cells.so, a library of its own
 // beside the engine's - the engine's export list is closed at ABI version 7 - that works on the engine's contexts: it links
 // against libadaptigraph_hip.so and takes its stream slot and its scratch from the context like every engine entry point.
 #include "../../include/adaptigraph_amd_cells.h"
@@ -8,6 +8,21 @@
 #include <climits>
 
 using namespace ag;
+
+namespace {
+// ints of the builder's zeroed region for B graphs [cell counts (B, cells_cap) | degrees (B, N) | batch flags (B)]: what a launch over
+// B graphs clears, and - ag_cells.hip lays the three parts out by the launch's own B - what it may touch of the region
+size_t cells_zeroed_ints(int B, int N, int cells_cap) { return (size_t)B * cells_cap + (size_t)B * N + (size_t)B; }
+// the cell builder's scratch for up to B graphs of N particles (CellArgs says what each part holds); sets cells_cap and zeroed_ints for B
+void carve_cells(Slab& s, CellArgs& a, int B, int N, int topk) {
+    const size_t nB = (size_t)B, rows = nB * (size_t)N, cells = cells_cap_for(N);
+    a.cells_cap = (int)cells; a.zeroed_ints = cells_zeroed_ints(B, N, a.cells_cap);
+    a.zeroed = s.take<int>(a.zeroed_ints); a.grid = s.take<char>(nB * cells_grid_bytes());
+    a.cell_start = s.take<int>(nB * (cells + 1)); a.cid = s.take<int>(rows); a.slot = s.take<int>(rows);
+    a.sorted = s.take<float>(rows * 4); a.ell = s.take<int>(rows * (size_t)std::min(N, topk));
+    a.tlist = s.take<int>(rows); a.ntool = s.take<int>(nB);
+}
+}  // namespace
 
 extern "C" int ag_build_edges_cells(ag_ctx* c, void* stream, const float* d_pos, int64_t pos_bstride, const uint8_t* d_mask,
                                     const uint8_t* d_tool, int32_t B, int32_t N, float thr, const float* d_thr_vec,
@@ -35,15 +50,150 @@ extern "C" int ag_build_edges_cells(ag_ctx* c, void* stream, const float* d_pos,
     a.thr = thr; a.thr_vec = d_thr_vec; a.thr2_vec = d_thr2_vec;
     a.B = B; a.N = N; a.topk = topk; a.rule = rule; a.edge_cap = (long)edge_cap;
     a.recv = d_recv; a.send = d_send; a.row_ptr = d_row_ptr; a.n_edges = d_n_edges;
-    const size_t nB = (size_t)B, rows = nB * (size_t)N, cells = cells_cap_for(N);
-    a.cells_cap = (int)cells; a.zeroed_ints = nB * cells + rows + nB;
-    rc = carve_slab(c, *call.sl, [&](Slab& s) {
-        a.zeroed = s.take<int>(a.zeroed_ints); a.grid = s.take<char>(nB * cells_grid_bytes());
-        a.cell_start = s.take<int>(nB * (cells + 1)); a.cid = s.take<int>(rows); a.slot = s.take<int>(rows);
-        a.sorted = s.take<float>(rows * 4); a.ell = s.take<int>(rows * (size_t)std::min(N, topk));
-        a.tlist = s.take<int>(rows); a.ntool = s.take<int>(nB);
-    });
+    rc = carve_slab(c, *call.sl, [&](Slab& s) { carve_cells(s, a, B, N, topk); });
     if (rc) return rc;
     HIPCHK(c, launch_cells_build(a, call.st));
+    return AG_OK;
+}
+
+// ================================================================================================ ag_rollout_cells
+// The rollout of ag_rollout_async over graphs of any size the cell-list builder serves.  A plain driver: one workspace, the caller's
+// stream, per step cell-list build -> overflow guard -> self-loop pass -> model forward -> tool height -> row update.  None of
+// rollout_impl's machinery (device plan, contact-free prefix, shared first forward, slot-indexed graphs, chunk lists, forked
+// streams) applies to a handful of candidates of tens of thousands of rows each.
+namespace {
+constexpr int kMaxTools = 8;       // tool keypoints per candidate the rollout's tool layout serves (ag_rollout_actions: M <= 8)
+
+}  // namespace
+
+extern "C" int ag_rollout_cells(ag_ctx* c, void* stream, const ag_rollout_params* p, const float* d_state0, const uint8_t* d_obj_mask,
+                                const float* d_eef_xz, const float* d_eef_delta, const int32_t* h_repeat, const float* d_phys_vec,
+                                float* d_state_seqs, int32_t* d_overflow_flag) {
+    if (!c) return AG_ERR_INVALID;
+    const char* me = "ag_rollout_cells";
+    if (!c->have_w) return fail(c, AG_ERR_NO_WEIGHTS, "%s before ag_ctx_load_weights", me);
+    if (!p || !d_state0 || !d_eef_xz || !d_eef_delta || !h_repeat || !d_state_seqs || !d_overflow_flag)
+        return fail(c, AG_ERR_INVALID, "%s: null pointer", me);
+    if (p->B < 1 || p->H < 1 || p->N_o < 1 || p->M < 1 || p->max_nR < 1 || p->topk < 1)
+        return fail(c, AG_ERR_INVALID, "%s: bad sizes B=%d H=%d N_o=%d M=%d topk=%d max_nR=%d", me, p->B, p->H, p->N_o, p->M, p->topk, p->max_nR);
+    if (p->y_mode != 0 && p->y_mode != 1) return fail(c, AG_ERR_INVALID, "y_mode must be 0 or 1");
+    if (p->y_mode == 1 && p->H != 1) return fail(c, AG_ERR_INVALID, "masked rollout has a single look-ahead step");
+    // ---- refusals, before anything is enqueued or counted
+    const long N_l = (long)p->N_o + p->M;
+    if (N_l > CELLS_MAX_PARTICLES) return fail(c, AG_ERR_UNSUPPORTED, "%s: N=%ld exceeds the cell-list builder's limit %d", me, N_l, CELLS_MAX_PARTICLES);
+    if (p->topk > CELLS_MAX_TOPK) return fail(c, AG_ERR_UNSUPPORTED, "%s: topk=%d exceeds %d", me, p->topk, CELLS_MAX_TOPK);
+    if (p->M > kMaxTools) return fail(c, AG_ERR_UNSUPPORTED, "%s: M=%d tool particles, the tool layout serves at most %d", me, p->M, kMaxTools);
+    const int n_his = c->dims.n_his;
+    if (c->precision == 1 && n_his != 4) return fail(c, AG_ERR_UNSUPPORTED, "the bf16x3 chains are built for n_his=4");
+    const int N = (int)N_l, k = std::min(N, p->topk);
+    const long bound = (long)N * (k + p->M);                 // in-degree <= topk + M (radius-AND-top-k, then tool rule)
+    const int edge_cap = (int)round_up((size_t)std::min<long>(bound, p->max_nR), 256);
+    int rc = check_graph_rows(c, me, N, edge_cap);
+    if (rc) return rc;
+
+    SlotGuard call;
+    rc = begin_call(c, stream, call);
+    if (rc) return rc;
+    hipStream_t st = call.st; CallSlot& sl = *call.sl;
+    const int Bc = std::min(clamp_chunk_for_offsets(auto_chunk(c, p->B, N), N, edge_cap), CELLS_MAX_GRAPHS);
+    const bool dedupe = c->opt.self_dedupe != 0;
+    const size_t nrep = (size_t)p->B * p->H;
+
+    // ---- host plan: per chunk and look-ahead step the slots in descending order of their repeat (stable), so that the candidates
+    // with a forward left at step ai are a prefix of the slots and every launch of that step covers that prefix only
+    rc = grow(c, false, sl.d_repeat, sl.repeat_cap, 2 * nrep, 2 * nrep + (nrep >> 2));
+    if (rc) return rc;
+    sl.h_repeat.resize(2 * nrep);
+    std::copy(h_repeat, h_repeat + nrep, sl.h_repeat.begin());
+    const int32_t* rep = sl.h_repeat.data();
+    int* h_cand = sl.h_repeat.data() + nrep;                 // [li][slot] -> candidate
+    for (int li = 0; li < p->H; ++li)
+        for (int b0 = 0; b0 < p->B; b0 += Bc) {
+            const int nb = std::min(Bc, p->B - b0);
+            int* seg = h_cand + (size_t)li * p->B + b0;
+            for (int b = 0; b < nb; ++b) seg[b] = b0 + b;
+            std::stable_sort(seg, seg + nb, [&](int x, int y) { return rep[(size_t)x * p->H + li] > rep[(size_t)y * p->H + li]; });
+        }
+
+    // ---- one slab: the workspace, the builder's scratch, the guarded counts, tool heights and valid-row counts
+    Work w{}; CellArgs ca{}; int* n_eff = nullptr; float* height = nullptr; int* count = nullptr;
+    rc = carve_slab(c, sl, [&](Slab& s) {
+        carve_work(c, s, w, Bc, N, 1, edge_cap, edge_cap, 1, true, true, true, p->N_o, 0);
+        carve_cells(s, ca, Bc, N, p->topk);
+        n_eff = s.take<int>(Bc); height = s.take<float>(Bc); count = s.take<int>(Bc);
+    });
+    if (rc) return rc;
+    // nothing below fails without having enqueued: from here on the call counts (a refusal or a failed allocation above leaves the
+    // counters of the context's last rollout as they were)
+    c->last_slot = (int)(call.sl - c->slots);
+    c->d_share_nns = nullptr; c->d_plan_sums = nullptr;
+    c->fwd_executed = 0; c->fwd_needed = 0;
+    for (size_t i = 0; i < nrep; ++i) c->fwd_needed += std::max(0, rep[i]);
+    c->steps_enqueued = 0; c->steps_bound = 0;
+
+    HIPCHK(c, hipMemsetAsync(d_state_seqs, 0, (size_t)p->B * p->H * p->N_o * 3 * 4, st));   // forward_dynamics.py:32
+    HIPCHK(c, hipMemcpyAsync(sl.d_repeat, rep, 2 * nrep * 4, hipMemcpyHostToDevice, st));
+
+    ca.pos = w.r.hist + (size_t)(n_his - 1) * N * 3; ca.pos_bstride = (long)n_his * N * 3;   // the newest frame, in place
+    ca.mask = w.r.mask; ca.tool = w.r.tool; ca.thr = p->adj_thresh;
+    ca.N = N; ca.topk = p->topk; ca.rule = p->connect_tools_all ? 1 : 0; ca.edge_cap = edge_cap;
+    ca.recv = w.recv; ca.send = w.send; ca.row_ptr = w.row_ptr; ca.n_edges = w.n_edges;
+
+    bool obj_cls_ready = false;
+    for (int b0 = 0; b0 < p->B; b0 += Bc) {
+        const int nb = std::min(Bc, p->B - b0);
+        GraphBufs g = w.g;
+        g.B = nb; g.n_p = p->N_o; g.n_his = n_his; g.n_edges = n_eff;
+        g.wb3 = c->precision == 1 ? c->d_wb3 : nullptr;
+        if (dedupe) {
+            g.c_self = c->d_cself; g.ns_edge = w.ns_edge; g.n_ns = w.n_ns;
+            g.self_row = (long)Bc * edge_cap;                // behind the last candidate's C rows of the workspace
+            HIPCHK(c, hipMemcpyAsync(w.g.C + (size_t)g.self_row * NFP, c->d_cself, 2 * NFP * 4, hipMemcpyDeviceToDevice, st));
+        }
+        RollRows ra{};
+        ra.b0 = b0; ra.N_o = p->N_o; ra.M = p->M; ra.H = p->H; ra.y_mode = p->y_mode; ra.n_his = n_his; ra.n_inst = 1;
+        ra.grip = p->gripper_offset; ra.grip_on = p->gripper_enable; ra.phys = p->physics_param; ra.phys_vec = d_phys_vec;
+        ra.state0 = d_state0; ra.state0_batched = p->y_mode == 1; ra.obj_mask = d_obj_mask;
+        ra.eef_xz = d_eef_xz; ra.eef_delta = d_eef_delta; ra.repeat = sl.d_repeat; ra.state_seqs = d_state_seqs;
+        ra.hist = w.r.hist; ra.pred = w.r.pred; ra.mask = w.r.mask; ra.tool = w.r.tool;
+        ra.node_in = w.g.node_in; ra.feat12 = w.g.feat12; ra.group = w.g.group; ra.c_node_in = w.g.c_node_in;
+        ra.height = height; ra.count = count;
+        for (int li = 0; li < p->H; ++li) {
+            const int* seg = h_cand + (size_t)li * p->B + b0;
+            const int max_rep = std::max(0, rep[(size_t)seg[0] * p->H + li]);   // descending order
+            if (max_rep == 0) continue;                      // nothing of this chunk is stepped in this look-ahead step
+            ra.li = li; ra.ai = 0; ra.B = nb; ra.cand = sl.d_repeat + nrep + (size_t)li * p->B + b0;
+            ra.write_obj_cls = obj_cls_ready ? 0 : 1;
+            { Scoped s(c, FAM_ROLL_INIT);
+              HIPCHK(c, launch_tool_height(ra, false, st));
+              HIPCHK(c, launch_roll_init_rows(ra, st)); }
+            { Scoped s(c, FAM_NODE_ENC);                     // object rows once per call, tool rows per look-ahead step
+              const long tool0 = 2L * p->N_o;
+              g.B = nb;
+              if (!obj_cls_ready) HIPCHK(c, node_enc_for(c, g, 0, tool0 + (long)nb * p->M, st));
+              else HIPCHK(c, node_enc_for(c, g, tool0, (long)nb * p->M, st)); }
+            obj_cls_ready = true;
+            int n_live = nb;
+            c->steps_bound += max_rep;
+            for (int ai = 1; ai <= max_rep; ++ai) {          // forward_dynamics.py:156
+                while (n_live > 0 && rep[(size_t)seg[n_live - 1] * p->H + li] < ai) --n_live;
+                ++c->steps_enqueued;
+                c->fwd_executed += n_live;
+                ca.B = n_live;
+                ca.zeroed_ints = cells_zeroed_ints(n_live, N, ca.cells_cap);
+                { Scoped s(c, FAM_EDGE_COUNT); HIPCHK(c, launch_cells_build(ca, st)); }
+                { Scoped s(c, FAM_EDGE_EMIT);
+                  HIPCHK(c, launch_cells_guard(w.n_edges, n_live, N, p->max_nR, n_eff, w.row_ptr, d_overflow_flag, st));
+                  if (dedupe) HIPCHK(c, launch_edge_nonself(w.recv, w.send, w.row_ptr, n_live, N, edge_cap, w.ns_edge, w.n_ns, nullptr, st)); }
+                g.B = n_live;
+                rc = run_model(c, g, w.r.pred, w.r.motion, st);
+                if (rc) return rc;
+                ra.B = n_live; ra.ai = ai;
+                { Scoped s(c, FAM_ROLL_UPDATE);
+                  HIPCHK(c, launch_tool_height(ra, true, st));
+                  HIPCHK(c, launch_roll_update_rows(ra, st)); }
+            }
+        }
+    }
     return AG_OK;
 }

@@ -303,6 +303,211 @@ __global__ __launch_bounds__(RT) void k_roll_update(RollDev d) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------ row-parallel bookkeeping
+// k_roll_init / k_roll_update walk a candidate's rows with ONE workgroup.  The rollout over cell-list graphs (ag_rollout_cells) steps
+// a handful of candidates of up to 2^20 rows: there the row loops run over a grid (row blocks, slots), one row per thread, and the
+// one value that needs the whole cloud - the tool height - comes from a kernel of its own.  Per-row arithmetic as in the two
+// kernels above, operation for operation.
+constexpr int RR = 256;                                      // rows per workgroup of the row kernels
+
+// Tool height of every slot (+ gripper offset) and, for the masked rollout, its count of valid rows.  One workgroup per slot:
+// tool_y itself, so the minimum and the masked mean have the bits k_roll_init / k_roll_update produce.
+__global__ __launch_bounds__(RT) void k_tool_height(RollRows a, int from_pred) {
+    __shared__ float red[RT];
+    __shared__ int redi[RT];
+    const int b = blockIdx.x, bg = a.cand ? a.cand[b] : a.b0 + b, tid = threadIdx.x;
+    const float* src = from_pred ? a.pred + (long)b * a.N_o * 3
+                     : a.li == 0 ? (a.state0_batched ? a.state0 + (long)bg * a.N_o * 3 : a.state0)
+                                 : a.state_seqs + ((long)bg * a.H + (a.li - 1)) * a.N_o * 3;
+    const uint8_t* om = a.obj_mask ? a.obj_mask + (long)bg * a.N_o : nullptr;
+    float y = tool_y(src, om, a.N_o, a.y_mode, red, redi);
+    if (a.grip_on) y = y + a.grip;                           // :80-81 / :167-168
+    int count = a.N_o;
+    if (om && !from_pred) {                                  // first-`count` rows carry p_instance (:294-300)
+        int c = 0;
+        for (int i = tid; i < a.N_o; i += RT) c += om[i] ? 1 : 0;
+        redi[tid] = c;
+        __syncthreads();
+        for (int o = RT / 2; o > 0; o >>= 1) { if (tid < o) redi[tid] += redi[tid + o]; __syncthreads(); }
+        count = redi[0];
+    }
+    if (tid == 0) { a.height[b] = y; if (!from_pred) a.count[b] = count; }
+}
+
+// n consecutive floats between global memory and the workgroup's LDS image, lane i at float i: a row is 3 floats, so a thread
+// that read its own row would stride the wavefront's loads by 12 bytes
+__device__ __forceinline__ void rows_in(float* sh, const float* g, int n) {
+    for (int j = threadIdx.x; j < n; j += RR) sh[j] = g[j];
+}
+__device__ __forceinline__ void rows_out(float* g, const float* sh, int n) {
+    for (int j = threadIdx.x; j < n; j += RR) g[j] = sh[j];
+}
+
+// k_roll_init's row loop: grid (ceil(N / RR), slots), thread = row.
+template <int NH>
+__global__ __launch_bounds__(RR) void k_roll_init_rows(RollRows a) {
+    constexpr int FP = NH == 5 ? F15_PITCH : F12;
+    __shared__ float sh[RR * 3];
+    const int b = blockIdx.y, bg = a.cand ? a.cand[b] : a.b0 + b, tid = threadIdx.x;
+    const int N = a.N_o + a.M;
+    const int i0 = blockIdx.x * RR, i = i0 + tid;
+    const int nr = min(RR, N - i0);                          // rows of this block (> 0 by the grid)
+    const float* src = a.li == 0 ? (a.state0_batched ? a.state0 + (long)bg * a.N_o * 3 : a.state0)
+                                 : a.state_seqs + ((long)bg * a.H + (a.li - 1)) * a.N_o * 3;
+    const uint8_t* om = a.obj_mask ? a.obj_mask + (long)bg * a.N_o : nullptr;
+    const float y = a.height[b];
+    const int count = a.count[b];
+    const int no = max(0, min(nr, a.N_o - i0));              // object rows of this block
+    rows_in(sh, src + (long)i0 * 3, no * 3);
+    __syncthreads();
+    float p[3] = {0.f, 0.f, 0.f}, act[3] = {0.f, 0.f, 0.f};
+    const bool is_tool = i >= a.N_o;
+    if (i < N) {
+        if (!is_tool) {
+            p[0] = sh[3 * tid]; p[1] = sh[3 * tid + 1]; p[2] = sh[3 * tid + 2];
+        } else {
+            const int m = i - a.N_o;
+            const float* xz = a.eef_xz + (((long)bg * a.H + a.li) * a.M + m) * 2;
+            const float* dl = a.eef_delta + (((long)bg * a.H + a.li) * a.M + m) * 3;
+            p[0] = xz[0]; p[1] = y; p[2] = xz[1];
+            act[0] = dl[0]; act[1] = dl[1]; act[2] = dl[2];
+        }
+    }
+    __syncthreads();
+    if (i < N) { sh[3 * tid] = p[0]; sh[3 * tid + 1] = p[1]; sh[3 * tid + 2] = p[2]; }
+    __syncthreads();
+#pragma unroll
+    for (int h = 0; h < NH; ++h) rows_out(a.hist + (((long)b * NH + h) * N + i0) * 3, sh, nr * 3);   // all frames equal (:25)
+    if (i >= N) return;
+    const long row = (long)b * N + i;
+    float* f = a.feat12 + row * FP;
+#pragma unroll
+    for (int c = 0; c < FP; ++c) f[c] = 0.0f;                // identical frames: residuals are exactly 0 (and the row's pad)
+    f[3 * (NH - 1)] = p[0]; f[3 * (NH - 1) + 1] = p[1]; f[3 * (NH - 1) + 2] = p[2];
+    const bool ov = is_tool ? false : (om ? om[i] != 0 : true);
+    float* n = a.node_in + row * NODE_IN;
+    n[0] = ov ? 1.0f : 0.0f;                                 // attrs[:, :nobj, 0] (:92 / :287)
+    n[1] = is_tool ? 1.0f : 0.0f;                            // attrs[:, nobj:, 1] (:93)
+    n[2] = is_tool ? 0.0f : (a.phys_vec ? a.phys_vec[i] : a.phys);                          // model.py:197,206-207
+    n[3] = act[0]; n[4] = act[1]; n[5] = act[2];             // states_delta (:87-88)
+    n[6] = 1.0f; n[7] = 0.0f;
+    for (int k = 0; k < a.n_inst; ++k) a.group[row * a.n_inst + k] = (k == 0 && !is_tool && i < count) ? 1.0f : 0.0f;
+    a.mask[row] = (is_tool || ov) ? 1 : 0;                   // state_mask (:107-109 / :302-304)
+    a.tool[row] = is_tool ? 1 : 0;                           // eef_mask (:111-112)
+    if (a.c_node_in) {                                       // class-table inputs (see GraphBufs)
+        if (is_tool) {
+            float* cn = a.c_node_in + (2L * a.N_o + (long)b * a.M + (i - a.N_o)) * NODE_IN;
+#pragma unroll
+            for (int k = 0; k < NODE_IN; ++k) cn[k] = n[k];
+        } else if (a.write_obj_cls && b == 0) {              // same for every candidate: slot 0 writes both variants
+            float* cv = a.c_node_in + (long)i * NODE_IN;
+            float* ci = a.c_node_in + ((long)a.N_o + i) * NODE_IN;
+            cv[0] = 1.0f; ci[0] = 0.0f;
+#pragma unroll
+            for (int k = 1; k < NODE_IN; ++k) { cv[k] = n[k]; ci[k] = n[k]; }
+        }
+    }
+}
+
+// k_roll_update's row loop: capture, tool advance, history shift, history features.  Grid and thread as k_roll_init_rows; a
+// block touches only its own rows of hist / feat12 / state_seqs, and pred is read-only here.
+template <int NH>
+__global__ __launch_bounds__(RR) void k_roll_update_rows(RollRows a) {
+    constexpr int FP = NH == 5 ? F15_PITCH : F12;
+    __shared__ float sh[NH][RR * 3];
+    __shared__ float shp[RR * 3];
+    const int b = blockIdx.y, bg = a.cand ? a.cand[b] : a.b0 + b, tid = threadIdx.x;
+    const int N = a.N_o + a.M;
+    const int i0 = blockIdx.x * RR, i = i0 + tid;
+    const int nr = min(RR, N - i0);
+    const int no = max(0, min(nr, a.N_o - i0));
+    const float* pred = a.pred + ((long)b * a.N_o + i0) * 3;
+#pragma unroll
+    for (int k = 0; k < NH; ++k) rows_in(sh[k], a.hist + (((long)b * NH + k) * N + i0) * 3, nr * 3);
+    rows_in(shp, pred, no * 3);
+    if (a.repeat[(long)bg * a.H + a.li] == a.ai)             // :160-161
+        for (int j = tid; j < no * 3; j += RR) a.state_seqs[(((long)bg * a.H + a.li) * a.N_o + i0) * 3 + j] = pred[j];
+    __syncthreads();
+    float h[NH][3];
+    if (i < N) {
+#pragma unroll
+        for (int k = 0; k < NH; ++k)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) h[k][c] = sh[k][3 * tid + c];
+        float nw[3];
+        if (i < a.N_o) {
+            nw[0] = shp[3 * tid]; nw[1] = shp[3 * tid + 1]; nw[2] = shp[3 * tid + 2];     // :170
+        } else {
+            const float* act = a.node_in + ((long)b * N + i) * NODE_IN + 3;
+            nw[0] = h[NH - 1][0] + act[0];                                                 // :164
+            nw[1] = a.height[b];                                                           // :166
+            nw[2] = h[NH - 1][2] + act[2];
+        }
+#pragma unroll
+        for (int k = 0; k < NH - 1; ++k)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) h[k][c] = h[k + 1][c];                             // :176
+#pragma unroll
+        for (int c = 0; c < 3; ++c) h[NH - 1][c] = nw[c];
+    }
+    __syncthreads();
+    if (i < N) {
+#pragma unroll
+        for (int k = 0; k < NH; ++k)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) sh[k][3 * tid + c] = h[k][c];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < NH; ++k) rows_out(a.hist + (((long)b * NH + k) * N + i0) * 3, sh[k], nr * 3);
+    if (i >= N) return;
+    float* f = a.feat12 + ((long)b * N + i) * FP;
+#pragma unroll
+    for (int k = 0; k < NH - 1; ++k)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) f[3 * k + c] = h[k + 1][c] - h[k][c];                  // model.py:156
+#pragma unroll
+    for (int c = 0; c < 3; ++c) f[3 * (NH - 1) + c] = h[NH - 1][c];
+}
+
+hipError_t launch_tool_height(const RollRows& a, bool from_pred, hipStream_t st) {
+    hipLaunchKernelGGL(k_tool_height, dim3(a.B), dim3(RT), 0, st, a, from_pred ? 1 : 0);
+    return hipGetLastError();
+}
+hipError_t launch_roll_init_rows(const RollRows& a, hipStream_t st) {
+    const dim3 grid((unsigned)((a.N_o + a.M + RR - 1) / RR), (unsigned)a.B);
+    if (a.n_his == 5) hipLaunchKernelGGL(k_roll_init_rows<5>, grid, dim3(RR), 0, st, a);
+    else hipLaunchKernelGGL(k_roll_init_rows<4>, grid, dim3(RR), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t launch_roll_update_rows(const RollRows& a, hipStream_t st) {
+    const dim3 grid((unsigned)((a.N_o + a.M + RR - 1) / RR), (unsigned)a.B);
+    if (a.n_his == 5) hipLaunchKernelGGL(k_roll_update_rows<5>, grid, dim3(RR), 0, st, a);
+    else hipLaunchKernelGGL(k_roll_update_rows<4>, grid, dim3(RR), 0, st, a);
+    return hipGetLastError();
+}
+
+// Overflow guard of the rollout over cell-list graphs.  The builder reports the TRUE count of a graph above edge_cap and then writes
+// nothing else for it - its row_ptr is whatever the workspace held; a graph between max_nR and edge_cap is written in full.  Either
+// way a graph above max_nR must not be walked: its count becomes 0 and its row_ptr all zeros, so the self-loop pass and the chains
+// see an empty graph, and *overflow takes the largest count.  n_edges is the builder's own array and is only read here.
+__global__ __launch_bounds__(RR) void k_cells_guard(const int* __restrict__ n_edges, int N, int max_nR, int* __restrict__ n_eff,
+                                                     int* __restrict__ row_ptr, int* overflow) {
+    const int b = blockIdx.y, n = n_edges[b];
+    const bool bad = n > max_nR;
+    const int j = blockIdx.x * RR + threadIdx.x;
+    if (bad && j <= N) row_ptr[(long)b * (N + 1) + j] = 0;
+    if (j == 0) {
+        n_eff[b] = bad ? 0 : n;
+        if (bad) atomicMax(overflow, n);
+    }
+}
+hipError_t launch_cells_guard(const int* n_edges, int B, int N, int max_nR, int* n_eff, int* row_ptr, int* overflow, hipStream_t st) {
+    hipLaunchKernelGGL(k_cells_guard, dim3((unsigned)((N + 1 + RR - 1) / RR), (unsigned)B), dim3(RR), 0, st, n_edges, N, max_nR, n_eff,
+                       row_ptr, overflow);
+    return hipGetLastError();
+}
+
 // Work list of a ragged batch (GraphBufs::rowlist).  One workgroup.  Layout: first - only if some particle of the chunk is
 // masked out - the N_o object rows of the phantom candidate (slot B), then for every slot s = 0..B-1 (in slot order, i.e. the
 // repeat-sorted launch order) its valid object particles and its tools.  tab[n] = number of entries when only the first n slots

@@ -100,4 +100,31 @@ hipError_t launch_share_prep(const float* state0, int N_o, int n_his, float* nod
 hipError_t launch_roll_init(const RollArgs& a, const RollBufs& r, const GraphBufs& g, hipStream_t st);
 hipError_t launch_roll_update(const RollArgs& a, const RollBufs& r, const GraphBufs& g, hipStream_t st);
 
+// The same bookkeeping with a candidate's rows spread over the grid, for the rollout over cell-list graphs (ag_rollout_cells: few
+// candidates, up to 2^20 rows each).  What RollArgs / RollBufs / GraphBufs give the kernels above, without the prefix sharing, the
+// device plan's live count and the ragged phantom, which that driver does not use.
+struct RollRows {
+    int B, N_o, M, H, li, ai, y_mode, b0;     // B = slots this launch covers; b0 = first candidate of the chunk in the full batch
+    int n_his, n_inst;
+    float grip; int grip_on; float phys;
+    int write_obj_cls;                        // the init kernel also writes the object rows of the class table
+    const float* phys_vec;                    // null or (N_o,)
+    const float* state0; int state0_batched;  // (N_o,3) or (Bfull,N_o,3)
+    const uint8_t* obj_mask;                  // (Bfull,N_o) or null
+    const float* eef_xz; const float* eef_delta;  // (Bfull,H,M,2), (Bfull,H,M,3)
+    const int* repeat;                        // device (Bfull,H)
+    const int* cand;                          // null, or (B,) device: slot -> candidate of the full batch
+    float* state_seqs;                        // (Bfull,H,N_o,3)
+    float* hist; float* pred; uint8_t* mask; uint8_t* tool;   // RollBufs
+    float* node_in; float* feat12; float* group; float* c_node_in;   // GraphBufs
+    float* height; int* count;                // (slots,): k_tool_height's output, read by the two row kernels
+};
+// tool height (+ gripper offset) per slot from the cloud the look-ahead step starts from (and the masked rollout's count of valid
+// rows), or - from_pred - from the latest prediction
+hipError_t launch_tool_height(const RollRows& a, bool from_pred, hipStream_t st);
+hipError_t launch_roll_init_rows(const RollRows& a, hipStream_t st);
+hipError_t launch_roll_update_rows(const RollRows& a, hipStream_t st);
+// graphs of the cell-list builder above max_nR become empty graphs (n_eff 0, row_ptr zeroed), *overflow = max of their counts
+hipError_t launch_cells_guard(const int* n_edges, int B, int N, int max_nR, int* n_eff, int* row_ptr, int* overflow, hipStream_t st);
+
 }  // namespace ag

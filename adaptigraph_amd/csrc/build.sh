@@ -2,7 +2,7 @@
 # Build libadaptigraph_hip.so for gfx950 (MI355X), in-tree.  hipcc cross-compiles without a GPU.
 #   build.sh         the product library, and libadaptigraph_hip_cma.so: the CMA-ES search (ag_cma.hip, ag_api_cma.hip;
 #                    include/adaptigraph_amd_cma.h), a library of its own that needs no engine context, and
-#                    libadaptigraph_hip_cells.so: the cell-list edge builder (ag_cells.hip, ag_api_cells.hip;
+#                    libadaptigraph_hip_cells.so: the cell-list edge builder and the rollout over its graphs (ag_cells.hip, ag_api_cells.hip;
 #                    include/adaptigraph_amd_cells.h), a library of its own that works on the engine's contexts and links against it
 #   build.sh diag    also libadaptigraph_hip_diag.so: the same sources with -DAG_DIAG (in-kernel clock / phase probes and the
 #                    injected-failure hook, ag_diag.hip) - used by tools/ and one test, never loaded by the product package

@@ -246,6 +246,64 @@ def dynamics_masked(state_init, state_mask, action, model, device, ppm_optimizer
     return {"state_seqs": out[:, 0], "action_seqs": decoded[:, 0].to(action.device)}
 
 
+def _run_cells(model, dev, task, ppm_optimizer, physics_param, B, H, N_o, y_mode, state0, obj_mask, xz, delta, repeat, sync, overflow_flag):
+    """_run on ag_rollout_cells (libadaptigraph_hip_cells.so): the rollout over cell-list graphs, up to 1,048,576 particles."""
+    if not isinstance(model, DynamicsPredictor):
+        raise TypeError("model must be an adaptigraph_amd.DynamicsPredictor")
+    eng = model.engine(dev)
+    assert xz.shape[2] == ppm_optimizer.eef_num
+    p = _rollout_params(task, ppm_optimizer, model, B, H, N_o, y_mode, 0.0)
+    p.physics_param, phys_vec = _physics(ppm_optimizer, physics_param, N_o, dev)
+    xz_d = xz.to(torch.float32).contiguous().to(dev)
+    delta_d = delta.to(torch.float32).contiguous().to(dev)
+    rep = repeat.to("cpu", torch.int32).contiguous()
+    out = torch.empty((B, H, N_o, 3), device=dev, dtype=torch.float32)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev) if sync else overflow_flag
+    assert flag is not None and flag.dtype == torch.int32, "_sync=False needs an int32 device tensor as _overflow_flag"
+    eng.check(_lib.load_cells().ag_rollout_cells(eng.ctx, current_stream(dev), C.byref(p), ptr(state0), ptr(obj_mask), ptr(xz_d),
+                                                 ptr(delta_d), C.c_void_p(rep.data_ptr()), ptr(phys_vec), ptr(out), ptr(flag)))
+    if sync and int(flag.item()) > int(task["max_nR"]):                                    # the one wait of the call
+        raise Exception("Exceeds max dims")                                                # utils.py:63-65
+    return out
+
+
+@torch.no_grad()
+def dynamics_cells(state, action, model, device, ppm_optimizer, physics_param=None, _sync=True, _overflow_flag=None):
+    """dynamics() for graphs beyond its 4096 particles: same arguments, same result dictionary, N_o + M up to 1,048,576
+    (NotImplementedError beyond, and for topk > 128).  Every step builds its graphs with the cell-list builder and runs the same
+    model chains; where dynamics() applies the two return the same bits.  Actions are decoded on the host; the engine's prefix
+    sharing, shared first forward and in-library streams do not run here, so below the limit dynamics() stays the faster path.
+    _sync=False: enqueue only, `_overflow_flag` (zeroed int32 device tensor) receives the largest edge count above max_nR."""
+    task = ppm_optimizer.task_config
+    dev = _require_gpu(device)
+    B, H = action.shape[0], action.shape[1]
+    action_cpu = action.detach().to("cpu", torch.float32)
+    decoded, repeat = decode_action(action_cpu, push_length=task["push_length"])          # :23
+    xz, delta = _tool_layout(decoded, action_cpu[:, :, 2], task)
+    state0 = state.detach().to(dev, torch.float32).contiguous()
+    out = _run_cells(model, dev, task, ppm_optimizer, physics_param, B, H, state0.shape[0], 0, state0, None, xz, delta, repeat,
+                     _sync, _overflow_flag)
+    return {"state_seqs": out, "action_seqs": decoded.to(action.device)}
+
+
+@torch.no_grad()
+def dynamics_masked_cells(state_init, state_mask, action, model, device, ppm_optimizer, physics_param=None, _sync=True,
+                          _overflow_flag=None):
+    """dynamics_masked() on the cell-list builder (see dynamics_cells): same arguments, same result dictionary, same bits where
+    both apply.  Masked-out rows go through the chains like every other row (the dense rows of option ragged = 0)."""
+    task = ppm_optimizer.task_config
+    dev = _require_gpu(device)
+    B = state_init.shape[0]
+    action_cpu = action.detach().to("cpu", torch.float32)[:, None]                         # :218
+    decoded, repeat = decode_action(action_cpu, push_length=task["push_length"])
+    xz, delta = _tool_layout(decoded, action_cpu[:, :, 2], task)
+    state0 = state_init.detach().to(dev, torch.float32).contiguous()
+    mask_u8 = state_mask.detach().to(dev).to(torch.bool).contiguous().view(torch.uint8)
+    out = _run_cells(model, dev, task, ppm_optimizer, physics_param, B, 1, state0.shape[1], 1, state0, mask_u8, xz, delta, repeat,
+                     _sync, _overflow_flag)
+    return {"state_seqs": out[:, 0], "action_seqs": decoded[:, 0].to(action.device)}
+
+
 def _masked_mean_y(pos, maskf, cnt):
     """forward_dynamics.py:233 / :360: the tool height = mean y of the valid object particles.  Summed in float64 and rounded
     once, so that a row's value does not depend on how torch tiles the reduction for the batch it happens to sit in."""

@@ -1,4 +1,4 @@
-/* adaptigraph_amd_cells.h - C-ABI of the cell-list edge builder, gfx950 only.  A library of its own,
+/* adaptigraph_amd_cells.h - C-ABI of the cell-list edge builder and of the rollout over its graphs, gfx950 only.  A library of its own,
  * libadaptigraph_hip_cells.so, beside the engine's (adaptigraph_amd.h, whose export list is closed at ABI version 7): it works on
  * the ENGINE'S contexts - an ag_ctx of ag_ctx_create - and links against libadaptigraph_hip.so, so load both (the engine's first,
  * or let the dynamic linker find it next to this one).  Conventions as in adaptigraph_amd.h: 0 on success, a negative AG_ERR_*
@@ -31,6 +31,24 @@ int ag_build_edges_cells(ag_ctx* ctx, void* stream, const float* d_pos, int64_t 
                          const uint8_t* d_tool_mask, int32_t B, int32_t N, float adj_thresh, const float* d_adj_thresh_vec,
                          const float* d_thr2_vec, int32_t topk, int32_t rule, int64_t edge_cap, int32_t* d_recv, int32_t* d_send,
                          int32_t* d_row_ptr, int32_t* d_n_edges);
+
+/* ag_rollout_async over graphs of up to 1,048,576 particles: same arguments, same contract (enqueue only, on the caller's stream;
+ * d_state_seqs (B,H,N_o,3) is cleared first; h_repeat may die right after the call), and - where both apply, N_o + M <= 4096 - the
+ * same bits as ag_rollout_async.  Per rollout step: the cell-list builder above on the newest history frame (rule = connect_tools_all
+ * ? 1 : 0), an overflow guard, the self-loop pass (option self_dedupe), the model forward, then the tool height and the history
+ * shift with a candidate's rows spread over the grid.  Actions are host-decoded (d_eef_xz, d_eef_delta, h_repeat as ag_rollout_async
+ * takes them); every chunk's candidates are stepped in descending order of their repeat, live ones only, so ag_ctx_rollout_counts
+ * reports executed == needed.  The engine's options that select kernels (precision, latency, self_dedupe, zero_skip, half_step,
+ * chunk) apply; those of ag_rollout_async's own machinery (ell_graph, share_first, share_prefix, streams, device_decode, ragged,
+ * repeat_sort, edge_order) are not read.
+ *   overflow   a graph with more than max_nR edges is stepped as an EMPTY graph (its count and row_ptr are zeroed before anything
+ *              walks them) and *d_overflow_flag = max(*d_overflow_flag, its edge count); the caller zeroes the flag before the call
+ *              and raises when it reads a value above max_nR.
+ * Refused with AG_ERR_UNSUPPORTED before anything is enqueued: N_o + M > 1,048,576; topk > 128; M > 8; a graph whose rows or edge
+ * slots exceed the 32-bit activation offsets; bf16x3 with n_his 5. */
+int ag_rollout_cells(ag_ctx* ctx, void* stream, const ag_rollout_params* p, const float* d_state0, const uint8_t* d_obj_mask,
+                     const float* d_eef_xz, const float* d_eef_delta, const int32_t* h_repeat, const float* d_phys_vec,
+                     float* d_state_seqs, int32_t* d_overflow_flag);
 
 #ifdef __cplusplus
 }

@@ -41,7 +41,8 @@ from .graph import (EdgeList, construct_edges_from_states_batch, construct_edges
                     BackoffPlan, RuleConfig, rule_attempt, backoff_rounds, attempt_with_backoff)
 from .model import DynamicsPredictor
 from .plan_utils import decode_action
-from .losses import chamfer, chamfer_diff, mean_chamfer, box_loss, rope_penalty, cloth_penalty, granular_penalty
+from .losses import (chamfer, chamfer_diff, mean_chamfer, box_loss, rope_penalty, cloth_penalty, granular_penalty, chamfer_tiled,
+                     chamfer_tiled_diff, mean_chamfer_tiled)
 from .costs import running_cost
 from .physics_param_optimizer import (dynamics_error, dynamics_error_sweep, dynamics_error_grad, optimize_grad, PhysParamFit,
                                       optimize_grad_device, dynamics_error_grad_device)
@@ -63,4 +64,4 @@ __all__ = ["hw_queues", "Engine", "default_engine", "dynamics", "dynamics_masked
            "optimize_grad_device", "dynamics_error_grad_device", "DeviceDynDataset", "BatchDraws", "construct_edges_graphs",
            "nonfixed_rule_graphs", "surface_rule_graphs", "BackoffPlan", "RuleConfig", "rule_attempt", "backoff_rounds", "attempt_with_backoff",
            "ChamferLoss", "HausdorffLoss", "EarthMoverLoss", "earth_mover_assignment", "LossSpec", "prefix_counts", "perception", "fps_cloud", "construct_graph", "state_cur_from_points",
-           "CmaSearch"]
+           "CmaSearch", "chamfer_tiled", "chamfer_tiled_diff", "mean_chamfer_tiled"]

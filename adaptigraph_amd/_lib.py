@@ -41,7 +41,8 @@ CMA_EXPORTS = ["ag_cma_state_doubles", "ag_cma_init", "ag_cma_ask", "ag_cma_tell
 # so is the cell-list edge builder (include/adaptigraph_amd_cells.h; tests/test_cells_restate.py holds this to that header); it works
 # on the engine's contexts and links against the engine's library
 CELLS_LIB_PATH = os.path.join(_HERE, "csrc", "libadaptigraph_hip_cells.so")
-CELLS_EXPORTS = ["ag_build_edges_cells", "ag_rollout_cells"]
+CELLS_EXPORTS = ["ag_build_edges_cells", "ag_rollout_cells", "ag_cost_chamfer_tiled", "ag_cost_chamfer_tiled_backward"]
+CHAMFER_TILED_MAX_POINTS, CHAMFER_TILED_MAX_TILE, CHAMFER_TILED_DEFAULT_TILE = 1 << 20, 4096, 2048     # ag_chamfer_tiled.h
 
 AG_LOSS_MSE, AG_LOSS_CHAMFER, AG_LOSS_HAUSDORFF, AG_LOSS_EMD = 0, 1, 2, 3
 AG_LOSS_ROWS = 16                       # flag on a set kind: each graph's real rows (adaptigraph_amd.h, ag_set_loss)
@@ -240,5 +241,9 @@ def load_cells():
     lib.ag_build_edges_cells.restype = C.c_int
     lib.ag_rollout_cells.argtypes = [vp, vp, C.POINTER(AgRolloutParams), vp, vp, vp, vp, vp, vp, vp, vp]   # as ag_rollout_async
     lib.ag_rollout_cells.restype = C.c_int
+    lib.ag_cost_chamfer_tiled.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]           # as ag_cost_chamfer, + tile_points
+    lib.ag_cost_chamfer_tiled.restype = C.c_int
+    lib.ag_cost_chamfer_tiled_backward.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]
+    lib.ag_cost_chamfer_tiled_backward.restype = C.c_int
     _cells = lib
     return lib

@@ -1,8 +1,9 @@
-// C-ABI of the cell-list edge builder and of the rollout over its graphs (include/adaptigraph_amd_cells.h): libadaptigraph_hip_cells.so, a library of its own
+// C-ABI of the cell-list edge builder, of the rollout over its graphs and of the tiled Chamfer cost (include/adaptigraph_amd_cells.h): libadaptigraph_hip_cells.so, a library of its own
 // beside the engine's - the engine's export list is closed at ABI version 7 - that works on the engine's contexts: it links
 // against libadaptigraph_hip.so and takes its stream slot and its scratch from the context like every engine entry point.
 #include "../../include/adaptigraph_amd_cells.h"
 #include "ag_cells.h"
+#include "ag_chamfer_tiled.h"
 #include "ag_host.h"
 
 #include <climits>
@@ -195,5 +196,59 @@ extern "C" int ag_rollout_cells(ag_ctx* c, void* stream, const ag_rollout_params
             }
         }
     }
+    return AG_OK;
+}
+
+// ================================================================================================ ag_cost_chamfer_tiled
+// ag_cost_chamfer / ag_cost_chamfer_backward past the LDS limit of ag_cost.hip (ag_chamfer_tiled.hip).  The per-point tables come from
+// the call slot's slab; everything is enqueued on the caller's stream.
+namespace {
+// the checks both entry points share; *tile becomes the tile the kernels run with
+int chamfer_tiled_check(ag_ctx* c, const char* me, bool ptrs_ok, int R, int N, int M, int By, int32_t* tile) {
+    if (!ptrs_ok || R < 1 || N < 1 || M < 1 || (By != 1 && By != R))
+        return fail(c, AG_ERR_INVALID, "%s: bad arguments R=%d N=%d M=%d By=%d", me, R, N, M, By);
+    if (*tile == 0) *tile = CHAMFER_TILED_DEFAULT_TILE;
+    if (*tile < 2 || *tile > CHAMFER_TILED_MAX_TILE || (*tile & 1))
+        return fail(c, AG_ERR_INVALID, "%s: tile_points=%d is not 0 or an even number in [2, %d]", me, *tile, CHAMFER_TILED_MAX_TILE);
+    if (N > CHAMFER_TILED_MAX_POINTS || M > CHAMFER_TILED_MAX_POINTS)
+        return fail(c, AG_ERR_UNSUPPORTED, "%s: N=%d, M=%d exceed the tiled kernels' limit of %d points per cloud", me, N, M, CHAMFER_TILED_MAX_POINTS);
+    // the tables' entries, and with them the workgroups of every launch (each covers at least one entry), are counted in int32
+    if ((long)R * ((long)N + M) > (long)INT32_MAX)
+        return fail(c, AG_ERR_UNSUPPORTED, "%s: R*(N+M)=%ld table entries exceed %d", me, (long)R * ((long)N + M), INT32_MAX);
+    return AG_OK;
+}
+}  // namespace
+
+extern "C" int ag_cost_chamfer_tiled(ag_ctx* c, void* stream, const float* d_x, const float* d_y, const uint8_t* d_xmask,
+                                     const uint8_t* d_ymask, int32_t R, int32_t N, int32_t M, int32_t By, int32_t tile_points,
+                                     float* d_out) {
+    if (!c) return AG_ERR_INVALID;
+    int rc = chamfer_tiled_check(c, "ag_cost_chamfer_tiled", d_x && d_y && d_out, R, N, M, By, &tile_points);
+    if (rc) return rc;
+    SlotGuard call;
+    rc = begin_call(c, stream, call);
+    if (rc) return rc;
+    float* d2 = nullptr;
+    rc = carve_slab(c, *call.sl, [&](Slab& s) { d2 = s.take<float>((size_t)R * ((size_t)N + M)); });
+    if (rc) return rc;
+    Scoped p(c, FAM_COST);
+    HIPCHK(c, launch_chamfer_tiled(d_x, d_y, d_xmask, d_ymask, R, N, M, By, tile_points, d2, d_out, call.st));
+    return AG_OK;
+}
+
+extern "C" int ag_cost_chamfer_tiled_backward(ag_ctx* c, void* stream, const float* d_x, const float* d_y, const uint8_t* d_xmask,
+                                              const uint8_t* d_ymask, int32_t R, int32_t N, int32_t M, int32_t By, int32_t tile_points,
+                                              const float* d_grad_out, float* d_grad_x) {
+    if (!c) return AG_ERR_INVALID;
+    int rc = chamfer_tiled_check(c, "ag_cost_chamfer_tiled_backward", d_x && d_y && d_grad_out && d_grad_x, R, N, M, By, &tile_points);
+    if (rc) return rc;
+    SlotGuard call;
+    rc = begin_call(c, stream, call);
+    if (rc) return rc;
+    int* nn = nullptr; float* cnt = nullptr;
+    rc = carve_slab(c, *call.sl, [&](Slab& s) { nn = s.take<int>((size_t)R * ((size_t)N + M)); cnt = s.take<float>((size_t)R * 2); });
+    if (rc) return rc;
+    Scoped p(c, FAM_COST);
+    HIPCHK(c, launch_chamfer_tiled_backward(d_x, d_y, d_xmask, d_ymask, R, N, M, By, tile_points, d_grad_out, nn, cnt, d_grad_x, call.st));
     return AG_OK;
 }

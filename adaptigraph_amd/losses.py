@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 import torch
 
+from . import _lib
 from .context import default_engine, ptr, current_stream, _require_gpu
 
 _KIND = {"rope": 0, "cloth": 1, "granular": 2}
@@ -84,6 +85,74 @@ def chamfer_diff(x, y, x_mask=None, y_mask=None):
 def mean_chamfer(state_pred, state_real, state_pred_mask, state_real_mask):
     """losses.py:12-24: per-pair masked chamfer, returned as a numpy float64 array like the reference."""
     out = chamfer(state_pred, state_real, state_pred_mask, state_real_mask)
+    return out.detach().cpu().numpy().astype(np.float64)
+
+
+def _tiled_args(x, y, x_mask, y_mask, tile):
+    dev = _require_gpu(x.device)
+    x = x.to(torch.float32).contiguous()
+    y = y.detach().to(device=dev, dtype=torch.float32).contiguous()
+    xm = x_mask.to(dev).to(torch.bool).contiguous().view(torch.uint8) if x_mask is not None else None
+    ym = y_mask.to(dev).to(torch.bool).contiguous().view(torch.uint8) if y_mask is not None else None
+    return x, y, xm, ym, 0 if tile is None else int(tile)
+
+
+def chamfer_tiled(x, y, x_mask=None, y_mask=None, tile=None):
+    """chamfer() for clouds of any size up to 1,048,576 points each (ag_cost_chamfer_tiled): x (B,N,3), y (1|B,M,3) -> (B,), with
+    chamfer()'s bits wherever chamfer() applies.  A row is spread over ceil(N/1024) + ceil(M/1024) workgroups, each streaming the
+    other cloud through LDS in tiles of `tile` points (None: the default; an even number up to 4096; the result does not depend on it)."""
+    x, y, xm, ym, tile = _tiled_args(x, y, x_mask, y_mask, tile)
+    dev = x.device
+    eng = default_engine(dev)
+    R, N, _ = x.shape
+    By, M, _ = y.shape
+    out = torch.empty(R, device=dev, dtype=torch.float32)
+    eng.check(_lib.load_cells().ag_cost_chamfer_tiled(eng.ctx, current_stream(dev), ptr(x), ptr(y), ptr(xm), ptr(ym), R, N, M, By, tile,
+                                                      ptr(out)))
+    return out
+
+
+class _ChamferTiledFunction(torch.autograd.Function):
+    """ag_cost_chamfer_tiled forward, ag_cost_chamfer_tiled_backward backward; gradient toward x only."""
+
+    @staticmethod
+    def forward(ctx, x, y, xm, ym, tile):
+        dev = x.device
+        eng = default_engine(dev)
+        R, N, _ = x.shape
+        By, M, _ = y.shape
+        out = torch.empty(R, device=dev, dtype=torch.float32)
+        eng.check(_lib.load_cells().ag_cost_chamfer_tiled(eng.ctx, current_stream(dev), ptr(x), ptr(y), ptr(xm), ptr(ym), R, N, M, By,
+                                                          tile, ptr(out)))
+        ctx.save_for_backward(x, y, xm, ym)
+        ctx.tile = tile
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        x, y, xm, ym = ctx.saved_tensors
+        dev = x.device
+        eng = default_engine(dev)
+        R, N, _ = x.shape
+        By, M, _ = y.shape
+        g_out = g_out.to(torch.float32).contiguous()
+        g_x = torch.empty_like(x)
+        eng.check(_lib.load_cells().ag_cost_chamfer_tiled_backward(eng.ctx, current_stream(dev), ptr(x), ptr(y), ptr(xm), ptr(ym), R, N, M,
+                                                                   By, ctx.tile, ptr(g_out), ptr(g_x)))
+        return g_x, None, None, None, None
+
+
+def chamfer_tiled_diff(x, y, x_mask=None, y_mask=None, tile=None):
+    """chamfer_tiled() under torch autograd: the same forward and, on finite input, chamfer_diff()'s gradient toward x bit for bit
+    wherever chamfer_diff() applies (each min routes to its arg-min, the lowest index among equal distances; zero at zero distance
+    and for masked-out points).  y is data."""
+    x, y, xm, ym, tile = _tiled_args(x, y, x_mask, y_mask, tile)
+    return _ChamferTiledFunction.apply(x, y, xm, ym, tile)
+
+
+def mean_chamfer_tiled(state_pred, state_real, state_pred_mask, state_real_mask):
+    """mean_chamfer() on chamfer_tiled(): per-pair masked chamfer of clouds of any size, as a numpy float64 array."""
+    out = chamfer_tiled(state_pred, state_real, state_pred_mask, state_real_mask)
     return out.detach().cpu().numpy().astype(np.float64)
 
 

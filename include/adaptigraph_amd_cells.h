@@ -50,6 +50,26 @@ int ag_rollout_cells(ag_ctx* ctx, void* stream, const ag_rollout_params* p, cons
                      const float* d_eef_xz, const float* d_eef_delta, const int32_t* h_repeat, const float* d_phys_vec,
                      float* d_state_seqs, int32_t* d_overflow_flag);
 
+/* The Chamfer cost of the engine's cost entry and its backward, for clouds of up to 1,048,576 points each: the same arguments and
+ * conventions (d_x (R,N,3), d_y (By,M,3) with By == 1 or By == R, optional (R,N) / (By,M) uint8 masks that may be NULL, d_out (R,);
+ * the backward takes d_grad_out (R,) and writes d_grad_x (R,N,3), exact zeros for masked-out points), and - wherever the engine's
+ * entries apply, N + M <= 13,480 - their bits, for every tile size: on finite input for the gradient; for the cost also on
+ * non-finite input as far as NaN and +inf go (a row with a NaN or infinite coordinate in a valid point is NaN where the engine's
+ * entry gives NaN and +inf where it gives +inf; the other rows keep their bits).  What a masked-out slot holds is never read.
+ * A workgroup owns up to 1024 points of one cloud of one row and streams the other cloud through a tile of tile_points points in
+ * LDS, so the memory per workgroup does not grow with the clouds and a row is spread over ceil(N/1024) + ceil(M/1024) workgroups.
+ *   tile_points  0: the default (2048); else an even number in [2, 4096]; anything else: AG_ERR_INVALID
+ * Among equal distances the gradient routes to the lowest index, across tiles as well.  An empty valid set on either side gives
+ * what the engine's entries give: the cost of that row is NaN (the mean over no point is 0/0), its gradient is zero.
+ * Limits, refused with AG_ERR_UNSUPPORTED before anything is enqueued and with d_out / d_grad_x untouched: N or M above 1,048,576;
+ * R * (N + M) above INT32_MAX (the per-point tables, R * (N + M) floats or ints from the call's workspace, are indexed - and the
+ * workgroups of every launch counted - in int32).  Enqueue only, on the caller's stream: no host wait inside the call. */
+int ag_cost_chamfer_tiled(ag_ctx* ctx, void* stream, const float* d_x, const float* d_y, const uint8_t* d_xmask,
+                          const uint8_t* d_ymask, int32_t R, int32_t N, int32_t M, int32_t By, int32_t tile_points, float* d_out);
+int ag_cost_chamfer_tiled_backward(ag_ctx* ctx, void* stream, const float* d_x, const float* d_y, const uint8_t* d_xmask,
+                                   const uint8_t* d_ymask, int32_t R, int32_t N, int32_t M, int32_t By, int32_t tile_points,
+                                   const float* d_grad_out, float* d_grad_x);
+
 #ifdef __cplusplus
 }
 #endif

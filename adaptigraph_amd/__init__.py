@@ -54,7 +54,8 @@ from .train_step import TrainStep
 from .set_losses import ChamferLoss, HausdorffLoss, EarthMoverLoss, earth_mover_assignment, LossSpec, prefix_counts
 from .dataset import DeviceDynDataset, BatchDraws
 from . import perception
-from .perception import fps_cloud, construct_graph, state_cur_from_points
+from .perception import (fps_cloud, construct_graph, state_cur_from_points, fps_cloud_grid, construct_graph_grid,
+                         state_cur_from_points_grid)
 
 __all__ = ["hw_queues", "Engine", "default_engine", "dynamics", "dynamics_masked", "dynamics_mixed", "rollout_work", "EdgeList", "construct_edges_from_states_batch", "construct_edges_from_states",
            "construct_edges_index", "construct_edges_cells", "construct_edges_with_backoff", "pad_torch", "truncate_graph", "DynamicsPredictor", "decode_action", "chamfer",
@@ -64,4 +65,5 @@ __all__ = ["hw_queues", "Engine", "default_engine", "dynamics", "dynamics_masked
            "optimize_grad_device", "dynamics_error_grad_device", "DeviceDynDataset", "BatchDraws", "construct_edges_graphs",
            "nonfixed_rule_graphs", "surface_rule_graphs", "BackoffPlan", "RuleConfig", "rule_attempt", "backoff_rounds", "attempt_with_backoff",
            "ChamferLoss", "HausdorffLoss", "EarthMoverLoss", "earth_mover_assignment", "LossSpec", "prefix_counts", "perception", "fps_cloud", "construct_graph", "state_cur_from_points",
-           "CmaSearch", "chamfer_tiled", "chamfer_tiled_diff", "mean_chamfer_tiled"]
+           "CmaSearch", "chamfer_tiled", "chamfer_tiled_diff", "mean_chamfer_tiled", "fps_cloud_grid", "construct_graph_grid",
+           "state_cur_from_points_grid"]

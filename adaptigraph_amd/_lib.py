@@ -41,7 +41,7 @@ CMA_EXPORTS = ["ag_cma_state_doubles", "ag_cma_init", "ag_cma_ask", "ag_cma_tell
 # so is the cell-list edge builder (include/adaptigraph_amd_cells.h; tests/test_cells_restate.py holds this to that header); it works
 # on the engine's contexts and links against the engine's library
 CELLS_LIB_PATH = os.path.join(_HERE, "csrc", "libadaptigraph_hip_cells.so")
-CELLS_EXPORTS = ["ag_build_edges_cells", "ag_rollout_cells", "ag_cost_chamfer_tiled", "ag_cost_chamfer_tiled_backward"]
+CELLS_EXPORTS = ["ag_build_edges_cells", "ag_rollout_cells", "ag_cost_chamfer_tiled", "ag_cost_chamfer_tiled_backward", "ag_fps_cloud_grid"]
 CHAMFER_TILED_MAX_POINTS, CHAMFER_TILED_MAX_TILE, CHAMFER_TILED_DEFAULT_TILE = 1 << 20, 4096, 2048     # ag_chamfer_tiled.h
 
 AG_LOSS_MSE, AG_LOSS_CHAMFER, AG_LOSS_HAUSDORFF, AG_LOSS_EMD = 0, 1, 2, 3
@@ -245,5 +245,7 @@ def load_cells():
     lib.ag_cost_chamfer_tiled.restype = C.c_int
     lib.ag_cost_chamfer_tiled_backward.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]
     lib.ag_cost_chamfer_tiled_backward.restype = C.c_int
+    lib.ag_fps_cloud_grid.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp]    # as ag_fps_cloud, + cells
+    lib.ag_fps_cloud_grid.restype = C.c_int
     _cells = lib
     return lib

@@ -1,9 +1,10 @@
-// C-ABI of the cell-list edge builder, of the rollout over its graphs and of the tiled Chamfer cost (include/adaptigraph_amd_cells.h): libadaptigraph_hip_cells.so, a library of its own
+// C-ABI of the cell-list edge builder, of the rollout over its graphs, of the tiled Chamfer cost and of the cell-pruned farthest-point sampler (include/adaptigraph_amd_cells.h): libadaptigraph_hip_cells.so, a library of its own
 // beside the engine's - the engine's export list is closed at ABI version 7 - that works on the engine's contexts: it links
 // against libadaptigraph_hip.so and takes its stream slot and its scratch from the context like every engine entry point.
 #include "../../include/adaptigraph_amd_cells.h"
 #include "ag_cells.h"
 #include "ag_chamfer_tiled.h"
+#include "ag_fps_grid.h"
 #include "ag_host.h"
 
 #include <climits>
@@ -250,5 +251,54 @@ extern "C" int ag_cost_chamfer_tiled_backward(ag_ctx* c, void* stream, const flo
     if (rc) return rc;
     Scoped p(c, FAM_COST);
     HIPCHK(c, launch_chamfer_tiled_backward(d_x, d_y, d_xmask, d_ymask, R, N, M, By, tile_points, d_grad_out, nn, cnt, d_grad_x, call.st));
+    return AG_OK;
+}
+
+// ================================================================================================ ag_fps_cloud_grid
+// ag_fps_cloud past its 1024 samples (ag_fps_grid.hip): both stages binned into cells and pruned by the cells' boxes, same indices.
+namespace {
+// one binning pass's scratch for B clouds of up to P points (FpsBinWs says what each part holds)
+void carve_fps_bin(Slab& s, FpsBinWs& w, int B, int P, int cells) {
+    const size_t nB = (size_t)B, rows = nB * (size_t)P, cc = (size_t)fps_grid_cells_cap(P, cells);
+    w.cells_cap = (int)cc; w.zeroed_words = nB * (6 + cc + 1);
+    w.zeroed = s.take<unsigned>(w.zeroed_words); w.grid = s.take<char>(nB * fps_grid_bytes());
+    w.start = s.take<int>(nB * (cc + 2)); w.cid = s.take<int>(rows); w.slot = s.take<int>(rows);
+    w.sorted = s.take<float>(rows * 4); w.md = s.take<float>(rows);
+    w.box = s.take<float>(nB * (cc + 1) * 6); w.key0 = s.take<unsigned long long>(nB * (cc + 1));
+    w.tab = s.take<char>(nB * fps_grid_tab_bytes((int)cc));
+}
+}  // namespace
+
+extern "C" int ag_fps_cloud_grid(ag_ctx* c, void* stream, const float* d_pos, const int64_t* d_pt_off, const int64_t* d_npts,
+                                 int32_t stride, const int32_t* d_fps_start, const float* d_fps_radius, const int32_t* d_rad_start,
+                                 int32_t B, int32_t max_nobj, int32_t max_pts, int32_t cells, int32_t* d_fps_idx, int32_t* d_n_obj) {
+    if (!c) return AG_ERR_INVALID;
+    const char* me = "ag_fps_cloud_grid";
+    if (!d_pos || !d_pt_off || !d_npts || !d_fps_start || !d_fps_radius || !d_rad_start || !d_fps_idx || !d_n_obj)
+        return fail(c, AG_ERR_INVALID, "%s: null pointer", me);
+    if (B < 1 || stride < 1 || max_nobj < 1 || max_pts < 1)
+        return fail(c, AG_ERR_INVALID, "%s: B=%d stride=%d max_nobj=%d max_pts=%d", me, B, stride, max_nobj, max_pts);
+    if (cells < 0 || (cells & (cells - 1)) || cells > FPS_GRID_MAX_CELLS)
+        return fail(c, AG_ERR_INVALID, "%s: cells=%d is not 0 or a power of two up to %d", me, cells, FPS_GRID_MAX_CELLS);
+    if (max_pts > FPS_GRID_MAX_POINTS)
+        return fail(c, AG_ERR_UNSUPPORTED, "%s: a cloud of %d points exceeds the limit %d", me, max_pts, FPS_GRID_MAX_POINTS);
+    if (max_nobj > FPS_GRID_MAX_NOBJ) return fail(c, AG_ERR_UNSUPPORTED, "%s: max_nobj=%d exceeds %d", me, max_nobj, FPS_GRID_MAX_NOBJ);
+    if (B > CELLS_MAX_GRAPHS) return fail(c, AG_ERR_UNSUPPORTED, "%s: B=%d exceeds %d clouds per call", me, B, CELLS_MAX_GRAPHS);
+    SlotGuard call;
+    int rc = begin_call(c, stream, call);
+    if (rc) return rc;
+    FpsGridArgs a{};
+    a.pos = d_pos; a.pt_off = reinterpret_cast<const long long*>(d_pt_off); a.npts = reinterpret_cast<const long long*>(d_npts);
+    a.stride = stride; a.fps_start = d_fps_start; a.fps_radius = d_fps_radius; a.rad_start = d_rad_start;
+    a.B = B; a.max_nobj = max_nobj; a.max_pts = max_pts; a.cells = cells; a.fps_idx = d_fps_idx; a.n_obj = d_n_obj;
+    rc = carve_slab(c, *call.sl, [&](Slab& s) {
+        carve_fps_bin(s, a.w1, B, max_pts, cells);
+        carve_fps_bin(s, a.w2, B, max_nobj, cells);
+        a.s1pos = s.take<float>((size_t)B * max_nobj * 3); a.s1idx = s.take<int>((size_t)B * max_nobj);
+        a.off2 = s.take<long long>(B); a.n2 = s.take<long long>(B);
+    });
+    if (rc) return rc;
+    Scoped p(c, FAM_FPS);
+    HIPCHK(c, launch_fps_grid(a, call.st));
     return AG_OK;
 }

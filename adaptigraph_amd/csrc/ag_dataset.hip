@@ -18,6 +18,7 @@
 #include "../../include/adaptigraph_amd.h"
 #include "ag_dataset.h"
 #include "ag_dist.h"
+#include "ag_fps_key.h"
 #include "ag_lds_optin.h"
 
 namespace ag {
@@ -31,36 +32,6 @@ constexpr int FPS_MAX_NOBJ = FW * FPS_PPT2;        // 1024 stage-1 points (16 KB
 
 size_t fps_max_points() { return FPS_MAX_POINTS; }
 int fps_max_nobj() { return FPS_MAX_NOBJ; }
-
-__device__ __forceinline__ unsigned long long fps_key(float d, int i) {
-    return ((unsigned long long)__float_as_uint(d) << 32) | (0xffffffffu - (unsigned)i);
-}
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned lo = __shfl_xor((unsigned)(v & 0xffffffffull), o);
-        const unsigned hi = __shfl_xor((unsigned)(v >> 32), o);
-        const unsigned long long w = ((unsigned long long)hi << 32) | lo;
-        v = w > v ? w : v;
-    }
-    return v;
-}
-// max of `mine` over the workgroup, in every thread.  `it` counts the reductions of the launch: consecutive ones use
-// alternate halves of wkey, so one barrier per reduction is enough (a thread can only overwrite a half after every thread
-// has passed the barrier of the reduction in between, i.e. has read it).
-// WAVES: wavefronts of the workgroup (wkey holds 2 * WAVES keys).
-template <int WAVES = FWAVES>
-__device__ __forceinline__ unsigned long long block_max_u64(unsigned long long mine, unsigned long long* wkey, int& it) {
-    mine = wave_max_u64(mine);
-    unsigned long long* w = wkey + (it & 1) * WAVES;
-    if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = mine;
-    __syncthreads();
-    unsigned long long g = w[0];
-#pragma unroll
-    for (int k = 1; k < WAVES; ++k) g = w[k] > g ? w[k] : g;
-    ++it;
-    return g;
-}
 
 // Stage 2 (fps_rad_idx) on the n1 stage-1 points sx / sy / sz (LDS, selection order; sidx: their cloud indices), starting at
 // `cur`, by a workgroup of W threads that keeps PPT2 points each (W * PPT2 >= n1): writes the kept cloud indices to out[] in
@@ -148,7 +119,7 @@ __global__ __launch_bounds__(FW) void k_fps_batch(FpsDev a) {
                 best = key > best ? key : best;
             }
         }
-        const unsigned long long g = block_max_u64(best, wkey, it);
+        const unsigned long long g = block_max_u64<FWAVES>(best, wkey, it);
         cur = (int)(0xffffffffu - (unsigned)(g & 0xffffffffull));
         if (tid == 0) { sidx[k] = cur; sx[k] = x[cur]; sy[k] = y[cur]; sz[k] = z[cur]; }
     }

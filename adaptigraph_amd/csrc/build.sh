@@ -2,8 +2,8 @@
 # Build libadaptigraph_hip.so for gfx950 (MI355X), in-tree.  hipcc cross-compiles without a GPU.
 #   build.sh         the product library, and libadaptigraph_hip_cma.so: the CMA-ES search (ag_cma.hip, ag_api_cma.hip;
 #                    include/adaptigraph_amd_cma.h), a library of its own that needs no engine context, and
-#                    libadaptigraph_hip_cells.so: the cell-list edge builder, the rollout over its graphs and the tiled Chamfer cost
-#                    (ag_cells.hip, ag_chamfer_tiled.hip, ag_api_cells.hip;
+#                    libadaptigraph_hip_cells.so: the cell-list edge builder, the rollout over its graphs, the tiled Chamfer cost and
+#                    the cell-pruned farthest-point sampler (ag_cells.hip, ag_chamfer_tiled.hip, ag_fps_grid.hip, ag_api_cells.hip;
 #                    include/adaptigraph_amd_cells.h), a library of its own that works on the engine's contexts and links against it
 #   build.sh diag    also libadaptigraph_hip_diag.so: the same sources with -DAG_DIAG (in-kernel clock / phase probes and the
 #                    injected-failure hook, ag_diag.hip) - used by tools/ and one test, never loaded by the product package
@@ -38,7 +38,7 @@ variant product build "" libadaptigraph_hip.so "$ENGINE_SRCS"
 variant cma build/cma "" libadaptigraph_hip_cma.so "ag_cma ag_api_cma"
 # The cells library calls the engine's internal C++ helpers (begin_call, fail, the slab of ag_host.h) and reads ag_ctx's layout across
 # the shared-object boundary: the two are always built together, here, from one tree.  The diag and experiment variants get none.
-variant cells build/cells "" libadaptigraph_hip_cells.so "ag_cells ag_chamfer_tiled ag_api_cells" "-L. -ladaptigraph_hip -Wl,-rpath,\$ORIGIN"
+variant cells build/cells "" libadaptigraph_hip_cells.so "ag_cells ag_chamfer_tiled ag_fps_grid ag_api_cells" "-L. -ladaptigraph_hip -Wl,-rpath,\$ORIGIN"
 variant diag build/diag "-DAG_DIAG" libadaptigraph_hip_diag.so "$ENGINE_SRCS ag_diag"
 
 DRY=0; NEWER=" "

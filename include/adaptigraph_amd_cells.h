@@ -1,4 +1,5 @@
-/* adaptigraph_amd_cells.h - C-ABI of the cell-list edge builder and of the rollout over its graphs, gfx950 only.  A library of its own,
+/* adaptigraph_amd_cells.h - C-ABI of the cell-list edge builder, of the rollout over its graphs, of the tiled Chamfer cost and of the cell-pruned
+ * farthest-point sampler, gfx950 only.  A library of its own,
  * libadaptigraph_hip_cells.so, beside the engine's (adaptigraph_amd.h, whose export list is closed at ABI version 7): it works on
  * the ENGINE'S contexts - an ag_ctx of ag_ctx_create - and links against libadaptigraph_hip.so, so load both (the engine's first,
  * or let the dynamic linker find it next to this one).  Conventions as in adaptigraph_amd.h: 0 on success, a negative AG_ERR_*
@@ -69,6 +70,25 @@ int ag_cost_chamfer_tiled(ag_ctx* ctx, void* stream, const float* d_x, const flo
 int ag_cost_chamfer_tiled_backward(ag_ctx* ctx, void* stream, const float* d_x, const float* d_y, const uint8_t* d_xmask,
                                    const uint8_t* d_ymask, int32_t R, int32_t N, int32_t M, int32_t By, int32_t tile_points,
                                    const float* d_grad_out, float* d_grad_x);
+
+/* ag_fps_cloud (adaptigraph_amd.h) past its 1024 samples: the same arguments plus `cells`, the same contract and outputs -
+ * d_fps_idx (B,max_nobj) int32 = stage1[stage2] in selection order, then -1; d_n_obj (B,) the counts; start indices clamped, a
+ * count above max_pts truncated.  Both stages are exact cell-pruned farthest-point
+ * sampling: the points are binned into cells, a cell keeps its tight box and the largest running minimum among its members, and
+ * after a new centre only the cells whose box is nearer than that maximum are visited.  The minima are updated with ag_fps_cloud's
+ * arithmetic and the argmax is its packed key, so the result is that of the brute-force sweep whatever the partition; a point with
+ * a NaN or infinite coordinate lives in a cell of its own kind that is never pruned, and is treated as that sweep treats it.
+ * Stage 2's square root is correctly rounded (np.linalg.norm's); ag_fps_cloud's is the native one, good to 1 ulp, so the two entries
+ * give the same bits wherever that ulp decides no pick - on every cloud ag_fps_cloud's own tests hold - and this one follows the
+ * numpy restatement where they part (lattices with many distances within an ulp of each other or of the radius).
+ *   cells   0: the default policy (a power of two with about 64 points per cell, at most 16,384 cells per cloud); else a power of
+ *           two up to 16,384 that forces the cell count per cloud (1 = the brute-force sweep through the same code); anything else:
+ *           AG_ERR_INVALID
+ * Limits, refused with AG_ERR_UNSUPPORTED before anything is allocated or enqueued: max_nobj <= 65,536; max_pts <= 1,048,576;
+ * B <= 65,535.  Enqueue only, on the caller's stream; the workspace comes from the call slot's slab. */
+int ag_fps_cloud_grid(ag_ctx* ctx, void* stream, const float* d_pos, const int64_t* d_pt_off, const int64_t* d_npts, int32_t stride,
+                      const int32_t* d_fps_start, const float* d_fps_radius, const int32_t* d_rad_start, int32_t B, int32_t max_nobj,
+                      int32_t max_pts, int32_t cells, int32_t* d_fps_idx, int32_t* d_n_obj);
 
 #ifdef __cplusplus
 }
